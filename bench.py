@@ -10,6 +10,11 @@ A step = forward (logits + the fp32 distance map, the reference's forward contra
 GPU (1024x2048 latent pixels x 256 channels, 190 prototypes, 19 classes, bf16 features), followed — for
 N > 1 — by one RCCL all-reduce of the flat gradient bucket.  Inputs are resident in HBM before the timed
 region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line (its per-operator `kernels` and `roofline` figures
+come from HIP events of those same steps).  `--full` adds the measurements that take runs of their own: the secondary
+`modes` (other outputs, shapes and graph replays) and the CPU baseline.  `--dump-outputs DIR` writes what the last timed
+step returned to a caller as DIR/<name>.npy (see `dump_outputs`).
 """
 from __future__ import annotations
 
@@ -76,6 +81,29 @@ def cpu_baseline(C, P, S, K, sample_hw, reps=6):
         "sample": f"oracle fwd+bwd, 1x{C}x{H}x{W} latent px slice of the workload, P={P}, S={S}, fp32, "
                   f"{reps} reps after 1 warm-up, {dt:.2f} s/rep, torch {torch.__version__} CPU",
     }
+
+
+DUMP_PIXELS = 16384     # --dump-outputs: pixel sample of the per-pixel arrays (~30 MB of .npy at the default workload)
+
+
+def dump_outputs(out_dir, M, arrays):
+    """--dump-outputs: write {name: tensor} as out_dir/<name>.npy in float32.  Per-pixel arrays (logits [M, K]; the distance
+    map [1, P, H, W], the class-gathered [1, J, M] and dX [1, C, H, W]) are cut to one fixed, seeded sample of DUMP_PIXELS
+    pixels (all of them when M is smaller), pixel-major [n, ...]; the parameter gradients are written whole."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = min(M, DUMP_PIXELS)
+    idx = torch.randperm(M, generator=torch.Generator().manual_seed(20220227))[:n].sort().values
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if name == "logits":
+            t = t.reshape(M, -1)[idx.to(t.device)]
+        elif name in ("distances", "class_distances", "dX"):
+            t = t.reshape(-1, M)[:, idx.to(t.device)].t()
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().contiguous().cpu().numpy())
 
 
 def secondary_modes(dev, spx, F_, steps=5, warmup=2):
@@ -271,9 +299,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cityscapes_1024x2048_c256_p190_s1", choices=sorted(WORKLOADS))
     ap.add_argument("--x-dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-modes", action="store_true", help="skip the secondary `modes` measurements (logits-only forward, class-gathered "
-                    "steps, the reference's own shapes as graph replays)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the secondary `modes` (default workload, one GPU) "
+                    "and the CPU baseline (one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs and gradients to "
+                    "DIR/<name>.npy (float32; a fixed pixel sample of the per-pixel arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-modes", action="store_true", help="with --full: skip the secondary `modes` measurements (logits-only forward, "
+                    "class-gathered steps, the reference's own shapes as graph replays)")
     ap.add_argument("--grads", default="logits,dist", help="diagnostic only: which output gradients flow back")
     ap.add_argument("--outputs", default="logits,dist", help="diagnostic only: 'logits' = logits-only forward (no fp32 distance map); "
                     "'logits,class_dist' = class-gathered distances (SURVEY 8f-1: what the fused KLD consumes) instead of the P-wide map")
@@ -284,6 +316,8 @@ def main():
                     "matrix and exp + last_layer_group run fused in the kernels (spx_dist_fwd_group / spx_dist_bwd_group)")
     ap.add_argument("--freeze", default="", help="diagnostic only: comma list of x,bank,head to exclude from the backward")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` typed directly: start the N ranks ourselves (one process per GPU, the same
@@ -399,6 +433,7 @@ def main():
         torch.autograd.backward(outs, gouts)
         if world > 1:
             bucket.all_reduce()
+        return logits, dmap
 
     def fence():
         torch.cuda.synchronize()
@@ -419,8 +454,9 @@ def main():
     fence()
     F_.set_profile(prof)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()                     # the last timed step's forward outputs (its gradients stay on the tensors)
     fence()
     elapsed = time.perf_counter() - t0
     F_.set_profile(None)
@@ -428,6 +464,15 @@ def main():
         t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        arrays = {"logits": last[0], "class_distances" if gather is not None else "distances": last[1],
+                  "dX": x.grad, "dPrototypes": bank.grad}
+        if tail is None:
+            arrays["dLastLayer"] = head.grad
+        else:
+            arrays.update(dGroupProjection=head.grad, dLastLayer=tail.grad)
+        dump_outputs(args.dump_outputs, H * W, arrays)
+    del last
 
     # ---- per-operator durations from the HIP events of the timed steps ----
     per_op = {}
@@ -532,14 +577,14 @@ def main():
             }
         default_run = (args.workload == "cityscapes_1024x2048_c256_p190_s1" and args.x_dtype == "bf16" and args.outputs == "logits,dist"
                        and args.grads == "logits,dist" and not args.freeze and not args.group_tail)
-        if world == 1 and default_run and not args.no_modes:
+        if args.full and world == 1 and default_run and not args.no_modes:
             del x, g_logits, g_dist
             torch.cuda.empty_cache()
             try:
                 out["modes"] = secondary_modes(dev, spx, F_)
             except Exception as exc:                     # a secondary measurement must never cost the headline line
                 out["modes"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(C, P, S, K, (128, W) if H >= 128 else (H, W))
         print(json.dumps(out), flush=True)
     if world > 1:
