@@ -37,7 +37,7 @@ extern "C" {
 #endif
 
 #define SPX_MAX_PANELS 64   /* (scale, <=192-prototype block) work units per pixel tile */
-#define SPX_ABI_VERSION 15
+#define SPX_ABI_VERSION 16
 
 /* How the prototype bank is cut into MFMA panels.  Filled by spx_make_plan(). */
 typedef struct spx_plan {
@@ -384,6 +384,33 @@ int spx_kld_backward(const float* vals, const int32_t* labels, int32_t B, int32_
  * indices int64 [N, H, W] (lowest channel on ties); values fp32 [N, H, W] (the extremum; may be NULL). */
 int spx_upsample_argext(const float* src, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
                         int32_t take_max, int64_t* indices, float* values, void* stream);
+
+/* Evaluation metrics: the counters segmentation/eval_valid_multiscale.py:229-269 derives from the
+ * full-resolution maps above, accumulated without writing those maps.  Per image n, on the bilinear maps of
+ * spx_upsample_argext's arithmetic: pred = argmax_c logits, near = argmin_p distances (lowest index on ties).
+ * Counters are int64 and ADDED to (zero them once, call once per batch).
+ *   logits     fp32 [N, h, w, K] addressed through host_logit_strides = element strides of (n, k, y, x)
+ *   distances  fp32 [N, P, h, w] addressed through host_dist_strides  = element strides of (n, p, y, x); may be NULL
+ *   labels     [N, H, W] contiguous, label_bytes 1 (uint8), 4 (int32) or 8 (int64); 0 = void, c + 1 = class c, any
+ *              other non-zero value is non-void and matches no class (the reference's `ann != 0`)
+ *   proto_class int32 [P]: cls(p), the first argmax of prototype_class_identity[p] (:109-112)
+ *   conf       [K + 1, K]: conf[r, pred] += 1 per non-void pixel, r = ann - 1 for 1 <= ann <= K, else K (:236-243)
+ *   hits       [P]: hits[near] += 1 per pixel (void included) with cls(near) == pred (:245-253)
+ * Sizes: K <= 1024, P <= 4096, N*H*W < 2^31.  Entries of proto_class outside [0, K) match no class. */
+int spx_eval_accumulate(const float* logits, const int64_t* host_logit_strides, const float* distances,
+                        const int64_t* host_dist_strides, const int32_t* proto_class, const void* labels, int32_t label_bytes,
+                        int32_t N, int32_t K, int32_t P, int32_t h, int32_t w, int32_t H, int32_t W, int64_t* conf,
+                        int64_t* hits, void* stream);
+/* Top-k class purity of sample pixels (:255-269).  samples [N, S, 2] = (y, x) per image, int32 (sample_bytes 4) or int64
+ * (sample_bytes 8), duplicates allowed, N*S < 2^24.  Per
+ * sample: the P interpolated distances in ascending order, ties by lower index (stable), hit_j = cls(order_j) == pred;
+ * topk[k] += sum_{j <= k} hit_j for k < P; seen (int64 [1], may be NULL) += 1.  Samples outside [0, H) x [0, W) are
+ * skipped and not counted. */
+int spx_eval_topk(const float* logits, const int64_t* host_logit_strides, const float* distances, const int64_t* host_dist_strides,
+                  const int32_t* proto_class, const void* samples, int32_t sample_bytes, int32_t N, int32_t S, int32_t K,
+                  int32_t P, int32_t h, int32_t w, int32_t H, int32_t W, int64_t* topk, int64_t* seen, void* stream);
+/* Host-side check of a proto_class table before it is uploaded: every entry in [0, K) (non-zero status otherwise). */
+int spx_eval_check_classes(const int32_t* host_classes, int32_t P, int32_t K);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,9 @@ Public surface mirrors the reference's module/function names for this path:
     projection_simplex_sort, resize_label           (segmentation/utils.py, segmentation/data/dataset.py)
     KLDLoss, KLDLossGroup                           (segmentation/model/loss.py; KLDLoss also takes the class-gathered
                                                      ClassDistances of forward_from_conv_features(target_labels=...))
+    SegmentationMetrics                             (segmentation/eval_valid_multiscale.py:229-275: mIoU, per-class IoU,
+                                                     pixel accuracy, nearest-prototype counts, top-k class purity,
+                                                     counted on the GPU without full-resolution maps)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -26,6 +29,7 @@ from .functional import (  # noqa: F401
 )
 from .checkpoint import export_state, import_state, load_reference_state_dict  # noqa: F401
 from .loss import ClassDistances, KLDLoss, KLDLossGroup, PixelWiseCrossEntropyLoss  # noqa: F401
+from .metrics import SegmentationMetrics, SegmentationResult  # noqa: F401
 from .model import PPNet  # noqa: F401
 from .model_multiscale import PPNetMultiScale, construct_PPNet  # noqa: F401
 from .model_multiscale_group import PPNetMultiScaleGroup, construct_PPNet_Group  # noqa: F401

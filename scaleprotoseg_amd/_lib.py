@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libspx_hip.so")
 SPX_MAX_PANELS = 64
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class SpxError(RuntimeError):
@@ -57,6 +57,7 @@ _PCE = C.POINTER(SpxCe)
 _V = C.c_void_p
 _I = C.c_int32
 _F = C.c_float
+_PL = C.POINTER(C.c_int64)
 
 # name -> (restype, argtypes); must list every symbol include/spx_hip.h declares
 SIGNATURES = {
@@ -117,6 +118,9 @@ SIGNATURES = {
     "spx_dist_bwd_ce": (C.c_int, [_PP, _V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _V, _V, _V, _PCE, _V, _V, _V, _V, _F, _I, _V]),
     "spx_ce_fwd": (C.c_int, [_V, _V, C.c_int64, _I, _V, _V, _V, _V]),
     "spx_ce_bwd": (C.c_int, [_V, _V, _V, _V, C.c_int64, _I, _V, _V]),
+    "spx_eval_accumulate": (C.c_int, [_V, _PL, _V, _PL, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "spx_eval_topk": (C.c_int, [_V, _PL, _V, _PL, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "spx_eval_check_classes": (C.c_int, [C.POINTER(_I), _I, _I]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -669,6 +669,72 @@ int spx_upsample_argext(const float* src, int32_t N, int32_t C, int32_t h, int32
                                                  (hipStream_t)stream), "spx_upsample_argext");
 }
 
+#define SPX_EVAL_MAX_CLASSES 1024
+#define SPX_EVAL_MAX_PROTOTYPES 4096
+
+int spx_eval_check_classes(const int32_t* host_classes, int32_t P, int32_t K) {
+    if (!host_classes) return fail("spx_eval_check_classes: NULL table");
+    if (P < 1 || P > SPX_EVAL_MAX_PROTOTYPES || K < 1 || K > SPX_EVAL_MAX_CLASSES)
+        return fail("spx_eval_check_classes: bad sizes (P=%d K=%d; P <= %d, K <= %d)", P, K, SPX_EVAL_MAX_PROTOTYPES, SPX_EVAL_MAX_CLASSES);
+    for (int p = 0; p < P; ++p)
+        if (host_classes[p] < 0 || host_classes[p] >= K)
+            return fail("spx_eval_check_classes: prototype %d has class %d outside [0, %d)", p, host_classes[p], K);
+    return 0;
+}
+
+static int eval_check(const char* who, const float* logits, const int64_t* lst, const float* dist, const int64_t* dst,
+                      int32_t N, int32_t K, int32_t P, int32_t h, int32_t w, int32_t H, int32_t W) {
+    if (!logits || !lst) return fail("%s: NULL logits / logit strides", who);
+    if (N < 1 || K < 1 || h < 1 || w < 1 || H < 1 || W < 1) return fail("%s: empty input (N=%d K=%d h=%d w=%d H=%d W=%d)", who, N, K, h, w, H, W);
+    if (K > SPX_EVAL_MAX_CLASSES) return fail("%s: %d classes (at most %d)", who, K, SPX_EVAL_MAX_CLASSES);
+    if ((long long)N * H * W >= (1LL << 31) || (long long)h * w >= (1LL << 31)) return fail("%s: maps too large", who);
+    for (int i = 0; i < 4; ++i)
+        if (lst[i] < 0) return fail("%s: negative logit stride", who);
+    // the kernels address inside one image with 32-bit offsets
+    if ((long long)(K - 1) * lst[1] + (long long)(h - 1) * lst[2] + (long long)(w - 1) * lst[3] >= (1LL << 31))
+        return fail("%s: one image of logits spans more than 2^31 elements", who);
+    if (dist) {
+        if (!dst) return fail("%s: NULL distance strides", who);
+        if (P < 1 || P > SPX_EVAL_MAX_PROTOTYPES) return fail("%s: %d prototypes (1..%d)", who, P, SPX_EVAL_MAX_PROTOTYPES);
+        for (int i = 0; i < 4; ++i)
+            if (dst[i] < 0) return fail("%s: negative distance stride", who);
+        if ((long long)(P - 1) * dst[1] + (long long)(h - 1) * dst[2] + (long long)(w - 1) * dst[3] >= (1LL << 31))
+            return fail("%s: one image of distances spans more than 2^31 elements", who);
+    }
+    return 0;
+}
+
+int spx_eval_accumulate(const float* logits, const int64_t* host_logit_strides, const float* distances,
+                        const int64_t* host_dist_strides, const int32_t* proto_class, const void* labels, int32_t label_bytes,
+                        int32_t N, int32_t K, int32_t P, int32_t h, int32_t w, int32_t H, int32_t W, int64_t* conf,
+                        int64_t* hits, void* stream) {
+    static const char* who = "spx_eval_accumulate";
+    if (!labels || !conf) return fail("%s: NULL labels / confusion counters", who);
+    if (distances && (!proto_class || !hits)) return fail("%s: distances without prototype classes / hit counters", who);
+    if (label_bytes != 1 && label_bytes != 4 && label_bytes != 8)
+        return fail("%s: label byte code %d (1 = uint8, 4 = int32, 8 = int64)", who, label_bytes);
+    if (int e = eval_check(who, logits, host_logit_strides, distances, host_dist_strides, N, K, P, h, w, H, W)) return e;
+    return hip_status(spx_launch_eval_accumulate(logits, (const long long*)host_logit_strides, distances,
+                                                 (const long long*)host_dist_strides, proto_class, labels, label_bytes, N, K, P,
+                                                 h, w, H, W, (unsigned long long*)conf, (unsigned long long*)hits,
+                                                 (hipStream_t)stream), who);
+}
+
+int spx_eval_topk(const float* logits, const int64_t* host_logit_strides, const float* distances, const int64_t* host_dist_strides,
+                  const int32_t* proto_class, const void* samples, int32_t sample_bytes, int32_t N, int32_t S, int32_t K,
+                  int32_t P, int32_t h, int32_t w, int32_t H, int32_t W, int64_t* topk, int64_t* seen, void* stream) {
+    static const char* who = "spx_eval_topk";
+    if (!distances || !proto_class || !samples || !topk) return fail("%s: NULL distances / prototype classes / samples / counters", who);
+    if (sample_bytes != 4 && sample_bytes != 8) return fail("%s: sample byte code %d (4 = int32, 8 = int64)", who, sample_bytes);
+    // a workgroup's u32 top-k copy grows by at most P per sample: with N*S < 2^24 spread over min(N*S, 256) workgroups it
+    // takes at most 2^16 samples, 2^16 * 4096 < 2^32
+    if (S < 1 || (long long)N * S >= (1LL << 24)) return fail("%s: bad sample count (N=%d S=%d; N*S < 2^24)", who, N, S);
+    if (int e = eval_check(who, logits, host_logit_strides, distances, host_dist_strides, N, K, P, h, w, H, W)) return e;
+    return hip_status(spx_launch_eval_topk(logits, (const long long*)host_logit_strides, distances, (const long long*)host_dist_strides,
+                                           proto_class, samples, sample_bytes, N, S, K, P, h, w, H, W, (unsigned long long*)topk,
+                                           (unsigned long long*)seen, (hipStream_t)stream), who);
+}
+
 static int kld_check(const char* who, const float* vals, const int32_t* labels, int32_t B, int32_t J, int32_t HW, int32_t K,
                      const void* out, int pairs) {
     if (!vals || !labels || !out) return fail("%s: NULL buffer", who);

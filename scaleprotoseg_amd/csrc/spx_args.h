@@ -148,6 +148,12 @@ hipError_t spx_launch_push_argmin(const float* dist, const int32_t* labels, cons
 hipError_t spx_launch_argmin_images(const float* values, int N, int P, int64_t* best, hipStream_t s);
 hipError_t spx_launch_upsample_argext(const float* src, int N, int C, int h, int w, int H, int W, int take_max,
                                       int64_t* idx, float* val, hipStream_t s);
+hipError_t spx_launch_eval_accumulate(const float* logits, const long long* lst, const float* dist, const long long* dst,
+                                      const int32_t* pcls, const void* labels, int label_bytes, int N, int K, int P, int h, int w,
+                                      int H, int W, unsigned long long* conf, unsigned long long* hits, hipStream_t s);
+hipError_t spx_launch_eval_topk(const float* logits, const long long* lst, const float* dist, const long long* dst,
+                                const int32_t* pcls, const void* samples, int sample_bytes, int N, int S, int K, int P, int h,
+                                int w, int H, int W, unsigned long long* topk, unsigned long long* seen, hipStream_t s);
 hipError_t spx_launch_sum_groups(const float* parts, size_t n, int groups, float* out, hipStream_t s);
 int spx_split_groups(const spx_plan& pl, int B, int HW, int32_t* group_first);
 hipError_t spx_launch_group_tail(const float* parts, int groups, long long M, int U, const float* Wg, int K2, float* gact,
