@@ -37,7 +37,8 @@ extern "C" {
 #endif
 
 #define SPX_MAX_PANELS 64   /* (scale, <=192-prototype block) work units per pixel tile */
-#define SPX_ABI_VERSION 16
+#define SPX_ABI_VERSION 17
+#define SPX_PRUNE_MAX_K 64   /* largest k of spx_prune_merge */
 
 /* How the prototype bank is cut into MFMA panels.  Filled by spx_make_plan(). */
 typedef struct spx_plan {
@@ -411,6 +412,45 @@ int spx_eval_topk(const float* logits, const int64_t* host_logit_strides, const 
                   int32_t P, int32_t h, int32_t w, int32_t H, int32_t W, int64_t* topk, int64_t* seen, void* stream);
 /* Host-side check of a proto_class table before it is uploaded: every entry in [0, K) (non-zero status otherwise). */
 int spx_eval_check_classes(const int32_t* host_classes, int32_t P, int32_t K);
+
+/* Prototype pruning: the k nearest training patches of every prototype (find_nearest.py:88-225 with full_save=True, as
+ * prune.py:22-30 calls it).  Per image and prototype the nearest latent pixel is kept as one 64-bit key:
+ *   bits 63..32 = float bits of d | void << 31, bits 31..0 = flat latent index i*W + j.
+ * d >= 0, so the bits order as the value; void = the pixel's label equals void_label.  The minimum key is the reference's
+ * np.amin / np.argmin of `proto_dist_ + 10e6 * (interpolated_y == -1)` (:118-142, a float64 sum): the nearest non-void
+ * pixel of an image with any; for an all-void image the nearest pixel, ranked after every non-void candidate; the
+ * lowest flat index on ties (first occurrence).  Integer atomic minima: run-to-run identical.
+ * spx_prune_argmin: on a distance map fp32 [B, P, HW] already in HBM (as spx_push_argmin serves the push); labels
+ * int32 [B, HW] at the latent resolution (resize_label, dataset.py:22-30); keys uint64 [B, P] written here. */
+int spx_prune_argmin(const float* distances, const int32_t* labels, int32_t void_label, int32_t B, int32_t P, int32_t HW,
+                     uint64_t* keys, void* stream);
+/* The same keys FUSED into the distance kernel (the P-wide map is never written), bit-identical to spx_prune_argmin on the
+ * map spx_dist_fwd writes.  Arguments as spx_dist_push_min; proto_key: any table of the plan's padded rows (read, not
+ * used for masking).  keys uint64 [B, P] written here. */
+int spx_dist_prune_min(const spx_plan* plan, const void* x, int32_t x_dtype, int32_t B, int32_t HW, const void* packed_bank,
+                       const float* packed_p2, const int32_t* labels, int32_t void_label, const uint32_t* proto_key, uint64_t* keys,
+                       void* stream);
+/* Footprint of every key's latent cell (i, j) = (flat / W, flat % W) in the full-resolution label (:145-158), computed in
+ * float64 exactly as written: ph = Hf / H, pw = Wf / W; box = (int(i*ph), int((i+1)*ph), int(j*pw), int((j+1)*pw)),
+ * stops clamped to Hf / Wf as a NumPy slice clamps them.  labels int32 [B, Hf, Wf] in the reference's convention there
+ * (convert_targets(target) - 1: void = -1); target_class int32 [P] = argmax of prototype_class_identity[p] (0 for an
+ * all-zero row).  Outputs: box int32 [B, P, 4] (h0, h1, w0, w1; zero area = empty footprint, the candidate the
+ * reference skips, :168-169) and label int32 [B, P] (:206-213): target_class[p] if any footprint pixel equals it, else
+ * the most frequent value, the smallest value on a count tie (np.unique + argmax); 0 for an empty footprint.  Any int32
+ * value counts as a value; values -1 .. 1022 are counted in an LDS histogram, others pairwise. */
+int spx_prune_footprint(const int32_t* labels, int32_t B, int32_t Hf, int32_t Wf, int32_t H, int32_t W, int32_t P,
+                        const uint64_t* keys, const int32_t* target_class, int32_t* label, int32_t* box, void* stream);
+/* Merge the candidates of B consecutive images (global indices image0 .. image0 + B - 1, later than every image already in
+ * the table) into the running table of the k nearest per prototype (:222-225), 1 <= k <= SPX_PRUNE_MAX_K.  Table rows
+ * [P, k]: table_key uint64 (a key above), table_image int64 (-1 = empty slot; empty slots come last), table_label int32,
+ * table_box int32 [.., 4], table_cell int32 [.., 2] = (i, j) for a grid of width W.  Initialise key to all ones and image
+ * to -1.  Candidates with an empty footprint are skipped.  A row holds the k smallest candidates by (key bits 63..32,
+ * image), in that order: a candidate replaces the last kept one only if its key is strictly smaller, so on an equal
+ * distance the earlier image stays (heapq.heappushpop).  The reference evicts whichever of several entries tied at the
+ * k-th distance sits at its heap's root; this rule keeps the earliest of them.  box / table_box 16-byte aligned. */
+int spx_prune_merge(const uint64_t* keys, const int32_t* label, const int32_t* box, int32_t B, int32_t P, int32_t W, int64_t image0,
+                    int32_t k, uint64_t* table_key, int64_t* table_image, int32_t* table_label, int32_t* table_box, int32_t* table_cell,
+                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,9 @@ Public surface mirrors the reference's module/function names for this path:
     SegmentationMetrics                             (segmentation/eval_valid_multiscale.py:229-275: mIoU, per-class IoU,
                                                      pixel accuracy, nearest-prototype counts, top-k class purity,
                                                      counted on the GPU without full-resolution maps)
+    find_k_nearest_patches_to_prototypes, prune_prototypes
+                                                    (find_nearest.py, prune.py: k nearest training patches per prototype
+                                                     and class-purity pruning, searched and merged on the GPU)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -23,6 +26,10 @@ from .functional import (  # noqa: F401
     argmin_over_images,
     class_gather_table,
     proto_head_forward,
+    decode_prune_keys,
+    prune_footprint,
+    prune_nearest_from_features,
+    prune_nearest_from_map,
     push_masked_argmin,
     push_min_from_features,
     upsample_argext,
@@ -39,6 +46,7 @@ from .push import (  # noqa: F401
     min_across_dataset,
     push_prototypes_multiscale,
 )
+from .prune import NearestPatches, find_k_nearest_patches_to_prototypes, prune_prototypes  # noqa: F401
 from .utils import projection_simplex_sort, resize_label  # noqa: F401
 
 __version__ = "0.1.0"

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libspx_hip.so")
 SPX_MAX_PANELS = 64
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class SpxError(RuntimeError):
@@ -121,6 +121,10 @@ SIGNATURES = {
     "spx_eval_accumulate": (C.c_int, [_V, _PL, _V, _PL, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
     "spx_eval_topk": (C.c_int, [_V, _PL, _V, _PL, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
     "spx_eval_check_classes": (C.c_int, [C.POINTER(_I), _I, _I]),
+    "spx_prune_argmin": (C.c_int, [_V, _V, _I, _I, _I, _I, _V, _V]),
+    "spx_dist_prune_min": (C.c_int, [_PP, _V, _I, _I, _I, _V, _V, _V, _I, _V, _V, _V]),
+    "spx_prune_footprint": (C.c_int, [_V, _I, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V]),
+    "spx_prune_merge": (C.c_int, [_V, _V, _V, _I, _I, _I, C.c_int64, _I, _V, _V, _V, _V, _V, _V]),
 }
 
 _lib: Optional[C.CDLL] = None

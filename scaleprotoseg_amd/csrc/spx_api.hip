@@ -223,7 +223,8 @@ static int dist_fwd_impl(const spx_plan* pl, const void* x, int32_t x_dtype, int
                          const int32_t* labels, const uint32_t* proto_key, int32_t J, float* cls_dist,
                          float* activations, float* logits, float epsilon, int32_t act_fn, void* stream,
                          SpxTailFwd tail = SpxTailFwd{nullptr, 0, nullptr}, const spx_ce* ce = nullptr, void* split_ws = nullptr,
-                         bool keep_partials = false, unsigned long long* push_keys = nullptr, float push_max = 0.0f, int push_void = -1, int push_K = 0) {
+                         bool keep_partials = false, unsigned long long* push_keys = nullptr, float push_max = 0.0f, int push_void = -1, int push_K = 0,
+                         int push_prune = 0) {
     if (check_plan(pl)) return 1;
     if (!x || !packed_bank || !packed_p2) return fail("spx_dist_fwd: NULL operand");
     if (x_dtype != 0 && x_dtype != 1) return fail("spx_dist_fwd: x_dtype %d (0 = bf16, 1 = fp32)", x_dtype);
@@ -254,6 +255,7 @@ static int dist_fwd_impl(const spx_plan* pl, const void* x, int32_t x_dtype, int
     a.push_max = push_max;
     a.push_void = push_void;
     a.push_K = push_K;
+    a.push_prune = push_prune;
     a.packed_tail = (const char*)tail.packed_tail;
     a.gact = tail.gact;
     a.K2 = tail.K2;
@@ -366,6 +368,20 @@ int spx_dist_push_min(const spx_plan* pl, const void* x, int32_t x_dtype, int32_
                       1e-4f, 0, stream, SpxTailFwd{nullptr, 0, nullptr}, nullptr, nullptr, false, (unsigned long long*)scratch, max_dist, void_class, K))
         return 1;
     return hip_status(spx_launch_push_finalize(scratch, (int)n, indices, values, (hipStream_t)stream), "spx_dist_push_min (decode)");
+}
+
+int spx_dist_prune_min(const spx_plan* pl, const void* x, int32_t x_dtype, int32_t B, int32_t HW, const void* packed_bank,
+                       const float* packed_p2, const int32_t* labels, int32_t void_label, const uint32_t* proto_key, uint64_t* keys,
+                       void* stream) {
+    if (check_cls("spx_dist_prune_min", labels, proto_key, 1, HW)) return 1;
+    if (!keys) return fail("spx_dist_prune_min: NULL keys");
+    if (check_plan(pl)) return 1;
+    if (B < 1 || B > 65535) return fail("spx_dist_prune_min: B %d out of range", B);
+    const size_t n = (size_t)B * pl->num_prototypes;
+    if (hip_status(hipMemsetAsync(keys, 0xFF, n * sizeof(uint64_t), (hipStream_t)stream), "spx_dist_prune_min (key fill)")) return 1;
+    return dist_fwd_impl(pl, x, x_dtype, B, HW, packed_bank, packed_p2, nullptr, nullptr, labels, proto_key, 1, nullptr, nullptr,
+                         nullptr, 1e-4f, 0, stream, SpxTailFwd{nullptr, 0, nullptr}, nullptr, nullptr, false,
+                         (unsigned long long*)keys, 0.0f, void_label, 1, 1);
 }
 
 static int dist_bwd_impl(const spx_plan* pl, const void* x, int32_t x_dtype, int32_t B, int32_t HW,
@@ -652,6 +668,38 @@ int spx_push_argmin(const float* distances, const int32_t* labels, const float* 
     return hip_status(spx_launch_push_argmin(distances, labels, class_identity, B, P, K, HW, void_class, max_dist,
                                              indices, values, scratch, (hipStream_t)stream),
                       "spx_push_argmin");
+}
+
+int spx_prune_argmin(const float* distances, const int32_t* labels, int32_t void_label, int32_t B, int32_t P, int32_t HW,
+                     uint64_t* keys, void* stream) {
+    if (!distances || !labels || !keys) return fail("spx_prune_argmin: NULL buffer");
+    if (B < 1 || P < 1 || HW < 1) return fail("spx_prune_argmin: empty input (B=%d P=%d HW=%d)", B, P, HW);
+    if (P > 0x7FFF8 || B > 65535) return fail("spx_prune_argmin: grid too large (B=%d P=%d)", B, P);
+    return hip_status(spx_launch_prune_argmin(distances, labels, void_label, B, P, HW, keys, (hipStream_t)stream), "spx_prune_argmin");
+}
+
+int spx_prune_footprint(const int32_t* labels, int32_t B, int32_t Hf, int32_t Wf, int32_t H, int32_t W, int32_t P,
+                        const uint64_t* keys, const int32_t* target_class, int32_t* label, int32_t* box, void* stream) {
+    if (!labels || !keys || !target_class || !label || !box) return fail("spx_prune_footprint: NULL buffer");
+    if (B < 1 || P < 1 || Hf < 1 || Wf < 1 || H < 1 || W < 1)
+        return fail("spx_prune_footprint: empty input (B=%d P=%d Hf=%d Wf=%d H=%d W=%d)", B, P, Hf, Wf, H, W);
+    if (B > 65535 || P > 0x7FFFFFFF / 4) return fail("spx_prune_footprint: grid too large (B=%d P=%d)", B, P);
+    if ((long long)H * W >= (1LL << 31)) return fail("spx_prune_footprint: latent grid too large");
+    return hip_status(spx_launch_prune_footprint(labels, B, Hf, Wf, H, W, P, keys, target_class, label, box, (hipStream_t)stream),
+                      "spx_prune_footprint");
+}
+
+int spx_prune_merge(const uint64_t* keys, const int32_t* label, const int32_t* box, int32_t B, int32_t P, int32_t W, int64_t image0,
+                    int32_t k, uint64_t* table_key, int64_t* table_image, int32_t* table_label, int32_t* table_box, int32_t* table_cell,
+                    void* stream) {
+    if (!keys || !label || !box || !table_key || !table_image || !table_label || !table_box || !table_cell)
+        return fail("spx_prune_merge: NULL buffer");
+    if (B < 1 || P < 1 || W < 1) return fail("spx_prune_merge: empty input (B=%d P=%d W=%d)", B, P, W);
+    if (k < 1 || k > SPX_PRUNE_MAX_K) return fail("spx_prune_merge: k %d outside 1..%d", k, SPX_PRUNE_MAX_K);
+    if (image0 < 0) return fail("spx_prune_merge: negative image index");
+    if ((((uintptr_t)box) | ((uintptr_t)table_box)) & 15) return fail("spx_prune_merge: box tables must be 16-byte aligned");
+    return hip_status(spx_launch_prune_merge(keys, label, box, B, P, W, image0, k, table_key, table_image, table_label, table_box,
+                                             table_cell, (hipStream_t)stream), "spx_prune_merge");
 }
 
 int spx_argmin_images(const float* values, int32_t N, int32_t P, int64_t* best, void* stream) {

@@ -25,6 +25,9 @@ struct SpxFwdArgs {
     unsigned long long* push_keys;   // [B, P], caller-initialised to all ones; NULL = off
     float push_max;                  // the reference's max_dist (1e10)
     int push_void, push_K;           // label decode of spx_push_argmin: labels are raw (void_class dropped from 0..K), see spx_hip.h
+    // prune mode of the same epilogue (spx_dist_prune_min): no class mask; a pixel whose label is push_void ranks after every
+    // other pixel (key: float bits of d | void << 31, see spx_prune.hip); push_max / push_K unused
+    int push_prune;
     // grouping-head tail (spx_dist_fwd_group): logits = W_g . exp(units), units = the head product
     const char* packed_tail;   // W_g A-fragments (spx_pack_group_tail); NULL = no tail
     float* gact;               // [B*HW, U] exp(units) (optional)
@@ -159,6 +162,12 @@ int spx_split_groups(const spx_plan& pl, int B, int HW, int32_t* group_first);
 hipError_t spx_launch_group_tail(const float* parts, int groups, long long M, int U, const float* Wg, int K2, float* gact,
                                  float* logits, const int32_t* labels, float* lse, int32_t* pred, float* partials, hipStream_t s);
 hipError_t spx_launch_push_finalize(const uint64_t* scratch, int n, int64_t* idx, float* val, hipStream_t s);
+hipError_t spx_launch_prune_argmin(const float* dist, const int32_t* labels, int void_label, int B, int P, int HW,
+                                   uint64_t* keys, hipStream_t s);
+hipError_t spx_launch_prune_footprint(const int32_t* labels, int B, int Hf, int Wf, int H, int W, int P, const uint64_t* keys,
+                                      const int32_t* target_class, int32_t* label, int32_t* box, hipStream_t s);
+hipError_t spx_launch_prune_merge(const uint64_t* keys, const int32_t* label, const int32_t* box, int B, int P, int W, long long image0,
+                                  int k, uint64_t* tkey, int64_t* timg, int32_t* tlabel, int32_t* tbox, int32_t* tcell, hipStream_t s);
 #ifdef SPX_DIAG
 void spx_gemm_force(int wm, int splits);
 #endif

@@ -62,7 +62,8 @@ __host__ __device__ constexpr int spx_fwd_lds_bytes() {
 // GATHER: class-gathered distances (spx_dist_fwd_cls) instead of the P-wide map.
 // (2-block panels with a one-block head fit 168 VGPRs: three waves per SIMD.)
 // ACT: the [pixel][P] activation output is requested (kept out of the default instance: its code costs registers).
-template <int NPB, int NCB, bool XF32, int VM, int SPLIT, bool GATHER, bool ACT>
+// PRUNE: the prune mode of the fused push (spx_dist_prune_min); its own instances, so the others compile as without it.
+template <int NPB, int NCB, bool XF32, int VM, int SPLIT, bool GATHER, bool ACT, bool PRUNE>
 __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WAVES) * SPLIT) void spx_fwd_kernel(const SpxFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT = 256 * SPLIT, NH = NPB / SPLIT;
@@ -154,6 +155,7 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
             int c = li;
             if (a.push_void >= 0) c = li == a.push_void ? -1 : (li < a.push_void ? li : li - 1);
             lab16 = (px_ok && c >= 0 && c < a.push_K) ? (uint32_t)c : 0xFFFEu;
+            if (PRUNE) lab16 = li == a.push_void ? 0x80000000u : 0u;   // prune mode: the void bit of the key
         }
         voff_c = px_ok ? (uint32_t)px * 4u : SPX_OOB;          // [slot][px] planes: a wave's 32 pixels are one 128-B run
         if (a.cls_dist && blockIdx.y == 0) {
@@ -257,7 +259,35 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
 #pragma unroll
                     for (int reg = 0; reg < 16; ++reg) av[reg] = -dv[reg];
                 }
-                if (GATHER && a.push_keys) {
+                if (PRUNE && GATHER && a.push_keys) {
+                    // Fused k-nearest search of the pruning (find_nearest.py:118-142): no class mask, the key of a pixel is
+                    // float bits of d | void << 31 (d >= 0, so the bits order as the value; void pixels rank after all others),
+                    // reduced over the wave's 32 pixels as an unsigned minimum, lowest pixel index on ties, then as the push.
+                    uint32_t* const sc = (uint32_t*)(smem + wave * SPX_FWD_TSCRATCH);
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg)
+                        sc[((reg & 3) + 8 * (reg >> 2) + 4 * h) * SPX_FWD_TROW + r] = px_ok ? (__float_as_uint(dv[reg] + 0.0f) | lab16) : 0xFFFFFFFFu;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int row = 8 * q + (lane >> 3);
+                        const u32x4 v = *(const u32x4*)(sc + row * SPX_FWD_TROW + 4 * (lane & 7));
+                        uint32_t best = v[0];
+                        int bi = pxw;
+#pragma unroll
+                        for (int e = 1; e < 4; ++e)
+                            if (v[e] < best) { best = v[e]; bi = pxw + e; }
+#pragma unroll
+                        for (int m = 1; m <= 4; m <<= 1) {
+                            const uint32_t ov = __shfl_xor(best, m);
+                            const int oi = __shfl_xor(bi, m);
+                            if (ov < best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+                        }
+                        if ((lane & 7) == 0) {
+                            const unsigned long long key = ((unsigned long long)best << 32) | (uint32_t)bi;
+                            __hip_atomic_fetch_min(pmin + pb * 32 + row, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                    }
+                } else if (GATHER && a.push_keys) {
                     // Fused prototype push (push_multiscale_optimization.py:74-91): v = d + max_dist * (1 - mask) with the
                     // reference's rounding, its minimum over the wave's 32 pixels per prototype row (lowest pixel index on
                     // ties) as an integer minimum into the workgroup's LDS row table; the table meets the global one once
@@ -602,24 +632,29 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
 #endif
 }
 
-template <int NPB, int NCB, int SPLIT, bool GATHER, bool ACT>
+template <int NPB, int NCB, int SPLIT, bool GATHER, bool ACT, bool PRUNE = false>
 static hipError_t launch_fwd_ga(const SpxFwdArgs& a, int x_dtype, dim3 grid, hipStream_t s) {
     constexpr size_t lds = (size_t)spx_fwd_lds_bytes<NPB, NCB, SPLIT>();
     const dim3 blk(256 * SPLIT);
     // a.vec_ok: 0 = element-wise staging, 1 = vector staging, 2 = vector staging with a ragged image end (H*W % 8 != 0)
     if (x_dtype == 1) {
-        if (a.vec_ok == 2) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, true, 2, SPLIT, GATHER, ACT>), grid, blk, lds, s, a);
-        else if (a.vec_ok) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, true, 1, SPLIT, GATHER, ACT>), grid, blk, lds, s, a);
-        else hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, true, 0, SPLIT, GATHER, ACT>), grid, blk, lds, s, a);
+        if (a.vec_ok == 2) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, true, 2, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
+        else if (a.vec_ok) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, true, 1, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
+        else hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, true, 0, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
     } else {
-        if (a.vec_ok == 2) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, false, 2, SPLIT, GATHER, ACT>), grid, blk, lds, s, a);
-        else if (a.vec_ok) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, false, 1, SPLIT, GATHER, ACT>), grid, blk, lds, s, a);
-        else hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, false, 0, SPLIT, GATHER, ACT>), grid, blk, lds, s, a);
+        if (a.vec_ok == 2) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, false, 2, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
+        else if (a.vec_ok) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, false, 1, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
+        else hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, false, 0, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
     }
     return hipGetLastError();
 }
 template <int NPB, int NCB, int SPLIT>
 static hipError_t launch_fwd_x(const SpxFwdArgs& a, int x_dtype, dim3 grid, hipStream_t s) {
+    if (a.labels && a.push_keys && a.push_prune) {
+        // the prune mode runs on a one-row head layout (no logits): only one-class-block instances exist
+        if constexpr (NCB == 1) return launch_fwd_ga<NPB, NCB, SPLIT, true, false, true>(a, x_dtype, grid, s);
+        return hipErrorInvalidValue;
+    }
     if (a.labels) return a.act ? launch_fwd_ga<NPB, NCB, SPLIT, true, true>(a, x_dtype, grid, s)
                                : launch_fwd_ga<NPB, NCB, SPLIT, true, false>(a, x_dtype, grid, s);
     return a.act ? launch_fwd_ga<NPB, NCB, SPLIT, false, true>(a, x_dtype, grid, s)

@@ -154,6 +154,20 @@ def reduce_push_candidates(
     return imgs[win_rank, ar], vals[win_rank, ar], flats[win_rank, ar]
 
 
+def reduce_prune_tables(packed: torch.Tensor, k: int, group=None) -> torch.Tensor:
+    """Combine the per-rank k-nearest tables of the pruning search (prune.py) into the global one.
+
+    packed int64 [P, k, 9] (key, GLOBAL image index, label, box, cell; see ``prune.NearestTable.packed``).  One
+    all-gather, then the table's own rule (``prune.merge_nearest_tables``: the k smallest by (distance key, image)).
+    Shards are contiguous ranges of the image list, so the result equals the single-process table; identical on every
+    rank."""
+    from .prune import merge_nearest_tables
+
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return packed
+    return merge_nearest_tables(_all_gather(packed.contiguous(), group), k)
+
+
 def gather_push_patches(local_patches: torch.Tensor, owner_mask: torch.Tensor, group=None) -> torch.Tensor:
     """[P, Cs] feature vectors: each rank fills the rows it owns (owner_mask), zeros elsewhere; a sum
     all-reduce assembles the full bank (exact: every row has exactly one non-zero contributor)."""

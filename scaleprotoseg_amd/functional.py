@@ -873,6 +873,104 @@ def push_min_from_features(
     return idx, val
 
 
+def _prune_labels(labels: torch.Tensor, B: int, H: int, W: int, dev) -> torch.Tensor:
+    if tuple(labels.shape) != (B, H, W):
+        raise SpxError(f"labels must be [{B}, {H}, {W}], got {tuple(labels.shape)}")
+    return labels.to(device=dev, dtype=torch.int32).reshape(B, H * W).contiguous()
+
+
+def prune_nearest_from_map(distances: torch.Tensor, labels: torch.Tensor, *, void_label: int = -1) -> torch.Tensor:
+    """Per (image, prototype) nearest latent pixel of the pruning's k-nearest search (find_nearest.py:118-142) on a distance
+    map already on the GPU: keys int64 [B, P] (the uint64 bits of spx_prune_argmin: float bits of d | void << 31 above,
+    flat index i*W + j below; ``decode_prune_keys`` splits them).  ``labels`` [B, H, W] at the latent resolution; a pixel is
+    void when its label equals ``void_label`` (void pixels stay candidates, ranked after every non-void one)."""
+    lib = _lib.load()
+    if distances.dim() != 4:
+        raise SpxError("distances must be [B, P, H, W]")
+    if not distances.is_cuda:
+        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    B, P, H, W = distances.shape
+    d = distances.detach().contiguous().float()
+    lab = _prune_labels(labels, B, H, W, d.device)
+    keys = torch.empty((B, P), dtype=torch.int64, device=d.device)
+    _lib.check(lib.spx_prune_argmin(_lib.ptr(d), _lib.ptr(lab), int(void_label), B, P, H * W, _lib.ptr(keys), _lib.stream_ptr()))
+    return keys
+
+
+_prune_rows_cache: Dict[Tuple[int, str], torch.Tensor] = {}
+
+
+def prune_nearest_from_features(
+    conv_features: torch.Tensor,
+    bank: torch.Tensor,
+    layout: BankLayout,
+    labels: torch.Tensor,
+    *,
+    void_label: int = -1,
+) -> torch.Tensor:
+    """``prune_nearest_from_map`` computed INSIDE the distance kernel from the features (spx_dist_prune_min): the
+    [B, P, H, W] map is never written.  Bit-identical to ``prune_nearest_from_map`` on the map ``proto_head_forward``
+    writes."""
+    lib = _lib.load()
+    if not conv_features.is_cuda:
+        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    B, HW = _check_x(conv_features, layout)
+    H, W = conv_features.shape[2], conv_features.shape[3]
+    x = conv_features.detach().contiguous()
+    dev = x.device
+    lab = _prune_labels(labels, B, H, W, dev)
+    P = layout.num_prototypes
+    bank2d = bank.detach().reshape(P, layout.channels_per_scale).contiguous().float()
+    plan = layout.plan()
+    plan_key = (layout.num_prototypes, layout.num_classes, layout.num_scales, layout.channels_per_scale,
+                tuple(tuple(int(v) for v in r_) for r_ in layout.scale_ranges))
+    packs = _cached_packs(plan_key, plan, bank, None, None, bank2d, None, None, False)
+    nrows = plan.npanels * plan.npb * 32
+    rows = _prune_rows_cache.get((nrows, str(dev)))
+    if rows is None:                     # the kernel reads a row table of the plan; the prune mode masks nothing with it
+        rows = _prune_rows_cache[(nrows, str(dev))] = torch.zeros((nrows,), dtype=torch.int32, device=dev)
+    keys = torch.empty((B, P), dtype=torch.int64, device=dev)
+    _lib.check(lib.spx_dist_prune_min(C.byref(plan), _lib.ptr(x), _x_dtype_code(x), B, HW, _lib.ptr(packs.bank), _lib.ptr(packs.p2),
+                                      _lib.ptr(lab), int(void_label), _lib.ptr(rows), _lib.ptr(keys), _lib.stream_ptr()))
+    return keys
+
+
+def decode_prune_keys(keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(flat index int64, distance fp32, void bool) of keys from ``prune_nearest_from_map`` / ``_from_features``."""
+    hi = (keys >> 32) & 0xFFFFFFFF
+    d = (hi & 0x7FFFFFFF).to(torch.int32).view(torch.float32)
+    return keys & 0xFFFFFFFF, d, (hi >> 31) == 1
+
+
+def prune_footprint(labels: torch.Tensor, keys: torch.Tensor, grid: Tuple[int, int], target_class: torch.Tensor,
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(label int32 [B, P], box int32 [B, P, 4]) of every key's latent cell in the full-resolution ``labels`` [B, Hf, Wf]
+    (find_nearest.py:145-158, :206-213; see spx_prune_footprint): box (h0, h1, w0, w1) in float64 arithmetic, zero area =
+    empty footprint (the candidate the reference skips); label = ``target_class[p]`` if present in the footprint, else its
+    most frequent value (smallest on a tie).  ``labels`` in the reference's convention there (void = -1)."""
+    lib = _lib.load()
+    if labels.dim() != 3:
+        raise SpxError("labels must be [B, Hf, Wf]")
+    if not (labels.is_cuda and keys.is_cuda):
+        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    B, Hf, Wf = labels.shape
+    H, W = int(grid[0]), int(grid[1])
+    if keys.dim() != 2 or keys.shape[0] != B or keys.dtype != torch.int64:
+        raise SpxError(f"keys must be int64 [{B}, P], got {keys.dtype} {tuple(keys.shape)}")
+    P = keys.shape[1]
+    if tuple(target_class.shape) != (P,):
+        raise SpxError(f"target_class must be [{P}]")
+    dev = keys.device
+    lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+    tc = target_class.to(device=dev, dtype=torch.int32).contiguous()
+    k = keys.contiguous()
+    out_label = torch.empty((B, P), dtype=torch.int32, device=dev)
+    out_box = torch.empty((B, P, 4), dtype=torch.int32, device=dev)
+    _lib.check(lib.spx_prune_footprint(_lib.ptr(lab), B, Hf, Wf, H, W, P, _lib.ptr(k), _lib.ptr(tc), _lib.ptr(out_label),
+                                       _lib.ptr(out_box), _lib.stream_ptr()))
+    return out_label, out_box
+
+
 def argmin_over_images(values: torch.Tensor) -> torch.Tensor:
     """tot_dist.argmin(dim=0) with lowest-image tie-break; push_multiscale_optimization.py:135-137."""
     lib = _lib.load()
