@@ -452,6 +452,45 @@ int spx_prune_merge(const uint64_t* keys, const int32_t* label, const int32_t* b
                     int32_t k, uint64_t* table_key, int64_t* table_image, int32_t* table_label, int32_t* table_box, int32_t* table_cell,
                     void* stream);
 
+/* Weight-side regularisers of the training objective (additive to ABI 17).  For class block j (the j-th class that owns
+ * prototypes), G groups, n_j columns, w[g][c] = wd[u0_j + g][flat_col[off_j + c]]:
+ *   term 0 EntropyGroup      mean_(j,g) -sum_c w log(w + eps) / log(n_j)               (segmentation/model/loss.py:398-426)
+ *   term 1 CrossEntropyGroup -mean_(j,i!=l) -sum_c w[i,c] log(max(w[l,c], eps))        (:429-464)
+ *   term 2 ScaleMax          -mean_(j,s: span non-empty) mean_g max_(c in span(j,s)) w  (:351-395; gradient to the first max)
+ *   term 3 L1                sum |head[k][u] (1 - ident[u][k])|                         (module_multiscale.py:260-261,
+ *                                                                                        module_multiscale_group_train.py:283-285)
+ * total = ((weights[3] l1 + weights[1] t1) + weights[2] t2) + weights[0] t0, the reference's order (:288-297).  Bit b of
+ * `terms` enables term b; a disabled term is 0 and gets no gradient.  Group terms need wd and the GroupTables; L1 needs head
+ * and ident.  Limits: nblocks <= 192, 1 <= G <= 16, 1 <= S <= 16, n_j <= 4096, U*P and K*Uh < 2^31.  No float atomics:
+ * fixed-order reductions in float64, run-to-run bit-identical. */
+#define SPX_REG_ENT 1
+#define SPX_REG_CEG 2
+#define SPX_REG_SMAX 4
+#define SPX_REG_L1 8
+typedef struct spx_reg {
+    const float* wd;                 /* [U, P] dense group matrix (spx_group_dense) */
+    int32_t U, P;
+    const int32_t *row_block, *row_local, *col_block, *col_local;   /* the GroupTables of spx_group_dense */
+    const int32_t* flat_col;         /* prototype column of every weight element in block order (spx_group_dense_bwd) */
+    const int32_t* block_info;       /* [nblocks][4]: off_j (first flat element), n_j, u0_j (first unit row), 0 */
+    const int32_t* spans;            /* [nblocks][S][2]: local columns [c0, c1) of scale s; c0 == c1: no prototype there */
+    int32_t nblocks, G, S, nspans;   /* nspans: non-empty spans (ScaleMax's mean count) */
+    const float* head;               /* [K, Uh] last_layer(_group).weight */
+    const float* ident;              /* [Uh, K] prototype / group class identity, fp32 */
+    int32_t K, Uh;
+    float epsilon;
+    float weights[4];
+    int32_t terms;
+} spx_reg;
+/* Forward, one launch: terms fp32 [4] and total fp32 [1].  workspace: spx_reg_workspace_bytes, ZERO-FILLED before its first
+ * use; every call leaves it zeroed again (its first word is the last-workgroup ticket).  One call at a time per workspace. */
+size_t spx_reg_workspace_bytes(const spx_reg* r);
+int spx_reg_fwd(const spx_reg* r, float* total, float* terms, void* workspace, void* stream);
+/* Backward, one launch: upstream of term b = g_total[0] * weights[b] + g_terms[b] (either pointer may be NULL = 0), read
+ * on the device.  d_wd [U, P] (every element written; 0 outside the blocks) when group terms are on, d_head [K, Uh] when
+ * L1 is on.  Gradients as torch's autograd of the reference forms (clamp passes where w >= eps, sgn(0) = 0). */
+int spx_reg_bwd(const spx_reg* r, const float* g_total, const float* g_terms, float* d_wd, float* d_head, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,9 @@ Public surface mirrors the reference's module/function names for this path:
     find_k_nearest_patches_to_prototypes, prune_prototypes
                                                     (find_nearest.py, prune.py: k nearest training patches per prototype
                                                      and class-purity pruning, searched and merged on the GPU)
+    EntropyGroup, CrossEntropyGroup, ScaleMax, GroupRegularizers, head_l1
+                                                    (segmentation/model/loss.py:351-464 and the masked last-layer L1 of the
+                                                     training modules: one forward and one backward launch, no host sync)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -35,7 +38,17 @@ from .functional import (  # noqa: F401
     upsample_argext,
 )
 from .checkpoint import export_state, import_state, load_reference_state_dict  # noqa: F401
-from .loss import ClassDistances, KLDLoss, KLDLossGroup, PixelWiseCrossEntropyLoss  # noqa: F401
+from .loss import (  # noqa: F401
+    ClassDistances,
+    CrossEntropyGroup,
+    EntropyGroup,
+    GroupRegularizers,
+    KLDLoss,
+    KLDLossGroup,
+    PixelWiseCrossEntropyLoss,
+    ScaleMax,
+    head_l1,
+)
 from .metrics import SegmentationMetrics, SegmentationResult  # noqa: F401
 from .model import PPNet  # noqa: F401
 from .model_multiscale import PPNetMultiScale, construct_PPNet  # noqa: F401

@@ -52,8 +52,37 @@ class SpxCe(C.Structure):
     ]
 
 
+class SpxReg(C.Structure):
+    """spx_reg of include/spx_hip.h: the weight-side regularisers' inputs (spx_reg_fwd / spx_reg_bwd)."""
+
+    _fields_ = [
+        ("wd", C.c_void_p),
+        ("U", C.c_int32),
+        ("P", C.c_int32),
+        ("row_block", C.c_void_p),
+        ("row_local", C.c_void_p),
+        ("col_block", C.c_void_p),
+        ("col_local", C.c_void_p),
+        ("flat_col", C.c_void_p),
+        ("block_info", C.c_void_p),
+        ("spans", C.c_void_p),
+        ("nblocks", C.c_int32),
+        ("G", C.c_int32),
+        ("S", C.c_int32),
+        ("nspans", C.c_int32),
+        ("head", C.c_void_p),
+        ("ident", C.c_void_p),
+        ("K", C.c_int32),
+        ("Uh", C.c_int32),
+        ("epsilon", C.c_float),
+        ("weights", C.c_float * 4),
+        ("terms", C.c_int32),
+    ]
+
+
 _PP = C.POINTER(SpxPlan)
 _PCE = C.POINTER(SpxCe)
+_PR = C.POINTER(SpxReg)
 _V = C.c_void_p
 _I = C.c_int32
 _F = C.c_float
@@ -125,6 +154,9 @@ SIGNATURES = {
     "spx_dist_prune_min": (C.c_int, [_PP, _V, _I, _I, _I, _V, _V, _V, _I, _V, _V, _V]),
     "spx_prune_footprint": (C.c_int, [_V, _I, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V]),
     "spx_prune_merge": (C.c_int, [_V, _V, _V, _I, _I, _I, C.c_int64, _I, _V, _V, _V, _V, _V, _V]),
+    "spx_reg_workspace_bytes": (C.c_size_t, [_PR]),
+    "spx_reg_fwd": (C.c_int, [_PR, _V, _V, _V, _V]),
+    "spx_reg_bwd": (C.c_int, [_PR, _V, _V, _V, _V, _V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -835,4 +835,40 @@ int spx_kld_backward(const float* vals, const int32_t* labels, int32_t B, int32_
     return hip_status(spx_launch_kld(3, vals, labels, B, J, HW, 0, K, lse, A, Cf, nullptr, grad, (hipStream_t)stream, cf_scale), "spx_kld_backward");
 }
 
+// ptrs = 0: the workspace query, which needs the sizes only
+static int reg_check(const char* who, const spx_reg* r, int ptrs = 1) {
+    if (!r) return fail("%s: NULL descriptor", who);
+    if (r->terms < 1 || r->terms > 15) return fail("%s: term mask %d (1..15)", who, r->terms);
+    if (r->terms & (SPX_REG_ENT | SPX_REG_CEG | SPX_REG_SMAX)) {
+        if (ptrs && (!r->wd || !r->row_block || !r->row_local || !r->col_block || !r->col_local || !r->flat_col || !r->block_info || !r->spans))
+            return fail("%s: group terms need wd and the group tables", who);
+        if (r->U < 1 || r->P < 1 || (long long)r->U * r->P >= (1LL << 31)) return fail("%s: bad group sizes (U=%d P=%d)", who, r->U, r->P);
+        if (r->nblocks < 1 || r->nblocks > SPX_GROUP_BLOCKS_MAX) return fail("%s: %d blocks (1..%d)", who, r->nblocks, SPX_GROUP_BLOCKS_MAX);
+        if (r->G < 1 || r->G > 16 || r->S < 1 || r->S > 16) return fail("%s: G=%d S=%d (1..16 each)", who, r->G, r->S);
+        if ((long long)r->nblocks * r->G > r->U) return fail("%s: %d blocks of %d rows exceed U=%d", who, r->nblocks, r->G, r->U);
+        if ((r->terms & SPX_REG_CEG) && r->G < 2) return fail("%s: the group cross entropy needs G >= 2", who);
+        if ((r->terms & SPX_REG_SMAX) && r->nspans < 1) return fail("%s: ScaleMax without a non-empty span", who);
+    }
+    if (r->terms & SPX_REG_L1) {
+        if (ptrs && (!r->head || !r->ident)) return fail("%s: L1 needs the head and the identity", who);
+        if (r->K < 1 || r->Uh < 1 || (long long)r->K * r->Uh >= (1LL << 31)) return fail("%s: bad head sizes (K=%d Uh=%d)", who, r->K, r->Uh);
+    }
+    return 0;
+}
+size_t spx_reg_workspace_bytes(const spx_reg* r) {
+    if (reg_check("spx_reg_workspace_bytes", r, 0)) return 0;
+    return spx_reg_workspace(*r);
+}
+int spx_reg_fwd(const spx_reg* r, float* total, float* terms, void* workspace, void* stream) {
+    if (reg_check("spx_reg_fwd", r)) return 1;
+    if (!total || !terms || !workspace) return fail("spx_reg_fwd: NULL output / workspace");
+    return hip_status(spx_launch_reg_fwd(*r, total, terms, workspace, (hipStream_t)stream), "spx_reg_fwd");
+}
+int spx_reg_bwd(const spx_reg* r, const float* g_total, const float* g_terms, float* d_wd, float* d_head, void* stream) {
+    if (reg_check("spx_reg_bwd", r)) return 1;
+    if ((r->terms & (SPX_REG_ENT | SPX_REG_CEG | SPX_REG_SMAX)) && !d_wd) return fail("spx_reg_bwd: NULL d_wd");
+    if ((r->terms & SPX_REG_L1) && !d_head) return fail("spx_reg_bwd: NULL d_head");
+    return hip_status(spx_launch_reg_bwd(*r, g_total, g_terms, d_wd, d_head, (hipStream_t)stream), "spx_reg_bwd");
+}
+
 }  // extern "C"

@@ -168,6 +168,11 @@ hipError_t spx_launch_prune_footprint(const int32_t* labels, int B, int Hf, int 
                                       const int32_t* target_class, int32_t* label, int32_t* box, hipStream_t s);
 hipError_t spx_launch_prune_merge(const uint64_t* keys, const int32_t* label, const int32_t* box, int B, int P, int W, long long image0,
                                   int k, uint64_t* tkey, int64_t* timg, int32_t* tlabel, int32_t* tbox, int32_t* tcell, hipStream_t s);
+// weight-side regularisers (spx_reg.hip)
+size_t spx_reg_workspace(const spx_reg& r);
+hipError_t spx_launch_reg_fwd(const spx_reg& r, float* total, float* terms, void* workspace, hipStream_t s);
+hipError_t spx_launch_reg_bwd(const spx_reg& r, const float* g_total, const float* g_terms, float* d_wd, float* d_head,
+                              hipStream_t s);
 #ifdef SPX_DIAG
 void spx_gemm_force(int wm, int splits);
 #endif

@@ -11,6 +11,7 @@ algebra that the tests hold the kernels against is test infrastructure and lives
 """
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple, Union
 
@@ -342,3 +343,223 @@ class KLDLossGroup(KLDLoss):
     def forward(self, list_group_activation, target_labels: torch.Tensor) -> torch.Tensor:
         vals, labels0, table = self._gather_groups(list_group_activation, target_labels)
         return self._forward_gathered(vals, None, labels0, table, target_labels.shape[-1] if target_labels.dim() >= 3 else 0)
+
+
+# ---- weight-side regularisers (segmentation/model/loss.py:351-464, module_multiscale*.py L1) ----------------------------
+REG_ENT, REG_CEG, REG_SMAX, REG_L1 = 1, 2, 4, 8        # SPX_REG_* of include/spx_hip.h: term b <-> bit b
+_GROUP_TERMS = REG_ENT | REG_CEG | REG_SMAX
+
+
+class _RegSpec:
+    """Everything the regulariser kernels read besides the two weight tensors: the module's GroupTables with their block /
+    span tables, the fp32 device copy of the L1 head's class identity, the zero-filled workspace (whose ticket word the
+    forward leaves zeroed) and the constant part of the spx_reg descriptor."""
+
+    def __init__(self, tables, ident, terms: int, weights, epsilon: float, device):
+        from . import _lib
+
+        self.tables, self.ident, self.terms = tables, ident, int(terms)
+        r = _lib.SpxReg()
+        if terms & _GROUP_TERMS:
+            reg = tables.reg
+            r.U, r.P = tables.U, tables.P
+            r.row_block, r.row_local = _lib.ptr(tables.row_block), _lib.ptr(tables.row_local)
+            r.col_block, r.col_local = _lib.ptr(tables.col_block), _lib.ptr(tables.col_local)
+            r.flat_col, r.block_info, r.spans = _lib.ptr(tables.flat_col), _lib.ptr(reg.block_info), _lib.ptr(reg.spans)
+            r.nblocks, r.G, r.S, r.nspans = len(tables.block_cols), reg.G, reg.S, reg.nspans
+        if terms & REG_L1:
+            r.ident = _lib.ptr(ident)
+            r.Uh, r.K = int(ident.shape[0]), int(ident.shape[1])
+        r.epsilon = float(epsilon)
+        r.weights = (C.c_float * 4)(*[float(w) for w in weights])
+        r.terms = int(terms)
+        self.desc = r
+        nbytes = _lib.load().spx_reg_workspace_bytes(C.byref(r))
+        if nbytes == 0:
+            raise SpxError(_lib.load().spx_last_error().decode("utf-8", "replace"))
+        self.workspace = torch.zeros(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+
+    def bind(self, wd: Optional[torch.Tensor], head: Optional[torch.Tensor]):
+        from . import _lib
+
+        r = self.desc
+        if self.terms & _GROUP_TERMS:
+            if tuple(wd.shape) != (r.U, r.P):
+                raise SpxError(f"regularisers: Wd {tuple(wd.shape)} does not match the group tables [{r.U}, {r.P}]")
+            r.wd = _lib.ptr(wd)
+        if self.terms & REG_L1:
+            if tuple(head.shape) != (r.K, r.Uh):
+                raise SpxError(f"regularisers: head {tuple(head.shape)} does not match the identity's [{r.K}, {r.Uh}]")
+            r.head = _lib.ptr(head)
+        return C.byref(r)
+
+
+class _RegFn(torch.autograd.Function):
+    """(total, terms[4]) of the enabled terms in ONE launch (spx_reg_fwd); backward ONE launch (spx_reg_bwd) writing d Wd
+    (dense [U, P]) and d head, scaled by the upstream gradients read on the device - no host synchronisation either way."""
+
+    @staticmethod
+    def forward(ctx, wd, head, spec):
+        from . import _lib
+
+        lib = _lib.load()
+        wd_c = wd.detach().contiguous() if wd is not None else None
+        head_c = head.detach().contiguous() if head is not None else None
+        dev = (wd_c if wd_c is not None else head_c).device
+        total = torch.empty((), dtype=torch.float32, device=dev)
+        terms = torch.empty((4,), dtype=torch.float32, device=dev)
+        _lib.check(lib.spx_reg_fwd(spec.bind(wd_c, head_c), _lib.ptr(total), _lib.ptr(terms), _lib.ptr(spec.workspace),
+                                   _lib.stream_ptr()))
+        ctx.save_for_backward(wd_c, head_c)
+        ctx.spec = spec
+        ctx.set_materialize_grads(False)
+        return total, terms
+
+    @staticmethod
+    def backward(ctx, g_total, g_terms):
+        from . import _lib
+
+        if g_total is None and g_terms is None:
+            return None, None, None
+        wd, head = ctx.saved_tensors
+        gt = g_total.float().contiguous() if g_total is not None else None
+        gs = g_terms.float().contiguous() if g_terms is not None else None
+        d_wd = torch.empty_like(wd) if wd is not None else None
+        d_head = torch.empty_like(head) if head is not None else None
+        _lib.check(_lib.load().spx_reg_bwd(ctx.spec.bind(wd, head), _lib.ptr(gt), _lib.ptr(gs), _lib.ptr(d_wd), _lib.ptr(d_head),
+                                           _lib.stream_ptr()))
+        return d_wd, d_head, None
+
+
+def _is_group_model(ppnet) -> bool:
+    return hasattr(ppnet, "group_projection") and hasattr(ppnet, "last_layer_group")
+
+
+def _check_weights(ws, what: str) -> None:
+    for w in ws:
+        if not w.is_cuda:
+            raise SpxError(f"{what}: weights on {w.device}; the regularisers run on the GPU only (no CPU fallback)")
+        if w.dtype != torch.float32:
+            raise SpxError(f"{what}: weights are {w.dtype}; the kernels take fp32")
+
+
+def _same_key(a, b) -> bool:
+    # objects (tables, identity tensors) by identity - the cache holds them, so an id cannot be recycled - numbers by value
+    return a is not None and len(a) == len(b) and all(x is y or (isinstance(x, (int, str)) and x == y) for x, y in zip(a, b))
+
+
+def _reg_spec(net, terms: int, weights, epsilon: float, device, holder) -> _RegSpec:
+    """The kernel-side spec of ``net``, cached in ``holder._spx_reg_spec`` on the group tables' identity (rebuilt with every
+    table version: a pruned bank or re-assigned identity gives new tables), the L1 identity tensor and its version."""
+    tables = None
+    if terms & _GROUP_TERMS:
+        _, _, _, tables = net._group_index(device)
+        if tables is None or getattr(tables, "reg", None) is None:
+            raise SpxError("regularisers: the group tables are outside the kernels' domain (GPU, <= 192 classes with "
+                           "prototypes, the same number of groups <= 16 for every class, <= 16 scales)")
+    key = (tables, str(device))
+    if terms & REG_L1:
+        src = net.group_class_identity if _is_group_model(net) else net.prototype_class_identity
+        key = key + (src, src._version, getattr(net, "_tables_version", 0))
+    c = getattr(holder, "_spx_reg_spec", None)
+    if c is not None and _same_key(c[0], key):
+        return c[1]
+    ident = src.detach().to(device=device, dtype=torch.float32).contiguous() if terms & REG_L1 else None
+    spec = _RegSpec(tables, ident, terms, weights, epsilon, device)
+    object.__setattr__(holder, "_spx_reg_spec", (key, spec))
+    return spec
+
+
+def _reg_apply(net, terms: int, weights, epsilon: float, holder, logits: Optional[torch.Tensor] = None):
+    head = None
+    if terms & REG_L1:
+        head = net.last_layer_group.weight if _is_group_model(net) else net.last_layer.weight
+        _check_weights([head], "regularisers")
+        dev = head.device
+    wd = None
+    if terms & _GROUP_TERMS:
+        ws = [gp.weight for gp in net.group_projection]
+        _check_weights(ws, "regularisers")
+        dev = ws[0].device
+        tag = getattr(logits, "spx_group_wd", None) if logits is not None else None
+        if tag is not None and tag[1] is net and tag[2] == tuple(w._version for w in ws):
+            wd = tag[0]                              # the Wd this very forward multiplied with: one scatter for both gradients
+        else:
+            wd = net._dense_group_matrix()
+    return _RegFn.apply(wd, head, _reg_spec(net, terms, weights, epsilon, dev, holder))
+
+
+class _RegBase(nn.Module):
+    def __init__(self, ppnet, terms: int, weights, epsilon: float) -> None:
+        super().__init__()
+        self.ppnet = ppnet
+        self.epsilon = epsilon
+        self._terms, self._weights = int(terms), tuple(float(w) for w in weights)
+
+    def _run(self, logits: Optional[torch.Tensor] = None):
+        return _reg_apply(self.ppnet, self._terms, self._weights, float(self.epsilon), self, logits)
+
+
+class GroupRegularizers(_RegBase):
+    """The weight-side terms of the group phase's objective in one forward launch and one backward launch
+    (segmentation/model/module_multiscale_group_train.py:274-297): ``forward(logits=None)`` returns ``(total, terms)``
+    with terms = [group entropy, group cross entropy, scale max, L1] (fp32 [4], for logging without a sync) and total =
+    the weighted sum in the reference's order.  Every term is computed and differentiated whatever its weight, as in the
+    reference (a weight of 0 times a non-finite term is NaN there too).  ``logits``: the output of this model's forward
+    of the same step; the terms then differentiate through the dense group matrix that forward used, so the group
+    weights still receive their gradient from one scatter.  On a prototype-phase model only the L1 of ``last_layer``
+    exists (the group weights must be 0)."""
+
+    def __init__(self, ppnet, group_ent: float = 0.0, crs_ent_group: float = 0.0, scale_max: float = 0.0, l1: float = 0.0,
+                 epsilon: float = 1e-5) -> None:
+        if _is_group_model(ppnet):
+            terms = _GROUP_TERMS | REG_L1
+        else:
+            if group_ent or crs_ent_group or scale_max:
+                raise SpxError("GroupRegularizers: a prototype-phase model has no group projections (group weights must be 0)")
+            terms = REG_L1
+        super().__init__(ppnet, terms, (group_ent, crs_ent_group, scale_max, l1), epsilon)
+
+    def forward(self, logits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        return self._run(logits)
+
+
+class _OneTerm(_RegBase):
+    BIT = 0
+
+    def __init__(self, ppnet, epsilon: float = 1e-5) -> None:
+        if not _is_group_model(ppnet):
+            raise SpxError(f"{type(self).__name__} needs a group-phase model (group_projection, last_layer_group)")
+        weights = [1.0 if (1 << b) == self.BIT else 0.0 for b in range(4)]
+        super().__init__(ppnet, self.BIT, weights, epsilon)
+
+    def forward(self) -> torch.Tensor:
+        return self._run()[0]          # total = 1 * term: a 0-d output of the kernel itself, no view to differentiate
+
+
+class EntropyGroup(_OneTerm):
+    """Drop-in for segmentation/model/loss.py:398-426 (``EntropyGroup(ppnet, epsilon)``, ``forward()``) on the GPU kernels."""
+
+    BIT = REG_ENT
+
+
+class CrossEntropyGroup(_OneTerm):
+    """Drop-in for segmentation/model/loss.py:429-464 on the GPU kernels."""
+
+    BIT = REG_CEG
+
+
+class ScaleMax(_OneTerm):
+    """Drop-in for segmentation/model/loss.py:351-395 (``ScaleMax(ppnet)``) on the GPU kernels; the gradient goes to the first
+    maximal column of every span, as torch's ``max(dim)``."""
+
+    BIT = REG_SMAX
+
+    def __init__(self, ppnet) -> None:
+        super().__init__(ppnet, 1e-5)
+
+
+def head_l1(ppnet) -> torch.Tensor:
+    """``(W * (1 - identity^T)).norm(p=1)`` of ``last_layer`` (prototype phase, module_multiscale.py:260-261, module.py:218-220)
+    or ``last_layer_group`` (group phase, module_multiscale_group_train.py:283-285) in one launch; differentiable to W."""
+    return _reg_apply(ppnet, REG_L1, (0.0, 0.0, 0.0, 1.0), 1e-5, ppnet)[0]

@@ -24,6 +24,43 @@ from .model_multiscale import _PrototypeBankMixin, _build_add_on, _first_add_on_
 from .utils import projection_simplex_sort
 
 
+class GroupRegTables:
+    """Device tables of the weight-side regularisers (csrc/spx_reg.hip), cached with the GroupTables they extend:
+    block_info int32 [J, 4] = (first flat weight element, n_j, first unit row, 0) and spans int32 [J, S, 2]."""
+
+    def __init__(self, block_info, spans, nspans: int, G: int, S: int):
+        self.block_info, self.spans, self.nspans, self.G, self.S = block_info, spans, int(nspans), int(G), int(S)
+
+
+def group_scale_spans(prototype_class_identity: torch.Tensor, scale_num_prototypes, num_scales: int, num_groups: int):
+    """(block_info [J, 4], spans [J, S, 2], number of non-empty spans) for the classes that own prototypes, in block order.
+    The span of (class block j, scale s) is the range of j's local weight columns that ScaleMax takes its maximum over
+    (segmentation/model/loss.py:366-390): the counts of j's prototypes inside scale_num_prototypes[s], laid end to end in
+    scale order; a scale without any of j's prototypes has the empty span (c, c).  Pure host work."""
+    ident = prototype_class_identity.detach().cpu()
+    K = ident.shape[1]
+    info, spans, nspans, off, u0 = [], [], 0, 0, 0
+    for k in range(K):
+        n = int(torch.count_nonzero(ident[:, k]))
+        if n == 0:
+            continue                                                       # loss.py:362-363
+        prev, row = 0, []
+        for s in range(num_scales):
+            lo, hi = (int(v) for v in scale_num_prototypes[s])
+            cnt = int(torch.count_nonzero(ident[lo:hi, k]))
+            if cnt and prev + cnt > n:
+                raise SpxError(f"class {k}: the scale ranges hold more of its prototypes ({prev + cnt}) than it owns ({n})")
+            row.append((prev, prev + cnt))
+            nspans += cnt > 0
+            prev += cnt
+        info.append((off, n, u0, 0))
+        spans.append(row)
+        off += num_groups * n
+        u0 += num_groups
+    return (torch.tensor(info, dtype=torch.int32).reshape(-1, 4), torch.tensor(spans, dtype=torch.int32).reshape(-1, num_scales, 2),
+            nspans)
+
+
 class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
     """Group-phase module; the reference names it ``PPNetMultiScale`` in model_multiscale_group.py (:82), so
     ``from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale`` works as upstream.  The package exports it
@@ -122,6 +159,11 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         if torch.device(device).type == "cuda" and len(block_cols) <= 192:
             tables = GroupTables(i32(row_block), i32(row_local), i32(col_block), i32(col_local), i32(rows_), i32(cols_),
                                  block_cols, r0, P)
+            tables.reg = None
+            gs = [int(gp.weight.shape[0]) for gp in self.group_projection]
+            if gs and all(g == gs[0] for g in gs) and 1 <= gs[0] <= 16 and 1 <= self.num_scales <= 16:
+                info, spans, nspans = group_scale_spans(ident, self.scale_num_prototypes, self.num_scales, gs[0])
+                tables.reg = GroupRegTables(i32(info), i32(spans), nspans, gs[0], self.num_scales)
         out = (rows_.to(device), cols_.to(device), r0, tables)
         self._group_index_cache = (ident, key, out)
         return out
@@ -234,6 +276,9 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         if ce_labels is not None and fused_ce is None:
             fused_ce = cross_entropy_from_logits(logits, ce_labels)       # heads the fused kernels do not carry
         logits = logits.reshape(B, H, W, -1)
+        # the dense group matrix this forward multiplied with (GroupRegularizers(logits=...) differentiates through it, so the
+        # group weights receive one scatter for both gradients); the weights' versions void it after an optimiser step
+        logits.spx_group_wd = (wd, self, tuple(gp.weight._version for gp in self.group_projection))
         if fused_ce is not None:
             fused_ce.target = ce_target
             fused_ce.target_version = ce_target._version      # an in-place edit of the labels afterwards voids the attachment
