@@ -47,16 +47,10 @@ static int hip_status(hipError_t e, const char* what) {
 static int check_plan(const spx_plan* pl) {
     if (!pl) return fail("plan is NULL");
     if (pl->npanels < 1 || pl->npanels > SPX_MAX_PANELS) return fail("plan: npanels %d out of range", pl->npanels);
-    if (pl->npb < 1 || pl->npb > 6) return fail("plan: npb %d out of range", pl->npb);
-    if (pl->ncb < 1 || pl->ncb > 5) return fail("plan: ncb %d out of range", pl->ncb);
     if (pl->kc != 32) return fail("plan: kc %d", pl->kc);
     if (pl->npb != 2 && pl->npb != 4 && pl->npb != 6) return fail("plan: npb %d (must be 2, 4 or 6)", pl->npb);
     if (pl->ncb != 1 && pl->ncb != 2 && pl->ncb != 5) return fail("plan: ncb %d (must be 1, 2 or 5)", pl->ncb);
     return 0;
-}
-static int x_vec_ok(const void* x, int x_dtype, int HW) {
-    (void)x; (void)x_dtype; (void)HW;
-    return 0;   /* decided per launch by the launchers (full tiles: vector staging at any alignment; ragged tail: element-wise) */
 }
 
 // Scale-parallel launch (grid.y = scale): for pixel grids that do not fill the chip (the reference's training crops:
@@ -64,9 +58,7 @@ static int x_vec_ok(const void* x, int x_dtype, int HW) {
 // panels of different scales are independent work - different channels of X and dX, different prototype rows - and run
 // as separate workgroups.  Only the logits (a sum over all prototypes) need a second step, a fixed-order sum of the
 // per-scale partials.  Returns the number of groups (1 = keep the single walk) and their first panels.
-#ifndef SPX_SPLIT_MAX_TILES
 #define SPX_SPLIT_MAX_TILES 1024
-#endif
 int spx_split_groups(const spx_plan& pl, int B, int HW, int32_t* group_first) {
     const long long tiles = (long long)B * ((HW + SPX_TILE_PX - 1) / SPX_TILE_PX);
     int g = 0;
@@ -246,7 +238,6 @@ static int dist_fwd_impl(const spx_plan* pl, const void* x, int32_t x_dtype, int
     a.logits = logits;
     a.B = B;
     a.HW = HW;
-    a.vec_ok = x_vec_ok(x, x_dtype, HW);
     a.labels = labels;
     a.proto_key = proto_key;
     a.cls_dist = cls_dist;
@@ -433,7 +424,6 @@ static int dist_bwd_impl(const spx_plan* pl, const void* x, int32_t x_dtype, int
     a.a_out = (uint16_t*)a_out;
     a.B = B;
     a.HW = HW;
-    a.vec_ok = x_vec_ok(x, x_dtype, HW);
     a.eps = epsilon;
     a.act_fn = act_fn;
     a.dbg = g_dbg;
@@ -652,7 +642,6 @@ int spx_bank_bwd(const spx_plan* pl, const void* x, int32_t x_dtype, int32_t B, 
     a.workspace = (float*)workspace;
     a.B = B;
     a.HW = HW;
-    a.vec_ok = x_vec_ok(x, x_dtype, HW);
     a.nsplit = spx_bank_bwd_nsplit(*pl, B, HW);
     return hip_status(spx_launch_bank_bwd(a, x_dtype, (hipStream_t)stream), "spx_bank_bwd");
 }

@@ -1,6 +1,7 @@
 // Kernel argument blocks + launcher prototypes shared by the kernel translation units and the C ABI.
 #pragma once
 #include "spx_common.h"
+#include <type_traits>
 
 struct SpxFwdArgs {
     spx_plan plan;
@@ -11,8 +12,8 @@ struct SpxFwdArgs {
     float* dist;
     float* act;
     float* logits;
-    int B, HW, vec_ok;
-    int tile_first, tiles_launch;   // this launch covers tiles [tile_first, tile_first + tiles_launch) of every image
+    int B, HW, vec_ok;              // vec_ok: the launcher's spx_x_stage_mode(HW); the kernels do not read it
+    int tile_first, tiles_launch;   // this launch covers tiles [tile_first, tile_first + tiles_launch) of every image (always all: tile_first = 0)
     int tile_mul;                   // block -> tile permutation: tile = (block * tile_mul) mod tiles_launch (1 = identity), see spx_tile_mul
     int dist_vec;              // distances 16-B aligned and HW % 4 == 0: 16-B stores of 4 pixels of a row
     // class-gathered distances (spx_dist_fwd_cls): every pixel keeps only the distances to its own class's prototypes
@@ -78,8 +79,8 @@ struct SpxBwdArgs {
     float* dx_acc;              // fp32 [B][C][HW rounded up to 4]: partial dX of scales that span several panels (bf16 features); may be NULL
     uint16_t* g_out;
     uint16_t* a_out;            // head-gradient scratch (spx_common.h): fp32 d_W tile partials (one class block) or the activation blob
-    int B, HW, vec_ok;
-    int tile_first, tiles_launch;   // this launch covers tiles [tile_first, tile_first + tiles_launch) of every image
+    int B, HW, vec_ok;              // vec_ok: the launcher's spx_x_stage_mode(HW); the kernels do not read it
+    int tile_first, tiles_launch;   // this launch covers tiles [tile_first, tile_first + tiles_launch) of every image (always all: tile_first = 0)
     int tile_mul;                   // see SpxFwdArgs
     float eps;
     int act_fn;
@@ -105,6 +106,21 @@ struct SpxBankBwdArgs {
 // 16-B bank groups (the plain slot r + 32 h would put them 4-way on the same banks).
 __host__ __device__ inline uint32_t spx_blob_slot(int r, int h, int s2) {
     return (uint32_t)(((r >> 2) * 8 + (r & 3) + 4 * h + 8 * s2) & 63);
+}
+
+// Staging mode of the X tiles (template parameter VM of the kernels): 0 = element-wise loads (images of fewer than 8 pixels),
+// 1 = 16-B vector loads, 2 = vector loads with a ragged image end (H*W % 8 != 0), see SpxXStager
+inline int spx_x_stage_mode(int HW) { return HW < 8 ? 0 : (HW % 8 == 0 ? 1 : 2); }
+// The run-time pair (x_dtype, staging mode) as compile-time constants: f(std::bool_constant<XF32>, std::integral_constant<int, VM>)
+template <typename F>
+static inline void spx_dispatch_x(int x_dtype, int vm, F f) {
+    auto with_vm = [&](auto xf32) {
+        if (vm == 2) f(xf32, std::integral_constant<int, 2>{});
+        else if (vm) f(xf32, std::integral_constant<int, 1>{});
+        else f(xf32, std::integral_constant<int, 0>{});
+    };
+    if (x_dtype == 1) with_vm(std::true_type{});
+    else with_vm(std::false_type{});
 }
 
 int spx_tile_mul(int tiles_launch, long long plane_bytes);

@@ -962,15 +962,9 @@ static hipError_t launch_bank_k(const SpxBankBwdArgs& a, int x_dtype, dim3 grid,
     constexpr int CPX = (SPX_BANK_PIPE && !KSPLIT && NPB == 6 && NCB == 1 && 2 * spx_bk_buf_bytes<NPB, NCB, DO_P, DO_W, 32>() <= SPX_LDS_LIMIT) ? 32 : 64;
     constexpr size_t lds = (size_t)spx_bk_lds_bytes<NPB, NCB, DO_P, DO_W, CPX>();
     static_assert(lds <= SPX_LDS_LIMIT, "bank kernel LDS");
-    if (x_dtype == 1) {
-        if (a.vec_ok == 2) hipLaunchKernelGGL((spx_bank_bwd_kernel<NPB, NCB, true, 2, DO_P, DO_W, KSPLIT, CPX>), grid, dim3(SPX_BK_THREADS), lds, s, a);
-        else if (a.vec_ok) hipLaunchKernelGGL((spx_bank_bwd_kernel<NPB, NCB, true, 1, DO_P, DO_W, KSPLIT, CPX>), grid, dim3(SPX_BK_THREADS), lds, s, a);
-        else hipLaunchKernelGGL((spx_bank_bwd_kernel<NPB, NCB, true, 0, DO_P, DO_W, KSPLIT, CPX>), grid, dim3(SPX_BK_THREADS), lds, s, a);
-    } else {
-        if (a.vec_ok == 2) hipLaunchKernelGGL((spx_bank_bwd_kernel<NPB, NCB, false, 2, DO_P, DO_W, KSPLIT, CPX>), grid, dim3(SPX_BK_THREADS), lds, s, a);
-        else if (a.vec_ok) hipLaunchKernelGGL((spx_bank_bwd_kernel<NPB, NCB, false, 1, DO_P, DO_W, KSPLIT, CPX>), grid, dim3(SPX_BK_THREADS), lds, s, a);
-        else hipLaunchKernelGGL((spx_bank_bwd_kernel<NPB, NCB, false, 0, DO_P, DO_W, KSPLIT, CPX>), grid, dim3(SPX_BK_THREADS), lds, s, a);
-    }
+    spx_dispatch_x(x_dtype, a.vec_ok, [&](auto xf32, auto vm) {
+        hipLaunchKernelGGL((spx_bank_bwd_kernel<NPB, NCB, decltype(xf32)::value, decltype(vm)::value, DO_P, DO_W, KSPLIT, CPX>), grid, dim3(SPX_BK_THREADS), lds, s, a);
+    });
     return hipGetLastError();
 }
 template <int NPB, int NCB, bool DO_P, bool DO_W>

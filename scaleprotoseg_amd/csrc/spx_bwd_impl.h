@@ -29,7 +29,6 @@
 #include <type_traits>
 
 #define SPX_BWD_WAVES 2                   // two workgroups per CU (256 registers per wave)
-#define SPX_BWD_XRING(xf32) 2             // X chunks in flight ahead of the MFMAs
 
 #define SPX_T_ROW 528                     // fp32 transpose tile row: 128 px * 4 B + 16 B pad
 #define SPX_T_BYTES (32 * SPX_T_ROW)
@@ -99,8 +98,7 @@ __global__ __launch_bounds__(256, SPX_BWD_WAVES) void spx_bwd_kernel(const SpxBw
     constexpr int ncstep = NCB * 2;
     const uint32_t HW = (uint32_t)a.HW;
     constexpr int ESZ = XF32 ? 4 : 2;
-    constexpr int XR = SPX_BWD_XRING(XF32);
-    using Pipe = SpxPipeline<NPB, XF32, VM, XR>;
+    using Pipe = SpxPipeline<NPB, XF32, VM>;
 
     const char* x_img = (const char*)a.x + (size_t)b * C * a.HW * ESZ;
     const SpxTileCtx tc = SpxXStager<XF32, VM>::make_ctx(x_img, a.HW, px0, tid);
@@ -980,25 +978,22 @@ __global__ __launch_bounds__(256, SPX_BWD_WAVES) void spx_bwd_kernel(const SpxBw
 template <int NPB, int NCB, bool GATHER, bool DACT>
 static hipError_t launch_bwd_gd(const SpxBwdArgs& a, int x_dtype, dim3 grid, hipStream_t s) {
     constexpr size_t lds = (size_t)spx_bwd_lds_bytes<NPB, NCB, DACT>();
-    if (x_dtype == 1) {
-        if (a.vec_ok == 2) hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, true, 2, GATHER, DACT>), grid, dim3(256), lds, s, a);
-        else if (a.vec_ok) hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, true, 1, GATHER, DACT>), grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, true, 0, GATHER, DACT>), grid, dim3(256), lds, s, a);
-    } else {
-        bool acc = false;
-        if (a.dx_acc && a.dx) {
-            for (int q = 1; q < a.plan.npanels; ++q) acc |= a.plan.panel_ch0[q] == a.plan.panel_ch0[q - 1];
-        }
-        if (acc) {
-            if (a.vec_ok == 2) hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, false, 2, GATHER, DACT, true>), grid, dim3(256), lds, s, a);
-            else if (a.vec_ok) hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, false, 1, GATHER, DACT, true>), grid, dim3(256), lds, s, a);
-            else hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, false, 0, GATHER, DACT, true>), grid, dim3(256), lds, s, a);
-        }
-        if (acc) {
-        } else if (a.vec_ok == 2) hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, false, 2, GATHER, DACT>), grid, dim3(256), lds, s, a);
-        else if (a.vec_ok) hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, false, 1, GATHER, DACT>), grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, false, 0, GATHER, DACT>), grid, dim3(256), lds, s, a);
+    // ACC instances exist for bf16 features only
+    bool acc = false;
+    if (x_dtype != 1 && a.dx_acc && a.dx) {
+        for (int q = 1; q < a.plan.npanels; ++q) acc |= a.plan.panel_ch0[q] == a.plan.panel_ch0[q - 1];
     }
+    spx_dispatch_x(x_dtype, a.vec_ok, [&](auto xf32, auto vm) {
+        constexpr bool XF32 = decltype(xf32)::value;
+        constexpr int VM = decltype(vm)::value;
+        if constexpr (!XF32) {
+            if (acc) {
+                hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, false, VM, GATHER, DACT, true>), grid, dim3(256), lds, s, a);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, XF32, VM, GATHER, DACT>), grid, dim3(256), lds, s, a);
+    });
     return hipGetLastError();
 }
 template <int NPB, int NCB>
@@ -1021,7 +1016,7 @@ static hipError_t spx_launch_bwd_tiles(const SpxBwdArgs& a, int x_dtype, hipStre
 template <int NPB>
 static hipError_t spx_launch_bwd_npb(const SpxBwdArgs& a0, int x_dtype, hipStream_t s) {
     SpxBwdArgs a = a0;
-    a.vec_ok = a.HW < 8 ? 0 : (a.HW % 8 == 0 ? 1 : 2);      // the element-wise path only for images of fewer than 8 pixels
+    a.vec_ok = spx_x_stage_mode(a.HW);
     a.tile_first = 0;
     a.tiles_launch = (a.HW + SPX_TILE_PX - 1) / SPX_TILE_PX;
     a.tile_mul = spx_tile_mul(a.tiles_launch, (long long)a.HW * (x_dtype == 1 ? 4 : 2));

@@ -294,7 +294,6 @@ __global__ __launch_bounds__(SPX_CE_THREADS) void spx_group_tail_kernel(const fl
             for (unsigned e = gridDim.x; e < ((gridDim.x + 3u) & ~3u); ++e) partials[(size_t)e * 2] = partials[(size_t)e * 2 + 1] = 0.0f;
     }
 }
-size_t spx_group_tail_partials(long long M) { return (size_t)((M + SPX_TAIL_PX - 1) / SPX_TAIL_PX); }
 hipError_t spx_launch_group_tail(const float* parts, int groups, long long M, int U, const float* Wg, int K2, float* gact,
                                  float* logits, const int32_t* labels, float* lse, int32_t* pred, float* partials, hipStream_t s) {
     const unsigned grid = (unsigned)((M + SPX_TAIL_PX - 1) / SPX_TAIL_PX);

@@ -61,12 +61,6 @@ __device__ __forceinline__ u32x4 buf_load_b128(spx_rsrc r, uint32_t voff, uint32
 __device__ __forceinline__ void buf_store_b128(u32x4 v, spx_rsrc r, uint32_t voff, uint32_t soff) {
     __builtin_amdgcn_raw_buffer_store_b128(v, r, voff + soff, 0, 0);
 }
-__device__ __forceinline__ u32x2 buf_load_b64(spx_rsrc r, uint32_t voff, uint32_t soff) {
-    return __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-}
-__device__ __forceinline__ void buf_store_b64(u32x2 v, spx_rsrc r, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, 0);
-}
 
 // Logical right shift of a 128-bit value (4 dwords, little endian) by `bits` in [0, 128), zeros shifted in.  Used on the
 // ONE 16-byte piece per feature row that straddles the end of an image whose H*W is not a multiple of the piece: the
@@ -140,16 +134,6 @@ __device__ __forceinline__ f32x16 tile_get(const f32x16 (&t)[N], int i) {
     return v;
 }
 #undef SPX_TILE_CASE
-#define SPX_TILE_CASE(K)                         \
-    if (N > K && i == K) {                       \
-        t[N > K ? K : 0] = v;                    \
-        asm volatile("; tile case " #K ::: );   \
-    }
-template <int N>
-__device__ __forceinline__ void tile_set(f32x16 (&t)[N], int i, const f32x16& v) {
-    SPX_TILE_CASE(0) SPX_TILE_CASE(1) SPX_TILE_CASE(2) SPX_TILE_CASE(3) SPX_TILE_CASE(4) SPX_TILE_CASE(5)
-}
-#undef SPX_TILE_CASE
 
 __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -200,14 +184,7 @@ __device__ __forceinline__ void split_bf16x2(f32x2 v, uint32_t& hi, uint32_t& lo
     asm("" : "+v"(hi));      // keeps the unpack below on the packed word (otherwise element 0 is converted a second time on its own)
     lo = pack_bf16x2(v - unpack_bf16x2(hi));
 }
-// sum of the two bf16 halves of a packed word, added to acc (v_dot2_f32_bf16 against ones)
-__device__ __forceinline__ float add_bf16x2(uint32_t w, float acc) {
-    bf16x2 one2;
-    one2[0] = (__bf16)1.0f;
-    one2[1] = (__bf16)1.0f;
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, w), one2, acc, false);
-}
-// the same with round-toward-zero: ONE instruction (v_cvt_pkrtz_f16_f32), exact for values with <= 11 significant bits (every
+// two values as a packed fp16 word, round-toward-zero: ONE instruction (v_cvt_pkrtz_f16_f32), exact for values with <= 11 significant bits (every
 // bf16 value in fp16's normal range), and a value beyond fp16's range saturates at 65504 instead of becoming inf
 __device__ __forceinline__ uint32_t pack_f16x2_rtz(f32x2 v) {
     return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(v[0], v[1]));
@@ -236,10 +213,6 @@ __device__ __forceinline__ float act_log(float d, float eps) {
     // log((d+1)/(d+eps)), segmentation/model/model_multiscale.py:326.  The ratio lies in [1, 1/eps], so the raw
     // v_rcp_f32 / v_log_f32 (1 ulp each, no denormal fix-up code) are exact enough: 6 VALU per element.
     return __builtin_amdgcn_logf((d + 1.0f) * __builtin_amdgcn_rcpf(d + eps)) * 0.69314718056f;
-}
-__device__ __forceinline__ float act_log_grad(float d, float eps) {
-    // d/dd log((d+1)/(d+eps)) = 1/(d+1) - 1/(d+eps) = -(1-eps) / ((d+1)(d+eps))
-    return -(1.0f - eps) * __builtin_amdgcn_rcpf((d + 1.0f) * (d + eps));
 }
 
 // cross entropy helpers (segmentation/model/loss.py:9-48): running maximum with the LOWEST class index on ties

@@ -144,9 +144,8 @@ __device__ __forceinline__ long long read_label(const void* labels, int label_by
 // shifts and masks), whenever the tile's footprint fits that block (up-sampling by ~x4.6 or more: all the reference's
 // evaluation shapes); otherwise the distances are read from memory directly.
 #define SPX_EVAL_STAGE 4096
-#ifndef SPX_EVAL_TILE_H
 #define SPX_EVAL_TILE_H 16                                    // output rows per tile: a tile is 64 x SPX_EVAL_TILE_H pixels,
-#endif                                                        // one per thread (4 / 8 / 16 rows: profiles/eval_metrics_summary.md)
+                                                              // one per thread (4 / 8 / 16 rows: profiles/eval_metrics_summary.md)
 #define SPX_EVAL_ACC_THREADS (64 * SPX_EVAL_TILE_H)
 #define SPX_EVAL_DCHUNK (SPX_EVAL_STAGE / 64)
 

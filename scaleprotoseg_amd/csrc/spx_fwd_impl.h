@@ -7,36 +7,16 @@
 #include "spx_args.h"
 #include "spx_mainloop.h"
 
-#ifndef SPX_FWD_WAVES
-#define SPX_FWD_WAVES 2
-#endif
-// X chunks in flight per workgroup (register ring).  A/B on MI355X: 2 beats 4 (0.74 vs 0.78 ms): the loads are not
-// what the loop waits for (in-kernel stamps: < 200 cycles per chunk), the extra registers only cost scheduling freedom
-#ifndef SPX_FWD_SPLIT
-#define SPX_FWD_SPLIT 1
-#endif
-#ifndef SPX_FWD_XPANEL
-#define SPX_FWD_XPANEL 0
-#endif
-#ifndef SPX_FWD_XRING
-#define SPX_FWD_XRING(xf32) 2
-#endif
+#define SPX_FWD_WAVES 2                 // two workgroups per CU (256 registers per wave)
 
 // per-wave LDS scratch of the epilogue's distance-tile turn: 32 prototype rows x 32 pixels fp32, 160-B rows (the
 // two half-waves land 32 banks apart: conflict-free writes); aliases the main-loop stages, free after the loop
-#ifndef SPX_FWD_TROW
 #define SPX_FWD_TROW 40
-#endif
 #define SPX_GATHER_CLASSES 1024         // classes of the in-kernel slot-count table of the gathered mode (4 KiB of idle stage memory)
 #define SPX_FWD_TSCRATCH 8192           // per wave: >= 32 * SPX_FWD_TROW * 4 (distance turn) and 32 px x 64 values (block I/O)
 // LDS carve (bytes): [stage 0][stage 1][head fragments of the current panel (NCB == 1 only)][|p|^2 of the panel]
-#ifdef SPX_FWD_HEAD_L2
-template <int NPB, int NCB>
-__host__ __device__ constexpr int spx_fwd_head_lds_bytes() { return 0; }   // experiment: head fragments straight from L2
-#else
 template <int NPB, int NCB>
 __host__ __device__ constexpr int spx_fwd_head_lds_bytes() { return NCB * NPB <= 6 ? NCB * NPB * 4096 : 0; }   // <= 24 KiB: resident in LDS
-#endif
 // Heads whose panel image does not fit (more than 6 class-block x prototype-block cells: 150 classes, or two class blocks over
 // 192-prototype panels) pass ONE prototype block's fragments at a time (NCB x 4 KiB) through LDS, fetched once per workgroup a
 // block ahead: as per-wave loads from L2 the same fragments were read four times per tile - 120 KiB per panel and wave for
@@ -45,33 +25,31 @@ __host__ __device__ constexpr int spx_fwd_head_lds_bytes() { return NCB * NPB <=
 template <int NPB, int NCB>
 __host__ __device__ constexpr int spx_fwd_head_blk_bytes() { return spx_fwd_head_lds_bytes<NPB, NCB>() == 0 ? NCB * 4096 : 0; }
 // region 0 = the two main-loop stages, re-used after the loop as the waves' epilogue scratch
-template <int NPB, int SPLIT>
+template <int NPB>
 __host__ __device__ constexpr int spx_fwd_region0_bytes() {
-    return 2 * spx_stage_bytes(NPB) > 4 * SPLIT * SPX_FWD_TSCRATCH ? 2 * spx_stage_bytes(NPB) : 4 * SPLIT * SPX_FWD_TSCRATCH;
+    return 2 * spx_stage_bytes(NPB) > 4 * SPX_FWD_TSCRATCH ? 2 * spx_stage_bytes(NPB) : 4 * SPX_FWD_TSCRATCH;
 }
-template <int NPB, int NCB, int SPLIT>
+template <int NPB, int NCB>
 __host__ __device__ constexpr int spx_fwd_lds_bytes() {
-    return spx_fwd_region0_bytes<NPB, SPLIT>() + spx_fwd_head_lds_bytes<NPB, NCB>() + spx_fwd_head_blk_bytes<NPB, NCB>() + 3 * NPB * 32 * 4 + NPB * 32 * 8;   // + |p|^2, class keys, slot plane offsets, push minima
+    return spx_fwd_region0_bytes<NPB>() + spx_fwd_head_lds_bytes<NPB, NCB>() + spx_fwd_head_blk_bytes<NPB, NCB>() + 3 * NPB * 32 * 4 + NPB * 32 * 8;   // + |p|^2, class keys, slot plane offsets, push minima
 }
 
-// SPLIT = waves per 32-pixel group.  SPLIT 1: 4 waves, each with all NPB blocks of its pixels (<= 256 VGPRs, two
-// waves per SIMD).  SPLIT 2: 8 waves, wave (pg = w & 3, ph = w >> 2) accumulates blocks [ph*NPB/2, (ph+1)*NPB/2) of
-// pixel group pg in <= 128 VGPRs: four waves per SIMD instead of two hide the LDS / HBM / transcendental latencies
-// that a two-wave SIMD leaves exposed (the kernel was issue-stalled, not bandwidth-bound: MFMA 17 % + VALU ~42 %
-// busy); the two halves' logits partials meet in LDS at the end.
+// 4 waves, each with all NPB blocks of its 32 pixels (<= 256 VGPRs, two waves per SIMD).
 // GATHER: class-gathered distances (spx_dist_fwd_cls) instead of the P-wide map.
 // (2-block panels with a one-block head fit 168 VGPRs: three waves per SIMD.)
 // ACT: the [pixel][P] activation output is requested (kept out of the default instance: its code costs registers).
 // PRUNE: the prune mode of the fused push (spx_dist_prune_min); its own instances, so the others compile as without it.
-template <int NPB, int NCB, bool XF32, int VM, int SPLIT, bool GATHER, bool ACT, bool PRUNE>
-__global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WAVES) * SPLIT) void spx_fwd_kernel(const SpxFwdArgs a) {
+template <int NPB, int NCB, bool XF32, int VM, bool GATHER, bool ACT, bool PRUNE>
+__global__ __launch_bounds__(256, NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WAVES) void spx_fwd_kernel(const SpxFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NT = 256 * SPLIT, NH = NPB / SPLIT;
-    static_assert(NPB % SPLIT == 0, "blocks must split evenly over the waves of a pixel group");
+    constexpr int NT = 256;                        // threads of the workgroup
     const spx_plan& pl = a.plan;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int pg = wave & 3, ph = wave >> 2;       // pixel group, prototype half
+    // pg = the wave's 32-pixel group.  ph is ALWAYS 0 (4 waves): a leftover of an 8-wave variant, kept as this runtime
+    // expression because hipcc does not know it: with pg = wave, ph = 0 written out register allocation shifts in most
+    // instances (two lose an occupancy step, three gain scratch: profiles/refactor_device_code.md, stage 2)
+    const int pg = wave & 3, ph = wave >> 2;
     const int r = lane & 31, h = lane >> 5;
     const int tiles_per_img = (a.HW + SPX_TILE_PX - 1) / SPX_TILE_PX;
     const int b = blockIdx.x / a.tiles_launch;
@@ -85,46 +63,35 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
     const int q_begin = a.ngroups > 1 ? a.group_first[blockIdx.y] : 0;
     const int q_end = a.ngroups > 1 ? a.group_first[blockIdx.y + 1] : pl.npanels;
     float* const logits_out = a.logits ? a.logits + (size_t)blockIdx.y * a.logits_group_stride : nullptr;
-    constexpr int XR = SPX_FWD_XRING(XF32);
-    using Pipe = SpxPipeline<NPB, XF32, VM, XR, NT, NH>;
+    using Pipe = SpxPipeline<NPB, XF32, VM>;
 
-#ifdef SPX_DIAG_STAGGER
-    // experiment: de-phase the two workgroups that share a CU (blocks i and i+256 of the first dispatch round)
-    if (blockIdx.x >= 256 && blockIdx.x < 512)
-        for (int i = 0; i < SPX_DIAG_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
-    const SpxTileCtx tc = SpxXStager<XF32, VM, NT>::make_ctx((const char*)a.x + (size_t)b * C * a.HW * (XF32 ? 4 : 2), a.HW, px0, tid);
+    const SpxTileCtx tc = SpxXStager<XF32, VM>::make_ctx((const char*)a.x + (size_t)b * C * a.HW * (XF32 ? 4 : 2), a.HW, px0, tid);
 
     constexpr int chunk_bytes = NPB * 2 * 1024;
     constexpr int head_lds = spx_fwd_head_lds_bytes<NPB, NCB>();
-    constexpr int region0 = spx_fwd_region0_bytes<NPB, SPLIT>();
+    constexpr int region0 = spx_fwd_region0_bytes<NPB>();
     const int nchunks = (Cs + SPX_KC - 1) / SPX_KC;
     char* const wlds = smem + region0;
     constexpr int head_blk = spx_fwd_head_blk_bytes<NPB, NCB>();
-    constexpr bool HSTREAM = head_blk != 0 && NT == 256;     // (the 8-wave experiment keeps the per-wave loads)
+    constexpr bool HSTREAM = head_blk != 0;
     float* const p2s = (float*)(wlds + head_lds + head_blk);
     uint32_t* const keys = (uint32_t*)(p2s + NPB * 32);     // GATHER: (class << 16) | slot per padded prototype row
     uint32_t* const koff = keys + NPB * 32;                 // GATHER: byte offset of the row's slot plane (slot * HW * 4)
     unsigned long long* const pmin = (unsigned long long*)(koff + NPB * 32);   // fused push: the workgroup's (value key, pixel) minimum per row
 
     Pipe pipe;
-    f32x16 acc[NH];
+    f32x16 acc[NPB];
     f32x16 accl[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
         for (int i = 0; i < 16; ++i) accl[cb][i] = 0.0f;
-    // SPX_FWD_DUAL_HEAD: the one-class-block head keeps a second logits accumulator for k-step 1 of every block, so the six
-    // head MFMAs of a block form two dependent chains of three instead of one of six (summed once, after the last panel)
-#ifndef SPX_FWD_DUAL_HEAD
-#define SPX_FWD_DUAL_HEAD 0
-#endif
-    constexpr bool DUAL = SPX_FWD_DUAL_HEAD && NCB == 1 && SPLIT == 1;
-    f32x16 accl2;
+    f32x16 accl2;      // DEAD (a second logits accumulator that did not pay), but not free to delete: without this zero-fill
+                       // hipcc schedules 10 of the 234 instances differently (profiles/refactor_device_code.md, stage 2)
 #pragma unroll
     for (int i = 0; i < 16; ++i) accl2[i] = 0.0f;
 #pragma unroll
-    for (int pb = 0; pb < NH; ++pb)
+    for (int pb = 0; pb < NPB; ++pb)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[pb][i] = 0.0f;
     float x2part = 0.0f;
@@ -226,19 +193,19 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
     auto epilogue = [&](int panel) {
         const float x2 = x2part + __shfl_xor(x2part, 32);
         const int p0 = pl.panel_p0[panel], np = pl.panel_np[panel];
-        if (HSTREAM && panel == q_begin) w_issue(panel, ph * NH);
+        if (HSTREAM && panel == q_begin) w_issue(panel, ph * NPB);
 #pragma unroll 1
-        for (int pbl = 0; pbl < NH; ++pbl) {
-            const int pb = ph * NH + pbl;              // block index inside the panel
+        for (int pbl = 0; pbl < NPB; ++pbl) {
+            const int pb = ph * NPB + pbl;              // block index inside the panel
             if (HSTREAM) {
                 __syncthreads();                       // every wave is done with the previous block's fragments
 #pragma unroll
                 for (int cb = 0; cb < (HSTREAM ? NCB : 0); ++cb) *(u32x4*)(wlds + cb * 4096 + tid * 16) = wreg[cb];
                 __syncthreads();
-                if (pbl + 1 < NH) w_issue(panel, pb + 1);
-                else if (panel + 1 < q_end) w_issue(panel + 1, ph * NH);
+                if (pbl + 1 < NPB) w_issue(panel, pb + 1);
+                else if (panel + 1 < q_end) w_issue(panel + 1, ph * NPB);
             }
-            const f32x16 tile = tile_get<NH>(acc, pbl);
+            const f32x16 tile = tile_get<NPB>(acc, pbl);
             if (pb * 32 < np) {
                 const spx_rsrc dr = make_rsrc_pred(a.dist ? a.dist + ((size_t)b * P + p0 + pb * 32) * a.HW : nullptr);
                 const spx_rsrc ar = make_rsrc_pred(ACT ? a.act + (size_t)b * a.HW * P + p0 + pb * 32 : nullptr);
@@ -401,24 +368,14 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
                                 const char* wf = wlds + ((cb * NPB + pb) * 2 + s2) * 2048 + lane * 16;
                                 whi = *(const bf16x8*)wf;
                                 wlo = *(const bf16x8*)(wf + 1024);
-                            } else if (HSTREAM) {
+                            } else {                     // HSTREAM: the block's fragments of this pass
                                 const char* wf = wlds + (cb * 2 + s2) * 2048 + lane * 16;
                                 whi = *(const bf16x8*)wf;
                                 wlo = *(const bf16x8*)(wf + 1024);
-                            } else {
-                                const uint32_t so = (uint32_t)((((cb * pl.npanels + panel) * NPB + pb) * 2 + s2) * 2048);
-                                whi = __builtin_bit_cast(bf16x8, buf_load_b128(hr, (uint32_t)lane * 16u, so));
-                                wlo = __builtin_bit_cast(bf16x8, buf_load_b128(hr, (uint32_t)lane * 16u, so + 1024u));
                             }
-                            if (DUAL && s2 == 1) {
-                                accl2 = mfma_bf16(whi, ahi, accl2);
-                                accl2 = mfma_bf16(wlo, ahi, accl2);
-                                accl2 = mfma_bf16(whi, alo, accl2);
-                            } else {
-                                accl[cb] = mfma_bf16(whi, ahi, accl[cb]);
-                                accl[cb] = mfma_bf16(wlo, ahi, accl[cb]);
-                                accl[cb] = mfma_bf16(whi, alo, accl[cb]);
-                            }
+                            accl[cb] = mfma_bf16(whi, ahi, accl[cb]);
+                            accl[cb] = mfma_bf16(wlo, ahi, accl[cb]);
+                            accl[cb] = mfma_bf16(whi, alo, accl[cb]);
                         }
                     }
                 }
@@ -437,7 +394,7 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
         // the next panel (if any) accumulates from zero
         if (panel + 1 < q_end) {
 #pragma unroll
-            for (int pb = 0; pb < NH; ++pb)
+            for (int pb = 0; pb < NPB; ++pb)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[pb][i] = 0.0f;
         }
@@ -446,18 +403,12 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
 #ifdef SPX_DIAG_STAMPS
     unsigned long long t0 = __builtin_amdgcn_s_memtime(), t1 = 0, t2 = 0;
 #endif
-    // SPX_FWD_XPANEL: fetch the NEXT panel's first chunks and constants before the current panel's epilogue (2-block
-    // panels have the register room).  Measured on the 4-scale bank at 2 Mpx: 0.705 vs 0.692 ms without - the fill is
-    // not what the multi-panel forward waits for - so it is off.
-    constexpr bool PREFETCH_NEXT = SPX_FWD_XPANEL && NPB == 2 && NCB <= 2;
     auto bank_of = [&](int panel) { return a.packed_bank + (size_t)(panel * nchunks) * chunk_bytes; };
     pipe.issue_prologue(tc, bank_of(q_begin), pl.panel_ch0[q_begin], Cs, tid, [&]() { consts_issue(q_begin); });
     for (int panel = q_begin; panel < q_end; ++panel) {
         x2part = 0.0f;
         pipe.run_body(acc, x2part, tc, smem, bank_of(panel), pl.panel_ch0[panel], Cs, lane, wave, tid, consts_commit);
         const bool more = panel + 1 < q_end;
-        if (PREFETCH_NEXT && more)
-            pipe.issue_prologue(tc, bank_of(panel + 1), pl.panel_ch0[panel + 1], Cs, tid, [&]() { consts_issue(panel + 1); });
 #ifdef SPX_DIAG_STAMPS
         t1 = __builtin_amdgcn_s_memtime();
 #endif
@@ -467,30 +418,10 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
 #endif
         if (more) {
             __syncthreads();   // the next panel's body overwrites the head / |p|^2 / stage LDS
-            if (!PREFETCH_NEXT)
-                pipe.issue_prologue(tc, bank_of(panel + 1), pl.panel_ch0[panel + 1], Cs, tid, [&]() { consts_issue(panel + 1); });
+            pipe.issue_prologue(tc, bank_of(panel + 1), pl.panel_ch0[panel + 1], Cs, tid, [&]() { consts_issue(panel + 1); });
         }
     }
 
-    if (DUAL) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) accl[0][i] += accl2[i];
-    }
-    if (want_head && SPLIT == 2) {
-        // the upper prototype half hands its logits partial to the lower one through its own scratch tile
-        // (wave-private until here: its last transposed reads were issued before, LDS serves a wave in order)
-        float* const sc = (float*)(smem + (4 + pg) * SPX_FWD_TSCRATCH);
-        static_assert(NCB == 1 || SPLIT == 1, "the split kernel carries one class block");
-        if (ph == 1) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) sc[reg * 64 + lane] = accl[0][reg];
-        }
-        __syncthreads();
-        if (ph == 0) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) accl[0][reg] += sc[reg * 64 + lane];
-        }
-    }
     // A wave's 32 pixels x n values of a [pixel][n] fp32 tensor (logits, group activations) are ONE contiguous block of
     // 128 n bytes in memory.  Written value by value from the accumulator layout they are n dword stores per lane with
     // an n*4-byte lane stride (each instruction touches 32+ cache lines: 0.9 ms per 2 Mpx for n = 57, measured); turned
@@ -503,7 +434,6 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
 #pragma unroll 1
         for (int i = lane; i < 32 * n; i += 64) buf_store_f32(bsc[i], rs, i < nvalid ? (uint32_t)i * 4u : SPX_OOB, 0);
     };
-    if (want_head && SPLIT == 2) __syncthreads();     // (split variant: the hand-off scratch above is read before it is reused)
     if (want_head && ph == 0 && a.packed_tail) {
         // grouping-head tail (model_multiscale_group.py:303-308): g = exp(units), logits = W_g . g.  The unit tiles
         // are the B operand of a second split-bf16 product, exactly as the activation tiles were for the head.
@@ -632,33 +562,25 @@ __global__ __launch_bounds__(256 * SPLIT, (NPB == 2 && NCB == 1 ? 3 : SPX_FWD_WA
 #endif
 }
 
-template <int NPB, int NCB, int SPLIT, bool GATHER, bool ACT, bool PRUNE = false>
+template <int NPB, int NCB, bool GATHER, bool ACT, bool PRUNE = false>
 static hipError_t launch_fwd_ga(const SpxFwdArgs& a, int x_dtype, dim3 grid, hipStream_t s) {
-    constexpr size_t lds = (size_t)spx_fwd_lds_bytes<NPB, NCB, SPLIT>();
-    const dim3 blk(256 * SPLIT);
-    // a.vec_ok: 0 = element-wise staging, 1 = vector staging, 2 = vector staging with a ragged image end (H*W % 8 != 0)
-    if (x_dtype == 1) {
-        if (a.vec_ok == 2) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, true, 2, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
-        else if (a.vec_ok) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, true, 1, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
-        else hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, true, 0, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
-    } else {
-        if (a.vec_ok == 2) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, false, 2, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
-        else if (a.vec_ok) hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, false, 1, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
-        else hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, false, 0, SPLIT, GATHER, ACT, PRUNE>), grid, blk, lds, s, a);
-    }
+    constexpr size_t lds = (size_t)spx_fwd_lds_bytes<NPB, NCB>();
+    spx_dispatch_x(x_dtype, a.vec_ok, [&](auto xf32, auto vm) {
+        hipLaunchKernelGGL((spx_fwd_kernel<NPB, NCB, decltype(xf32)::value, decltype(vm)::value, GATHER, ACT, PRUNE>), grid, dim3(256), lds, s, a);
+    });
     return hipGetLastError();
 }
-template <int NPB, int NCB, int SPLIT>
+template <int NPB, int NCB>
 static hipError_t launch_fwd_x(const SpxFwdArgs& a, int x_dtype, dim3 grid, hipStream_t s) {
     if (a.labels && a.push_keys && a.push_prune) {
         // the prune mode runs on a one-row head layout (no logits): only one-class-block instances exist
-        if constexpr (NCB == 1) return launch_fwd_ga<NPB, NCB, SPLIT, true, false, true>(a, x_dtype, grid, s);
+        if constexpr (NCB == 1) return launch_fwd_ga<NPB, NCB, true, false, true>(a, x_dtype, grid, s);
         return hipErrorInvalidValue;
     }
-    if (a.labels) return a.act ? launch_fwd_ga<NPB, NCB, SPLIT, true, true>(a, x_dtype, grid, s)
-                               : launch_fwd_ga<NPB, NCB, SPLIT, true, false>(a, x_dtype, grid, s);
-    return a.act ? launch_fwd_ga<NPB, NCB, SPLIT, false, true>(a, x_dtype, grid, s)
-                 : launch_fwd_ga<NPB, NCB, SPLIT, false, false>(a, x_dtype, grid, s);
+    if (a.labels) return a.act ? launch_fwd_ga<NPB, NCB, true, true>(a, x_dtype, grid, s)
+                               : launch_fwd_ga<NPB, NCB, true, false>(a, x_dtype, grid, s);
+    return a.act ? launch_fwd_ga<NPB, NCB, false, true>(a, x_dtype, grid, s)
+                 : launch_fwd_ga<NPB, NCB, false, false>(a, x_dtype, grid, s);
 }
 
 // one translation unit per panel height (SPX_TU_NPB), so the variants compile in parallel
@@ -672,18 +594,17 @@ template <int NPB>
 static hipError_t spx_launch_fwd_tiles(const SpxFwdArgs& a, int x_dtype, hipStream_t s) {
     const spx_plan& pl = a.plan;
     dim3 grid((unsigned)(a.tiles_launch * a.B), (unsigned)(a.ngroups > 1 ? a.ngroups : 1));
-    // SPX_FWD_SPLIT 2 = 8-wave workgroups (4 waves per SIMD): measured 0.84 vs 0.72 ms at the north-star shape, off
-    if (pl.ncb == 1) return launch_fwd_x<NPB, 1, SPX_FWD_SPLIT>(a, x_dtype, grid, s);
+    if (pl.ncb == 1) return launch_fwd_x<NPB, 1>(a, x_dtype, grid, s);
     // 33..64 head rows (the grouping head: 3 groups x 19 / 21 classes)
-    if (pl.ncb == 2) return launch_fwd_x<NPB, 2, 1>(a, x_dtype, grid, s);
+    if (pl.ncb == 2) return launch_fwd_x<NPB, 2>(a, x_dtype, grid, s);
     // up to 160 classes: 80 logits accumulators per lane
-    return launch_fwd_x<NPB, 5, 1>(a, x_dtype, grid, s);
+    return launch_fwd_x<NPB, 5>(a, x_dtype, grid, s);
 }
 // one translation unit per panel height (SPX_TU_NPB), so the variants compile in parallel
 template <int NPB>
 static hipError_t spx_launch_fwd_npb(const SpxFwdArgs& a0, int x_dtype, hipStream_t s) {
     SpxFwdArgs a = a0;
-    a.vec_ok = a.HW < 8 ? 0 : (a.HW % 8 == 0 ? 1 : 2);      // the element-wise path only for images of fewer than 8 pixels
+    a.vec_ok = spx_x_stage_mode(a.HW);
     a.tile_first = 0;
     a.tiles_launch = (a.HW + SPX_TILE_PX - 1) / SPX_TILE_PX;
     a.tile_mul = spx_tile_mul(a.tiles_launch, (long long)a.HW * (x_dtype == 1 ? 4 : 2));

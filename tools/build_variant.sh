@@ -1,7 +1,7 @@
 #!/bin/bash
 # Development A/B: build a variant of some translation units with extra -D flags and link it with the other (already built)
 # objects into scaleprotoseg_amd/variants/libspx_<name>.so (selected at run time with SPX_LIB_OVERRIDE; the product library is
-# never touched).   tools/build_variant.sh <name> "<tu> [<tu> ...]" [flags...]      e.g.  ... nobar "spx_bwd_npb6" -DSPX_DIAG_X
+# never touched).   tools/build_variant.sh <name> "<tu> [<tu> ...]" [flags...]      e.g.  ... stamps "spx_fwd_npb6 spx_bwd_npb6 spx_api" -DSPX_DIAG_STAMPS
 set -e
 cd "$(dirname "$0")/../scaleprotoseg_amd"
 name=$1; tus=$2; shift 2
