@@ -491,6 +491,44 @@ int spx_reg_fwd(const spx_reg* r, float* total, float* terms, void* workspace, v
  * L1 is on.  Gradients as torch's autograd of the reference forms (clamp passes where w >= eps, sgn(0) = 0). */
 int spx_reg_bwd(const spx_reg* r, const float* g_total, const float* g_terms, float* d_wd, float* d_head, void* stream);
 
+/* Activation losses of the labelled pixels over class-gathered planes (additive to ABI 17; segmentation/model/loss.py:149-348).
+ * vals fp32 [B, J, HW] slot planes (spx_dist_fwd_cls, or gathered activations), labels int32 [B, HW] (class 0..K-1, anything
+ * else = no class), slot_scale int32 [K, J]: scale id of (class, slot), -1 = the class has no such slot, -2 = a slot that lies
+ * in no scale.  A segment is (image, class) with n pixels and Jc slots; a = activation of a pixel for a slot (mode 0: vals;
+ * mode 1: log((vals + 1) / (vals + epsilon)); mode 2: -vals; applied at load, the gradient is with respect to vals).
+ *   term 0 spatial entropy  mean over segments with n >= 2 of mean_j H_j / ln n, H_j = entropy of the softmax of a_j over the
+ *                           segment's pixels (ln n is a constant of the gradient)                              (:149-211)
+ *   term 1 sample entropy   mean over items (segment, scale) with n >= 1 and ns >= 2 slots of that scale of the pixel mean of
+ *                           the entropy of the softmax over the ns slots / ln ns; an item with ns < 2 is skipped  (:214-284)
+ *   term 2 norm             mean over segments with n >= 1 of mean_j (sum_px |a| / n) (norm_type 0, l1) or mean_j max_px |a|
+ *                           (norm_type 1, linf; the gradient is shared evenly by the pixels at the maximum)      (:287-348)
+ * A term without a segment / item is 0 with zero gradient.  Bit b of `terms` enables term b; a disabled term is 0, takes no
+ * part in the total and gets no gradient.  Call order: zero-fill `workspace` (spx_actloss_workspace_bytes), segment_max,
+ * segment_sums, finish; then backward any number of times.  Integer atomics and fixed-order sums only: run-to-run bit-identical.
+ * Limits: those of the spx_kld_* reduction passes (J <= 16, K*J*12 + K*4 + 8 <= 60 KiB), HW < 2^29. */
+#define SPX_ACT_SPAT 1
+#define SPX_ACT_SAMPL 2
+#define SPX_ACT_NORM 4
+typedef struct spx_actloss {
+    const float* vals;
+    const int32_t* labels;
+    const int32_t* slot_scale;
+    int32_t B, J, HW, W, K;          /* W: row length of the pixel grid (a traversal hint), 0 or a divisor of HW */
+    int32_t mode, terms, norm_type;
+    float epsilon;
+    float weights[3];
+} spx_actloss;
+size_t spx_actloss_workspace_bytes(const spx_actloss* a);
+int spx_actloss_segment_max(const spx_actloss* a, void* workspace, void* stream);
+int spx_actloss_segment_sums(const spx_actloss* a, void* workspace, void* stream);
+/* out fp32 [7]: the three terms, 1 / max(1, number of segments or items) of each, total = sum of weights[b] * term b.
+ * coef fp32 [B*K, 6, J]: what the backward reads per (segment, slot). */
+int spx_actloss_finish(const spx_actloss* a, void* workspace, float* coef, float* out, void* stream);
+/* grad fp32 [B, J, HW] = d/dvals, every element written.  Upstream of term b = g_total[0] * weights[b] + g_terms[b] (either
+ * pointer may be NULL = 0), read on the device. */
+int spx_actloss_backward(const spx_actloss* a, const float* coef, const float* g_total, const float* g_terms, float* grad,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

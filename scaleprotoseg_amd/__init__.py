@@ -18,6 +18,9 @@ Public surface mirrors the reference's module/function names for this path:
     EntropyGroup, CrossEntropyGroup, ScaleMax, GroupRegularizers, head_l1
                                                     (segmentation/model/loss.py:351-464 and the masked last-layer L1 of the
                                                      training modules: one forward and one backward launch, no host sync)
+    EntropySpatLoss, EntropySamplLoss, NormLoss, ActivationRegularizers
+                                                    (segmentation/model/loss.py:149-348: the activation-side terms over the
+                                                     class-gathered planes, two reduction passes + one gradient pass)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -39,12 +42,16 @@ from .functional import (  # noqa: F401
 )
 from .checkpoint import export_state, import_state, load_reference_state_dict  # noqa: F401
 from .loss import (  # noqa: F401
+    ActivationRegularizers,
     ClassDistances,
     CrossEntropyGroup,
     EntropyGroup,
+    EntropySamplLoss,
+    EntropySpatLoss,
     GroupRegularizers,
     KLDLoss,
     KLDLossGroup,
+    NormLoss,
     PixelWiseCrossEntropyLoss,
     ScaleMax,
     head_l1,

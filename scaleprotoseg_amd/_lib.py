@@ -80,9 +80,30 @@ class SpxReg(C.Structure):
     ]
 
 
+class SpxActLoss(C.Structure):
+    """spx_actloss of include/spx_hip.h: the activation losses' inputs (spx_actloss_*)."""
+
+    _fields_ = [
+        ("vals", C.c_void_p),
+        ("labels", C.c_void_p),
+        ("slot_scale", C.c_void_p),
+        ("B", C.c_int32),
+        ("J", C.c_int32),
+        ("HW", C.c_int32),
+        ("W", C.c_int32),
+        ("K", C.c_int32),
+        ("mode", C.c_int32),
+        ("terms", C.c_int32),
+        ("norm_type", C.c_int32),
+        ("epsilon", C.c_float),
+        ("weights", C.c_float * 3),
+    ]
+
+
 _PP = C.POINTER(SpxPlan)
 _PCE = C.POINTER(SpxCe)
 _PR = C.POINTER(SpxReg)
+_PA = C.POINTER(SpxActLoss)
 _V = C.c_void_p
 _I = C.c_int32
 _F = C.c_float
@@ -157,6 +178,11 @@ SIGNATURES = {
     "spx_reg_workspace_bytes": (C.c_size_t, [_PR]),
     "spx_reg_fwd": (C.c_int, [_PR, _V, _V, _V, _V]),
     "spx_reg_bwd": (C.c_int, [_PR, _V, _V, _V, _V, _V]),
+    "spx_actloss_workspace_bytes": (C.c_size_t, [_PA]),
+    "spx_actloss_segment_max": (C.c_int, [_PA, _V, _V]),
+    "spx_actloss_segment_sums": (C.c_int, [_PA, _V, _V]),
+    "spx_actloss_finish": (C.c_int, [_PA, _V, _V, _V, _V]),
+    "spx_actloss_backward": (C.c_int, [_PA, _V, _V, _V, _V, _V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -825,6 +825,43 @@ int spx_kld_backward(const float* vals, const int32_t* labels, int32_t B, int32_
 }
 
 // ptrs = 0: the workspace query, which needs the sizes only
+static int actloss_check(const char* who, const spx_actloss* a, int planes) {
+    if (!a) return fail("%s: NULL descriptor", who);
+    if (!a->slot_scale) return fail("%s: NULL slot_scale", who);
+    if (planes && (!a->vals || !a->labels)) return fail("%s: NULL buffer", who);
+    if (a->mode < 0 || a->mode > 2) return fail("%s: mode %d (0 activations, 1 log, 2 linear)", who, a->mode);
+    if (a->terms < 1 || a->terms > (SPX_ACT_SPAT | SPX_ACT_SAMPL | SPX_ACT_NORM)) return fail("%s: terms %d", who, a->terms);
+    if (a->norm_type != 0 && a->norm_type != 1) return fail("%s: norm_type %d (0 l1, 1 linf)", who, a->norm_type);
+    if (a->HW >= (1 << 29)) return fail("%s: HW too large", who);
+    // sizes: the domain of the KLD reduction passes
+    if (kld_check(who, (const float*)a->slot_scale, a->slot_scale, a->B, a->J, a->HW, a->K, a->slot_scale, 0)) return 1;
+    return kld_check_w(who, a->HW, a->W);
+}
+size_t spx_actloss_workspace_bytes(const spx_actloss* a) {
+    if (actloss_check("spx_actloss_workspace_bytes", a, 0)) return 0;
+    return spx_actloss_ws_bytes(a->B, a->K, a->J);
+}
+int spx_actloss_segment_max(const spx_actloss* a, void* workspace, void* stream) {
+    if (actloss_check("spx_actloss_segment_max", a, 1)) return 1;
+    if (!workspace) return fail("spx_actloss_segment_max: NULL workspace");
+    return hip_status(spx_launch_actloss_max(a, workspace, (hipStream_t)stream), "spx_actloss_segment_max");
+}
+int spx_actloss_segment_sums(const spx_actloss* a, void* workspace, void* stream) {
+    if (actloss_check("spx_actloss_segment_sums", a, 1)) return 1;
+    if (!workspace) return fail("spx_actloss_segment_sums: NULL workspace");
+    return hip_status(spx_launch_actloss_sums(a, workspace, (hipStream_t)stream), "spx_actloss_segment_sums");
+}
+int spx_actloss_finish(const spx_actloss* a, void* workspace, float* coef, float* out, void* stream) {
+    if (actloss_check("spx_actloss_finish", a, 0)) return 1;
+    if (!workspace || !coef || !out) return fail("spx_actloss_finish: NULL buffer");
+    return hip_status(spx_launch_actloss_finish(a, workspace, coef, out, (hipStream_t)stream), "spx_actloss_finish");
+}
+int spx_actloss_backward(const spx_actloss* a, const float* coef, const float* g_total, const float* g_terms, float* grad, void* stream) {
+    if (actloss_check("spx_actloss_backward", a, 1)) return 1;
+    if (!coef || !grad) return fail("spx_actloss_backward: NULL buffer");
+    return hip_status(spx_launch_actloss_backward(a, coef, g_total, g_terms, grad, (hipStream_t)stream), "spx_actloss_backward");
+}
+
 static int reg_check(const char* who, const spx_reg* r, int ptrs = 1) {
     if (!r) return fail("%s: NULL descriptor", who);
     if (r->terms < 1 || r->terms > 15) return fail("%s: term mask %d (1..15)", who, r->terms);

@@ -207,5 +207,11 @@ hipError_t spx_launch_kld_lse(const uint32_t* keys, const uint64_t* ssum_fx, int
                               double* scale_out, hipStream_t s);
 hipError_t spx_launch_kld_gram_loss(const int64_t* a_fx, const double* scale, const uint32_t* counts, const uint8_t* pair_ok, int nseg, int K,
                                     int J, float* A, float* Cf, double* part, float* loss, hipStream_t s);
+size_t spx_actloss_ws_bytes(int B, int K, int J);
+hipError_t spx_launch_actloss_max(const spx_actloss* p, void* workspace, hipStream_t s);
+hipError_t spx_launch_actloss_sums(const spx_actloss* p, void* workspace, hipStream_t s);
+hipError_t spx_launch_actloss_finish(const spx_actloss* p, void* workspace, float* coef, float* out, hipStream_t s);
+hipError_t spx_launch_actloss_backward(const spx_actloss* p, const float* coef, const float* g_total, const float* g_terms, float* grad,
+                                       hipStream_t s);
 hipError_t spx_launch_kld(int pass, const float* vals, const int32_t* labels, int B, int J, int HW, int W, int K, const float* t0,
                           const float* t1, const float* t2, const double* scale, void* out, hipStream_t s, const float* cf_scale = nullptr);

@@ -563,3 +563,209 @@ def head_l1(ppnet) -> torch.Tensor:
     """``(W * (1 - identity^T)).norm(p=1)`` of ``last_layer`` (prototype phase, module_multiscale.py:260-261, module.py:218-220)
     or ``last_layer_group`` (group phase, module_multiscale_group_train.py:283-285) in one launch; differentiable to W."""
     return _reg_apply(ppnet, REG_L1, (0.0, 0.0, 0.0, 1.0), 1e-5, ppnet)[0]
+
+
+# ---- activation losses of the labelled pixels (segmentation/model/loss.py:149-348) ---------------------------------------
+ACT_SPAT, ACT_SAMPL, ACT_NORM = 1, 2, 4                # SPX_ACT_* of include/spx_hip.h: term b <-> bit b
+_ACT_MODES = {"log": 1, "linear": 2}
+_NORM_TYPES = {"l1": 0, "linf": 1}
+
+
+def slot_scale_table(table: torch.Tensor, num_scales: int, scale_num_prototypes) -> torch.Tensor:
+    """[K, J] int32 scale id of (class, slot) for a ``class_slot_table``: -1 = the class has no such slot, -2 = a prototype
+    that lies in no scale's range (it counts for the spatial entropy and the norm, not for the sample entropy)."""
+    t = table.detach().cpu().long()
+    sid = torch.where(t >= 0, torch.full_like(t, -2), torch.full_like(t, -1))
+    for s in range(int(num_scales)):
+        lo, hi = scale_num_prototypes[s]
+        sid[(t >= int(lo)) & (t < int(hi))] = s
+    return sid.to(torch.int32).contiguous()
+
+
+def _act_desc(v, lab, sid, cfg):
+    from . import _lib
+
+    B, J, HW = v.shape
+    d = _lib.SpxActLoss()
+    d.vals, d.labels, d.slot_scale = _lib.ptr(v), _lib.ptr(lab), _lib.ptr(sid)
+    d.B, d.J, d.HW, d.W, d.K = B, J, HW, cfg["W"], cfg["K"]
+    d.mode, d.terms, d.norm_type = cfg["mode"], cfg["terms"], cfg["norm_type"]
+    d.epsilon = cfg["epsilon"]
+    d.weights = (C.c_float * 3)(*cfg["weights"])
+    return d
+
+
+class _ActLossFn(torch.autograd.Function):
+    """(total, terms[3]) of class-gathered planes in FOUR launches (workspace fill, segment maxima, segment sums, finish:
+    csrc/spx_actloss.hip); backward ONE launch, scaled by the upstream gradients read on the device."""
+
+    @staticmethod
+    def forward(ctx, vals, labels, sid, cfg):
+        from . import _lib
+
+        lib = _lib.load()
+        v = vals.detach().contiguous()
+        lab = labels.to(device=v.device, dtype=torch.int32).contiguous()
+        B, J, HW = v.shape
+        s = _lib.stream_ptr()
+        d = _act_desc(v, lab, sid, cfg)
+        nbytes = lib.spx_actloss_workspace_bytes(C.byref(d))
+        if nbytes == 0:
+            raise SpxError(lib.spx_last_error().decode("utf-8", "replace"))
+        ws = torch.zeros((nbytes // 8,), dtype=torch.int64, device=v.device)
+        coef = torch.empty((B * cfg["K"], 6, J), dtype=torch.float32, device=v.device)
+        out = torch.empty((7,), dtype=torch.float32, device=v.device)
+        _lib.check(lib.spx_actloss_segment_max(C.byref(d), _lib.ptr(ws), s))
+        _lib.check(lib.spx_actloss_segment_sums(C.byref(d), _lib.ptr(ws), s))
+        _lib.check(lib.spx_actloss_finish(C.byref(d), _lib.ptr(ws), _lib.ptr(coef), _lib.ptr(out), s))
+        ctx.save_for_backward(v, lab, sid, coef)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        return out[6].reshape(()), out[:3]
+
+    @staticmethod
+    def backward(ctx, g_total, g_terms):
+        from . import _lib
+
+        if g_total is None and g_terms is None:
+            return None, None, None, None
+        v, lab, sid, coef = ctx.saved_tensors
+        gt = g_total.float().reshape(1).contiguous() if g_total is not None else None
+        gs = g_terms.float().contiguous() if g_terms is not None else None
+        grad = torch.empty_like(v)
+        d = _act_desc(v, lab, sid, ctx.cfg)
+        _lib.check(_lib.load().spx_actloss_backward(C.byref(d), _lib.ptr(coef), _lib.ptr(gt), _lib.ptr(gs), _lib.ptr(grad), _lib.stream_ptr()))
+        return grad, None, None, None
+
+
+class ActivationRegularizers(nn.Module):
+    """The activation-side terms of the training objective (segmentation/model/loss.py:149-348; module_multiscale.py:170-175,
+    module_multiscale_group_train.py:189-190) in one pipeline: ``forward(prototype_activations, target_labels)`` returns
+    ``(total, terms)`` with terms = [spatial entropy, sample entropy, norm] (fp32 [3], for logging without a sync) and total =
+    ent_spat * terms[0] + ent_sampl * terms[1] + norm * terms[2].  The analogue of ``GroupRegularizers`` for the terms that read
+    the prototype activations of the labelled pixels; ``EntropySpatLoss``, ``EntropySamplLoss`` and ``NormLoss`` are this class
+    with one term.
+
+    ``prototype_activations`` is the [M, P] / [B, H*W, P] activation tensor (its class-gathered entries are taken with torch), or
+    the ``ClassDistances`` of ``forward_from_conv_features(..., target_labels=...)``: the activation (``activation`` = "log":
+    log((d+1)/(d+epsilon)), or "linear": -d) is then applied inside the kernels and the gradient reaches the distances, so
+    neither the P-wide map nor an activation plane crosses HBM.  Labels: 0 = void, 1..K = class, anything else no class.
+
+    Divergence from the reference, sample entropy: a (class, scale) with fewer than two prototypes is skipped.  The reference
+    divides by ln 1 = 0 there (NaN for one prototype) and raises from ``torch.stack([])`` for none.  A term without any segment
+    is a device scalar 0 (the reference returns a CPU tensor).  GPU fp32 only, at most 16 prototypes per class: anything else
+    raises ``SpxError``; there is no other backend."""
+
+    def __init__(self, prototype_class_identity: torch.Tensor, num_scales: int, scale_num_prototypes: Dict[int, Tuple[int, int]],
+                 ent_spat: float = 0.0, ent_sampl: float = 0.0, norm: float = 0.0, norm_type: str = "l1", epsilon: float = 1e-4,
+                 activation: str = "log") -> None:
+        super().__init__()
+        self._setup(prototype_class_identity, num_scales, scale_num_prototypes, ACT_SPAT | ACT_SAMPL | ACT_NORM,
+                    (ent_spat, ent_sampl, norm), norm_type, epsilon, activation)
+
+    def _setup(self, ident, num_scales, scale_num_prototypes, terms, weights, norm_type, epsilon, activation) -> None:
+        if norm_type not in _NORM_TYPES:
+            raise ValueError(f"norm_type must be 'l1' or 'linf', got {norm_type!r}")
+        if activation not in _ACT_MODES:
+            raise ValueError(f"activation must be 'log' or 'linear', got {activation!r}")
+        self.prototype_class_identity = ident
+        self.num_scales = num_scales
+        self.scale_num_prototypes = scale_num_prototypes
+        self.norm_type = norm_type
+        self.epsilon = epsilon
+        self.activation = activation
+        self._terms, self._weights = int(terms), tuple(float(w) for w in weights)
+
+    def _slot_table(self) -> torch.Tensor:
+        ident = self.prototype_class_identity
+        c = getattr(self, "_slot_table_cache", None)
+        if c is None or c[0] is not ident or c[1] != ident._version:
+            c = (ident, ident._version, class_slot_table(ident))
+            self._slot_table_cache = c
+        return c[2]
+
+    def _tables_on(self, table: torch.Tensor, dev):
+        """(table on ``dev``, its slot-scale table on ``dev``), cached per table OBJECT, in-place version, scale ranges and
+        device: host work with a read-back, done once.  A few entries, so that one module can serve the model's table (a
+        ``ClassDistances``) and its own (an activation tensor) in turn; an entry holds its table, so an id cannot be recycled."""
+        scales = tuple((int(s), tuple(int(x) for x in self.scale_num_prototypes[s])) for s in range(int(self.num_scales)))
+        key = (table._version, scales, str(dev))
+        cache = getattr(self, "_act_tables_cache", None)
+        if cache is None:
+            cache = self._act_tables_cache = []
+        for c in cache:
+            if c[0] is table and c[1] == key:
+                return c[2], c[3]
+        sid = slot_scale_table(table, self.num_scales, self.scale_num_prototypes).to(dev)
+        cache.insert(0, (table, key, table.to(dev), sid))
+        del cache[4:]
+        return cache[0][2], cache[0][3]
+
+    def _run(self, prototype_activations, target_labels: torch.Tensor):
+        cd = prototype_activations if isinstance(prototype_activations, ClassDistances) else None
+        src = cd.values if cd is not None else prototype_activations
+        if not src.is_cuda:
+            raise SpxError(f"activation losses: input on {src.device}; the losses run on the GPU only (no CPU fallback)")
+        if src.dtype != torch.float32:
+            raise SpxError(f"activation losses: input is {src.dtype}; the kernels take fp32")
+        dev = src.device
+        if cd is not None:
+            if cd.target is target_labels and cd.target_version == target_labels._version:
+                labels0 = cd.labels                                                     # already target - 1 (int32)
+            else:
+                labels0 = target_labels.reshape(target_labels.shape[0], -1).long() - 1
+            table, sid = self._tables_on(cd.table, dev)
+            planes, mode, W = cd.values, _ACT_MODES[self.activation], int(cd.grid[-1])
+        else:
+            B = target_labels.shape[0]
+            labels0 = target_labels.reshape(B, -1).long().to(dev) - 1                  # loss.py:167
+            table, sid = self._tables_on(self._slot_table(), dev)
+            K = table.shape[0]
+            act = prototype_activations.reshape(B, -1, self.prototype_class_identity.shape[0])
+            idx = table[labels0.clamp(0, K - 1)].clamp(min=0)                           # [B, HW, J]; unused entries are masked in the kernels
+            planes = torch.gather(act, 2, idx).permute(0, 2, 1).contiguous()
+            mode, W = 0, (int(target_labels.shape[-1]) if target_labels.dim() >= 3 else 0)
+        K, J = table.shape
+        if not _kld_kernels_usable(planes, K, J):
+            raise SpxError(f"activation losses: planes {tuple(planes.shape)} (K={K}, J={J}) are outside the HIP kernels' domain "
+                           "(J <= 16, K*J*12 <= 60 KiB); there is no other backend")
+        HW = planes.shape[2]
+        cfg = {"K": K, "W": W if W and HW % W == 0 else 0, "mode": mode, "terms": self._terms,
+               "norm_type": _NORM_TYPES[self.norm_type], "epsilon": float(self.epsilon), "weights": self._weights}
+        return _ActLossFn.apply(planes, labels0, sid, cfg)
+
+    def forward(self, prototype_activations: Union[torch.Tensor, ClassDistances], target_labels: torch.Tensor):
+        return self._run(prototype_activations, target_labels)
+
+
+class _OneActTerm(ActivationRegularizers):
+    def forward(self, prototype_activations: Union[torch.Tensor, ClassDistances], target_labels: torch.Tensor) -> torch.Tensor:
+        return self._run(prototype_activations, target_labels)[0]       # total = 1 * term
+
+
+class EntropySpatLoss(_OneActTerm):
+    """Drop-in for segmentation/model/loss.py:149-211 on the GPU kernels (see ``ActivationRegularizers``); ``epsilon`` and
+    ``activation`` are used only when a ``ClassDistances`` is passed."""
+
+    def __init__(self, prototype_class_identity: torch.Tensor, *, epsilon: float = 1e-4, activation: str = "log") -> None:
+        nn.Module.__init__(self)
+        self._setup(prototype_class_identity, 0, {}, ACT_SPAT, (1.0, 0.0, 0.0), "l1", epsilon, activation)
+
+
+class EntropySamplLoss(_OneActTerm):
+    """Drop-in for segmentation/model/loss.py:214-284 on the GPU kernels.  Divergence: a (class, scale) with fewer than two
+    prototypes is skipped (the reference is NaN for one and raises for none); see ``ActivationRegularizers``."""
+
+    def __init__(self, prototype_class_identity: torch.Tensor, num_scales: int, scale_num_prototypes: Dict[int, Tuple[int, int]], *,
+                 epsilon: float = 1e-4, activation: str = "log") -> None:
+        nn.Module.__init__(self)
+        self._setup(prototype_class_identity, num_scales, scale_num_prototypes, ACT_SAMPL, (0.0, 1.0, 0.0), "l1", epsilon, activation)
+
+
+class NormLoss(_OneActTerm):
+    """Drop-in for segmentation/model/loss.py:287-348 on the GPU kernels: ``norm_type`` "l1" or "linf" (anything else raises
+    ``ValueError`` here; the reference fails in forward); the linf gradient is shared evenly by the pixels at the maximum."""
+
+    def __init__(self, prototype_class_identity: torch.Tensor, norm_type: str, *, epsilon: float = 1e-4, activation: str = "log") -> None:
+        nn.Module.__init__(self)
+        self._setup(prototype_class_identity, 0, {}, ACT_NORM, (0.0, 0.0, 1.0), norm_type, epsilon, activation)
