@@ -435,11 +435,17 @@ class _Packs:
 # ---- pack cache: the MFMA-ordered operands depend on the parameters only, so an unchanged bank / head /
 # tail (inference, evaluation, several forwards per optimizer step) reuses them instead of re-running the pack kernels and
 # their five allocations per forward.  Key: (object, ``_version``, ``data_ptr``) of each parameter + the plan + what was packed.
-# ``_version`` follows every in-place edit made THROUGH the parameter (optimizer steps, ``copy_``, ``add_``); a new Parameter
-# object (``prune_prototypes``) or new storage (``weight.data = ...``: the simplex projection) changes the key too.  The one
-# edit none of them sees is an in-place write through ``.data`` (``p.data.copy_(...)``: ``.data`` has its own version counter):
-# the package's own such sites (the push commit, the ``_initialize_weights`` fills) call ``invalidate_pack_cache()``, and so must
-# foreign code that edits a parameter that way.
+# ``_version`` follows every in-place edit made THROUGH the parameter (optimizer steps, ``copy_``, ``add_``,
+# ``load_state_dict``); a new Parameter object (``prune_prototypes``, ``load_state_dict(assign=True)``) changes the key too.
+# A rebind of the storage (``weight.data = ...``: the simplex projection; ``Module._apply``: ``.cpu()`` / ``.to(device)`` / dtype
+# casts) leaves ``_version`` alone and is seen through ``data_ptr`` only - and the allocator reissues a freed block to the next
+# request of its size, so the third value of a parameter would sit under the key of the first.  Every entry therefore HOLDS the
+# storages it packed from: while it lives their addresses cannot be handed out again, so an equal key means the same storage
+# (the weak reference: the same object), unchanged as far as its version counter can tell.  A miss drops the entries that can no
+# longer hit (an older version or storage of the same object, a dead object), which also releases what they hold.
+# The one edit nothing here sees is an in-place write through ``.data`` (``p.data.copy_(...)``: ``.data`` has its own version
+# counter): the package's own such sites (the push commit, the ``_initialize_weights`` fills) call ``invalidate_pack_cache()``,
+# and so must foreign code that edits a parameter that way.
 import collections as _collections
 import weakref as _weakref
 
@@ -457,24 +463,40 @@ def _tensor_key(t: Optional[torch.Tensor]):
     return None if t is None else (id(t), int(t._version), int(t.data_ptr()), tuple(t.shape), t.dtype)
 
 
+def _superseded(entry_key, refs, key, tensors) -> bool:
+    """An entry that cannot hit again: one of its tensors is gone, or is one of ``tensors`` under an older version / storage."""
+    for i, (r, t) in enumerate(zip(refs, tensors)):
+        if r is None:
+            continue
+        obj = r()
+        if obj is None or (obj is t and entry_key[1 + i] != key[1 + i]):
+            return True
+    return False
+
+
 def _cached_packs(plan_key, plan, bank, head, tail, bank2d, head2d, tail2d, need_bwd):
     if torch.cuda.is_current_stream_capturing():
         # a captured step is replayed after its parameters have been edited in place (the static-buffer protocol of HIP graphs):
         # the pack kernels must be part of the graph
         return _Packs(plan, bank2d, head2d, need_bwd, tail2d)
+    tensors = (bank, head, tail)
     key = (plan_key, _tensor_key(bank), _tensor_key(head), _tensor_key(tail), bool(need_bwd))
     hit = _PACK_CACHE.get(key)
     if hit is not None:
-        refs, packs = hit
-        if all((r is None and t is None) or (r is not None and r() is t) for r, t in zip(refs, (bank, head, tail))):
+        refs, _, packs = hit
+        if all((r is None and t is None) or (r is not None and r() is t) for r, t in zip(refs, tensors)):
             _PACK_CACHE.move_to_end(key)
             PACK_CACHE_STATS["hits"] += 1
             return packs
         del _PACK_CACHE[key]
     PACK_CACHE_STATS["misses"] += 1
     packs = _Packs(plan, bank2d, head2d, need_bwd, tail2d)
-    refs = tuple(None if t is None else _weakref.ref(t) for t in (bank, head, tail))
-    _PACK_CACHE[key] = (refs, packs)
+    # (after the new packs exist: the blocks the dropped entries release are not taken by these very allocations)
+    for k in [k for k, (refs, _, _) in _PACK_CACHE.items() if _superseded(k, refs, key, tensors)]:
+        del _PACK_CACHE[k]
+    refs = tuple(None if t is None else _weakref.ref(t) for t in tensors)
+    storages = tuple(None if t is None else t.untyped_storage() for t in tensors)
+    _PACK_CACHE[key] = (refs, storages, packs)
     while len(_PACK_CACHE) > _PACK_CACHE_MAX:
         _PACK_CACHE.popitem(last=False)
     return packs

@@ -24,7 +24,15 @@ from ._lib import SpxError
 @dataclass
 class ClassDistances:
     """values [B, J, H*W] (slot planes: entry (j, px) = distance to prototype j of the pixel's class), labels [B, H*W] int
-    (class 0..K-1, anything else = no class), table [K, J] prototype index of (class, slot) or -1."""
+    (class 0..K-1, anything else = no class), table [K, J] prototype index of (class, slot) or -1.
+
+    The planes belong to the labels they were gathered under.  ``KLDLoss`` and ``ActivationRegularizers`` take the label
+    map they are called with: handed ``target`` itself, unedited, they use ``labels`` as they are (no further launch); handed any
+    other tensor (or ``target`` after an in-place edit) they shift that map and compare it with ``labels`` on the device.  Equal
+    classes at every pixel (a clone, a reloaded batch) give the same value.  If a single pixel has another class the planes
+    hold the wrong prototypes' distances for it and cannot be gathered again from here, so the loss - and with it every
+    gradient - is NaN instead of a finite number that belongs to neither label map (no host synchronisation: the NaN is
+    made on the device).  Run the forward again with the new labels."""
 
     values: torch.Tensor
     labels: torch.Tensor
@@ -60,6 +68,22 @@ def gather_class_distances(prototype_distances: torch.Tensor, labels0: torch.Ten
     valid = ok.unsqueeze(-1) & (idx >= 0)
     out = torch.gather(d, 2, idx.clamp(min=0))
     return torch.where(valid, out, torch.zeros_like(out))
+
+
+def _labels_of(cd: ClassDistances, target_labels: torch.Tensor):
+    """(labels0 [B, H*W], poison or None) for a loss that is handed ``cd`` and ``target_labels``: ``cd.labels`` when the map is
+    the very tensor the planes were gathered under; else the shifted map and a device scalar that is 1 where it names the same
+    class at every pixel (out-of-range values are all "no class") and NaN otherwise - see ``ClassDistances``."""
+    if cd.target is target_labels and cd.target_version == target_labels._version:
+        return cd.labels, None                                                    # already target - 1 (int32)
+    labels0 = target_labels.reshape(target_labels.shape[0], -1).long() - 1      # loss.py:73
+    K = int(cd.table.shape[0])
+    cls = lambda t: torch.where((t >= 0) & (t < K), t, torch.full_like(t, -1))
+    mine = cd.labels.reshape(cd.labels.shape[0], -1).long()
+    if labels0.shape != mine.shape:
+        raise SpxError(f"labels {tuple(target_labels.shape)} do not match the ClassDistances' {tuple(mine.shape)} pixels")
+    differ = (cls(labels0.to(mine.device)) != cls(mine)).any()
+    return labels0, torch.where(differ, float("nan"), 1.0)
 
 
 class PixelWiseCrossEntropyLoss(nn.Module):
@@ -243,8 +267,9 @@ class KLDLoss(nn.Module):
 
     def forward(self, prototype_distances: Union[torch.Tensor, ClassDistances], target_labels: torch.Tensor) -> torch.Tensor:
         cd = prototype_distances if isinstance(prototype_distances, ClassDistances) else None
-        if cd is not None and cd.target is target_labels and cd.target_version == target_labels._version:
-            labels0 = cd.labels                                                           # already target - 1 (int32)
+        poison = None
+        if cd is not None:
+            labels0, poison = _labels_of(cd, target_labels)
         else:
             labels0 = target_labels.reshape(target_labels.shape[0], -1).long() - 1      # loss.py:73
         if isinstance(prototype_distances, ClassDistances):
@@ -255,7 +280,8 @@ class KLDLoss(nn.Module):
             vals = gather_class_distances(prototype_distances, labels0, table)
         planes = prototype_distances.values if isinstance(prototype_distances, ClassDistances) else None
         width = prototype_distances.grid[-1] if isinstance(prototype_distances, ClassDistances) else prototype_distances.shape[-1]
-        return self._forward_gathered(vals, planes, labels0, table, width)
+        loss = self._forward_gathered(vals, planes, labels0, table, width)
+        return loss if poison is None else loss * poison.to(loss.device)       # NaN when the planes were gathered under other classes
 
     def _forward_gathered(self, vals: torch.Tensor, planes, labels0: torch.Tensor, table: torch.Tensor, width: int = 0) -> torch.Tensor:
         """Loss from the class-gathered values ``vals`` [B, H*W, J] (``planes``: the same as [B, J, H*W], if the caller
@@ -709,11 +735,9 @@ class ActivationRegularizers(nn.Module):
         if src.dtype != torch.float32:
             raise SpxError(f"activation losses: input is {src.dtype}; the kernels take fp32")
         dev = src.device
+        poison = None
         if cd is not None:
-            if cd.target is target_labels and cd.target_version == target_labels._version:
-                labels0 = cd.labels                                                     # already target - 1 (int32)
-            else:
-                labels0 = target_labels.reshape(target_labels.shape[0], -1).long() - 1
+            labels0, poison = _labels_of(cd, target_labels)
             table, sid = self._tables_on(cd.table, dev)
             planes, mode, W = cd.values, _ACT_MODES[self.activation], int(cd.grid[-1])
         else:
@@ -732,7 +756,10 @@ class ActivationRegularizers(nn.Module):
         HW = planes.shape[2]
         cfg = {"K": K, "W": W if W and HW % W == 0 else 0, "mode": mode, "terms": self._terms,
                "norm_type": _NORM_TYPES[self.norm_type], "epsilon": float(self.epsilon), "weights": self._weights}
-        return _ActLossFn.apply(planes, labels0, sid, cfg)
+        total, terms = _ActLossFn.apply(planes, labels0, sid, cfg)
+        if poison is not None:                                                          # NaN when the planes were gathered under other classes
+            total, terms = total * poison.to(total.device), terms * poison.to(terms.device)
+        return total, terms
 
     def forward(self, prototype_activations: Union[torch.Tensor, ClassDistances], target_labels: torch.Tensor):
         return self._run(prototype_activations, target_labels)

@@ -132,7 +132,10 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
     def _group_index(self, device):
         """(rows, cols, number of units, GroupTables) of every group-projection weight inside the dense [NG, P] head matrix."""
         ident = self.prototype_class_identity
-        key = (self._tables_version, ident._version, tuple(gp.weight.shape for gp in self.group_projection), str(device))
+        # (the scale ranges: the ScaleMax spans hang on these tables, and ``scale_num_prototypes[s] = ...`` is an item edit of a
+        # dict that passes no __setattr__)
+        scales = tuple(tuple(int(v) for v in self.scale_num_prototypes[s]) for s in range(self.num_scales))
+        key = (self._tables_version, ident._version, tuple(gp.weight.shape for gp in self.group_projection), scales, str(device))
         c = self._group_index_cache
         if c is not None and c[0] is ident and c[1] == key:
             return c[2]

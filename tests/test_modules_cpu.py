@@ -336,3 +336,63 @@ def test_kld_loss_refuses_inputs_outside_the_kernels():
         gci[2 * k:2 * k + 2, k] = 1
     with pytest.raises(SpxError):
         KLDLossGroup(ident, gci, 2)([torch.rand(9, 2) for _ in range(4)], torch.ones(1, 3, 3, dtype=torch.long))
+
+
+def test_torch_version_counter_behaviour_the_pack_cache_key_relies_on():
+    """The pack cache (scaleprotoseg_amd/functional.py) keys on the Parameter object, its ``_version`` and its storage.  What
+    torch does to those three under each kind of edit is pinned here, so that a torch upgrade that changes any of it fails in
+    this test and not in training."""
+    p = nn.Parameter(torch.rand(4, 3))
+    v, ptr, held = p._version, p.data_ptr(), p.data
+    p.data = torch.rand(4, 3)                                   # a rebind through .data: new storage, the SAME version
+    assert p._version == v and p.data_ptr() != ptr and held.data_ptr() == ptr
+    p.data.copy_(torch.rand(4, 3))                              # an in-place write through .data: invisible to the version
+    p.data.add_(1.0)
+    assert p._version == v
+    with torch.no_grad():                                       # in-place edits through the parameter itself bump it
+        p.copy_(torch.rand(4, 3))
+        assert p._version > v
+        v = p._version
+        p.add_(1.0)
+        assert p._version > v
+
+
+def test_torch_module_edits_the_pack_cache_key_relies_on():
+    lin = nn.Linear(3, 4, bias=False)
+    w = lin.weight
+    v = w._version
+    lin.load_state_dict({"weight": torch.rand(4, 3)})           # default: copy_ into the same Parameter
+    assert lin.weight is w and w._version > v
+    for make in (lambda ps: torch.optim.SGD(ps, lr=0.1), lambda ps: torch.optim.Adam(ps, lr=0.1, foreach=True),
+                 lambda ps: torch.optim.Adam(ps, lr=0.1, foreach=False)):
+        v, before = w._version, w.detach().clone()
+        w.grad = torch.ones_like(w)
+        make([w]).step()
+        assert lin.weight is w and w._version > v and not torch.equal(w.detach(), before)
+    w.grad = None
+    lin.load_state_dict({"weight": torch.rand(4, 3)}, assign=True)      # assign: ANOTHER Parameter object (same requires_grad)
+    assert lin.weight is not w and isinstance(lin.weight, nn.Parameter) and lin.weight.requires_grad
+    # Module._apply-style casts and moves (.double(), .float(), .cpu(), .to(device)): the same object and version on new storage
+    w = lin.weight
+    v, held = w._version, w.data
+    lin.double()
+    assert lin.weight is w and w._version == v and w.dtype == torch.float64 and w.data_ptr() != held.data_ptr()
+    lin.float()
+    assert lin.weight is w and w._version == v and w.dtype == torch.float32 and w.data_ptr() != held.data_ptr()
+    assert torch.equal(w.detach(), held)
+
+
+def test_scale_table_item_edits_reach_the_group_tables():
+    """``scale_num_prototypes[s] = ...`` is an item edit of a dict: it passes no ``__setattr__``, so the caches that read the
+    scale ranges carry them in their keys (the gather and push tables through the layout, the group tables' ScaleMax spans)."""
+    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet, group_scale_spans
+
+    net = GroupNet(_Backbone(32), 64, (24, 16, 1, 1), [], 3, add_on_layers_type="deeplab_simple",
+                   patch_classification=True, num_scales=2, num_groups=2)
+    spans = lambda: group_scale_spans(net.prototype_class_identity, net.scale_num_prototypes, 2, 2)[1]
+    before = spans()
+    idx = net._group_index("cpu")
+    assert net._group_index("cpu") is idx
+    net.scale_num_prototypes[0], net.scale_num_prototypes[1] = (0, 8), (8, 24)
+    assert not torch.equal(spans(), before)
+    assert net._group_index("cpu") is not idx                   # rebuilt: the span tables hang on it
