@@ -529,6 +529,32 @@ int spx_actloss_finish(const spx_actloss* a, void* workspace, float* coef, float
 int spx_actloss_backward(const spx_actloss* a, const float* coef, const float* g_total, const float* g_terms, float* grad,
                          void* stream);
 
+/* Activation-overlap metrics (additive to ABI 17; segmentation/analysis/prototype_overlap.py:28-92, group_overlap.py:28-87):
+ * how much the high-activation regions of one class's prototypes (or groups) overlap.
+ *   planes     fp32 [N, C, h, w] activation planes, addressed through host_strides = element strides of (n, c, y, x)
+ *   u[n,c,Y,X] the plane upsampled to H x W as OpenCV INTER_CUBIC / F.interpolate(mode="bicubic", align_corners=False) define
+ *              it: source coordinate (X + 0.5) * w / W - 0.5, four taps per axis, Keys' kernel with a = -0.75, tap indices
+ *              clamped to the grid; computed in fp32 and never written to memory
+ *   T[n,c]     np.quantile(u[n,c], q), linear method: the caller passes k = floor(q * (H*W - 1)) and gamma = the fractional part
+ *              (float64 on the host, gamma rounded to fp32); with v = the sorted values, d = v[k+1] - v[k]:
+ *              T = gamma >= 0.5 ? v[k+1] - d * (1 - gamma) : v[k] + d * gamma in fp32 (numpy's _lerp)
+ *   mask       u > T (strict: a constant plane has an empty mask)
+ * spx_overlap_thresholds writes T fp32 [N, C], found by an exact radix select (integer histograms: run-to-run identical).
+ * spx_overlap_accumulate ADDS, for image n and every class k with a pixel labels[n] == k + 1 (labels as spx_eval_accumulate
+ * takes them), over the slots j of slot_table int32 [K, J] (channel of (class, slot); outside [0, C) = no such slot):
+ *   area[k, j] += |mask_j|;   inter[k, j, j'] += |mask_j & mask_j'| for j < j';   images[k] += 1
+ * (int64 [K, J], [K, J, J], [K]; the union of a pair is area_j + area_j' - inter).  thresholds: what spx_overlap_thresholds
+ * wrote for the same planes and size.  workspace: spx_overlap_workspace_bytes(N, C, K) bytes (independent of H and W; 0 and
+ * spx_last_error for bad sizes), no initialisation needed, one call at a time per workspace.
+ * Limits: J <= 32, K <= 1024, C <= 4096, N <= 65535, H*W < 2^31, H and W <= 32768, h <= 16384, w <= 1638. */
+size_t spx_overlap_workspace_bytes(int32_t N, int32_t C, int32_t K);
+int spx_overlap_thresholds(const float* planes, const int64_t* host_strides, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
+                           int32_t W, int64_t k, float gamma, void* workspace, float* thresholds, void* stream);
+int spx_overlap_accumulate(const float* planes, const int64_t* host_strides, const float* thresholds, const void* labels,
+                           int32_t label_bytes, const int32_t* slot_table, int32_t N, int32_t C, int32_t K, int32_t J, int32_t h,
+                           int32_t w, int32_t H, int32_t W, int64_t* inter, int64_t* area, int64_t* images, void* workspace,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

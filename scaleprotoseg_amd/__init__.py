@@ -21,6 +21,9 @@ Public surface mirrors the reference's module/function names for this path:
     EntropySpatLoss, EntropySamplLoss, NormLoss, ActivationRegularizers
                                                     (segmentation/model/loss.py:149-348: the activation-side terms over the
                                                      class-gathered planes, two reduction passes + one gradient pass)
+    ActivationOverlap, high_activation_threshold    (segmentation/analysis/prototype_overlap.py, group_overlap.py: overlap
+                                                     mIoU of the high-activation masks of one class's prototypes / groups;
+                                                     cubic upsample + exact quantile threshold, recomputed, never stored)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -58,6 +61,7 @@ from .loss import (  # noqa: F401
 )
 from .metrics import SegmentationMetrics, SegmentationResult  # noqa: F401
 from .model import PPNet  # noqa: F401
+from .overlap import ActivationOverlap, OverlapResult, high_activation_threshold  # noqa: F401
 from .model_multiscale import PPNetMultiScale, construct_PPNet  # noqa: F401
 from .model_multiscale_group import PPNetMultiScaleGroup, construct_PPNet_Group  # noqa: F401
 from .push import (  # noqa: F401

@@ -183,6 +183,9 @@ SIGNATURES = {
     "spx_actloss_segment_sums": (C.c_int, [_PA, _V, _V]),
     "spx_actloss_finish": (C.c_int, [_PA, _V, _V, _V, _V]),
     "spx_actloss_backward": (C.c_int, [_PA, _V, _V, _V, _V, _V]),
+    "spx_overlap_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "spx_overlap_thresholds": (C.c_int, [_V, _PL, _I, _I, _I, _I, _I, _I, C.c_int64, _F, _V, _V, _V]),
+    "spx_overlap_accumulate": (C.c_int, [_V, _PL, _V, _V, _I, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V]),
 }
 
 _lib: Optional[C.CDLL] = None

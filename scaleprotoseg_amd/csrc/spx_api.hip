@@ -772,6 +772,66 @@ int spx_eval_topk(const float* logits, const int64_t* host_logit_strides, const 
                                            (unsigned long long*)seen, (hipStream_t)stream), who);
 }
 
+#define SPX_OVL_MAX_SLOTS 32
+#define SPX_OVL_MAX_OUT 32768
+#define SPX_OVL_MAX_ROWS 16384
+#define SPX_OVL_MAX_COLS 1638
+
+static int overlap_check(const char* who, const float* planes, const int64_t* st, int32_t N, int32_t C, int32_t h, int32_t w,
+                         int32_t H, int32_t W, const void* workspace) {
+    if (!planes || !st || !workspace) return fail("%s: NULL planes / strides / workspace", who);
+    if (N < 1 || C < 1 || h < 1 || w < 1 || H < 1 || W < 1) return fail("%s: empty input (N=%d C=%d h=%d w=%d H=%d W=%d)", who, N, C, h, w, H, W);
+    if (N > 65535 || C > SPX_EVAL_MAX_PROTOTYPES) return fail("%s: bad sizes (N=%d C=%d; N <= 65535, C <= %d)", who, N, C, SPX_EVAL_MAX_PROTOTYPES);
+    if ((long long)H * W >= (1LL << 31) || H > SPX_OVL_MAX_OUT || W > SPX_OVL_MAX_OUT)
+        return fail("%s: output %d x %d too large (H*W < 2^31, H and W <= %d)", who, H, W, SPX_OVL_MAX_OUT);
+    if (h > SPX_OVL_MAX_ROWS || w > SPX_OVL_MAX_COLS)
+        return fail("%s: latent grid %d x %d too large (h <= %d, w <= %d)", who, h, w, SPX_OVL_MAX_ROWS, SPX_OVL_MAX_COLS);
+    for (int i = 0; i < 4; ++i)
+        if (st[i] < 0) return fail("%s: negative stride", who);
+    if ((long long)(C - 1) * st[1] + (long long)(h - 1) * st[2] + (long long)(w - 1) * st[3] >= (1LL << 31))
+        return fail("%s: one image of planes spans more than 2^31 elements", who);
+    return 0;
+}
+
+size_t spx_overlap_workspace_bytes(int32_t N, int32_t C, int32_t K) {
+    if (N < 1 || N > 65535 || C < 1 || C > SPX_EVAL_MAX_PROTOTYPES || K < 1 || K > SPX_EVAL_MAX_CLASSES) {
+        fail("spx_overlap_workspace_bytes: bad sizes (N=%d C=%d K=%d; N <= 65535, C <= %d, K <= %d)", N, C, K, SPX_EVAL_MAX_PROTOTYPES,
+             SPX_EVAL_MAX_CLASSES);
+        return 0;
+    }
+    return spx_overlap_ws_bytes(N, C, K);
+}
+
+int spx_overlap_thresholds(const float* planes, const int64_t* host_strides, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
+                           int32_t W, int64_t k, float gamma, void* workspace, float* thresholds, void* stream) {
+    static const char* who = "spx_overlap_thresholds";
+    if (!thresholds) return fail("%s: NULL thresholds", who);
+    if (int e = overlap_check(who, planes, host_strides, N, C, h, w, H, W, workspace)) return e;
+    // 0 < q < 1: the lower order statistic is never the last one, the weight of the upper one is a proper fraction
+    const long long HW = (long long)H * W;
+    if (k < 0 || k > (HW > 1 ? HW - 2 : 0) || !(gamma >= 0.0f && gamma < 1.0f))
+        return fail("%s: rank %lld / weight %g outside a quantile 0 < q < 1 of %lld values", who, (long long)k, (double)gamma, HW);
+    return hip_status(spx_launch_overlap_thresholds(planes, (const long long*)host_strides, N, C, h, w, H, W, k, gamma, workspace,
+                                                    thresholds, (hipStream_t)stream), who);
+}
+
+int spx_overlap_accumulate(const float* planes, const int64_t* host_strides, const float* thresholds, const void* labels,
+                           int32_t label_bytes, const int32_t* slot_table, int32_t N, int32_t C, int32_t K, int32_t J, int32_t h,
+                           int32_t w, int32_t H, int32_t W, int64_t* inter, int64_t* area, int64_t* images, void* workspace,
+                           void* stream) {
+    static const char* who = "spx_overlap_accumulate";
+    if (!thresholds || !labels || !slot_table || !inter || !area || !images)
+        return fail("%s: NULL thresholds / labels / slot table / counters", who);
+    if (label_bytes != 1 && label_bytes != 4 && label_bytes != 8)
+        return fail("%s: label byte code %d (1 = uint8, 4 = int32, 8 = int64)", who, label_bytes);
+    if (K < 1 || K > SPX_EVAL_MAX_CLASSES || J < 1 || J > SPX_OVL_MAX_SLOTS)
+        return fail("%s: bad sizes (K=%d J=%d; K <= %d, J <= %d)", who, K, J, SPX_EVAL_MAX_CLASSES, SPX_OVL_MAX_SLOTS);
+    if (int e = overlap_check(who, planes, host_strides, N, C, h, w, H, W, workspace)) return e;
+    return hip_status(spx_launch_overlap_accumulate(planes, (const long long*)host_strides, thresholds, labels, label_bytes, slot_table,
+                                                    N, C, K, J, h, w, H, W, (unsigned long long*)inter, (unsigned long long*)area,
+                                                    (unsigned long long*)images, workspace, (hipStream_t)stream), who);
+}
+
 static int kld_check(const char* who, const float* vals, const int32_t* labels, int32_t B, int32_t J, int32_t HW, int32_t K,
                      const void* out, int pairs) {
     if (!vals || !labels || !out) return fail("%s: NULL buffer", who);

@@ -207,6 +207,14 @@ hipError_t spx_launch_kld_lse(const uint32_t* keys, const uint64_t* ssum_fx, int
                               double* scale_out, hipStream_t s);
 hipError_t spx_launch_kld_gram_loss(const int64_t* a_fx, const double* scale, const uint32_t* counts, const uint8_t* pair_ok, int nseg, int K,
                                     int J, float* A, float* Cf, double* part, float* loss, hipStream_t s);
+// activation-overlap metrics (spx_overlap.hip)
+size_t spx_overlap_ws_bytes(int N, int C, int K);
+hipError_t spx_launch_overlap_thresholds(const float* planes, const long long* st, int N, int C, int h, int w, int H, int W,
+                                         long long k, float gamma, void* workspace, float* thresholds, hipStream_t s);
+hipError_t spx_launch_overlap_accumulate(const float* planes, const long long* st, const float* thresholds, const void* labels,
+                                         int label_bytes, const int32_t* table, int N, int C, int K, int J, int h, int w, int H, int W,
+                                         unsigned long long* inter, unsigned long long* area, unsigned long long* images,
+                                         void* workspace, hipStream_t s);
 size_t spx_actloss_ws_bytes(int B, int K, int J);
 hipError_t spx_launch_actloss_max(const spx_actloss* p, void* workspace, hipStream_t s);
 hipError_t spx_launch_actloss_sums(const spx_actloss* p, void* workspace, hipStream_t s);

@@ -1,0 +1,393 @@
+// Activation-overlap metrics (segmentation/analysis/prototype_overlap.py:28-92, group_overlap.py:28-87): every activation
+// plane of a class is upsampled to the label size (OpenCV INTER_CUBIC), thresholded at its own q-quantile, and the
+// intersections of the binary masks of one class's planes are counted.  The upsampled [C, H, W] tensor (1.9 GB per Cityscapes
+// image) is never written: every pass recomputes a pixel's value from the latent plane with ovl_value() below, and because
+// that is ONE function compiled with -ffp-contract=off the value of a pixel is the same bits in every pass - the selection
+// that finds the threshold and the comparison that builds the mask agree on every pixel.
+//
+//   spx_overlap_thresholds   radix select of the order statistics v[k], v[k1] of each plane over the order-preserving uint32
+//                            key of the fp32 value: three histogram rounds of 11 / 11 / 10 key bits, a one-workgroup scan per
+//                            plane between them; T = numpy's _lerp(v[k], v[k1], gamma) in fp32.
+//   spx_overlap_accumulate   class presence from the labels, then per (image, present class, pixel tile): one ballot per
+//                            slot, popcount(b_j & b_j') per slot pair (j == j': the mask's area), 64-bit integer atomics.
+#include "spx_common.h"
+
+#define OVL_THREADS 256
+#define OVL_STAGE 8192            // floats of latent rows staged per band (32 KiB)
+#define OVL_BAND 256              // most output rows of one band (the y-tap table's size)
+#define OVL_BINS 2048             // bins of a histogram round (the last round uses 1024)
+#define OVL_MAX_J 32
+#define OVL_MAX_PAIRS (OVL_MAX_J * (OVL_MAX_J + 1) / 2)
+#define OVL_PAIR_REGS ((OVL_MAX_PAIRS + 63) / 64)
+#define OVL_CNT_ROWS 64           // output rows of a counting tile (64 columns wide): 16 per wave
+
+struct OvlPlanes {                // element strides of a 4-D fp32 tensor, in (n, channel, y, x) order
+    const float* p;
+    long long sn, sc, sy, sx;
+};
+
+// ---- the upsampled value ---------------------------------------------------------------------------------------------
+// Source coordinate of output index d for `in` source and `out` output samples: s = (d + 0.5) * in / out - 0.5, taken
+// EXACTLY as the fraction num / den with num = (2d + 1) * in - out, den = 2 * out: i = floor(s), t = s - i = r / den with one
+// rounding (fits int32: the entry points bound out <= 32768, in <= 16384).  Taps i - 1 .. i + 2, clamped to the grid.
+__device__ __forceinline__ void ovl_coord(int d, int in, int out, int& i, float& t) {
+    const int num = (2 * d + 1) * in - out, den = 2 * out;
+    int r;
+    if (num < 0) {                // only -out < num < 0: i = -1
+        i = -1;
+        r = num + den;
+    } else {
+        i = (int)((unsigned)num / (unsigned)den);
+        r = num - i * den;
+    }
+    t = (float)r / (float)den;
+}
+// Keys' cubic convolution weights at a = -0.75 (OpenCV's INTER_CUBIC, torch's bicubic) for the taps at distance
+// t + 1, t, 1 - t, 2 - t.
+__device__ __forceinline__ float ovl_cc1(float x) { return ((1.25f * x - 2.25f) * x) * x + 1.0f; }            // |x| <= 1
+__device__ __forceinline__ float ovl_cc2(float x) { return ((-0.75f * x + 3.75f) * x - 6.0f) * x + 3.0f; }    // 1 < |x| < 2
+__device__ __forceinline__ void ovl_weights(float t, float* wgt) {
+    wgt[0] = ovl_cc2(t + 1.0f);
+    wgt[1] = ovl_cc1(t);
+    wgt[2] = ovl_cc1(1.0f - t);
+    wgt[3] = ovl_cc2(2.0f - t);
+}
+__device__ __forceinline__ int ovl_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+// taps of one axis: element offsets (clamped index - origin) * stride and the four weights
+__device__ __forceinline__ void ovl_axis(int d, int in, int out, int origin, int stride, int* off, float* wgt) {
+    int i;
+    float t;
+    ovl_coord(d, in, out, i, t);
+    ovl_weights(t, wgt);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) off[a] = (ovl_clamp(i - 1 + a, in - 1) - origin) * stride;
+}
+// THE value of an upsampled pixel: rows first, left to right, then the four rows top to bottom.  p may point to LDS or to
+// memory; the arithmetic is the same sequence of fp32 operations either way.
+__device__ __forceinline__ float ovl_value(const float* p, const int* oy, const float* wy, const int* ox, const float* wx) {
+    float v = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const float* q = p + oy[a];
+        const float row = ((q[ox[0]] * wx[0] + q[ox[1]] * wx[1]) + q[ox[2]] * wx[2]) + q[ox[3]] * wx[3];
+        v = a == 0 ? row * wy[0] : v + row * wy[a];
+    }
+    return v;
+}
+
+// order-preserving key of an fp32 value (-0.0 sorts directly below +0.0, NaNs at the two ends) and its inverse
+__device__ __forceinline__ uint32_t ovl_key(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ovl_unkey(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// ---- selection -------------------------------------------------------------------------------------------------------
+// Workspace: state uint32 [N*C][4] = (prefix, rank) of the two order statistics; hist uint32 [N*C][2][OVL_BINS]; presence
+// int32 [N][K].  Nothing depends on H or W.
+static inline size_t ovl_state_bytes(long long planes) { return (size_t)planes * 16; }
+static inline size_t ovl_hist_bytes(long long planes) { return (size_t)planes * 2 * OVL_BINS * 4; }
+
+__global__ __launch_bounds__(OVL_THREADS) void spx_overlap_init_kernel(uint32_t* __restrict__ state, uint32_t* __restrict__ hist,
+                                                                       uint32_t k0, uint32_t k1) {
+    const size_t plane = blockIdx.x;
+    uint32_t* hq = hist + plane * 2 * OVL_BINS;
+    for (int i = threadIdx.x; i < 2 * OVL_BINS; i += OVL_THREADS) hq[i] = 0u;
+    if (threadIdx.x == 0) {
+        state[plane * 4 + 0] = 0u;
+        state[plane * 4 + 1] = k0;
+        state[plane * 4 + 2] = 0u;
+        state[plane * 4 + 3] = k1;
+    }
+}
+
+// one run of equal bins per thread: consecutive rows of a column mostly fall into one bin of the coarse rounds
+__device__ __forceinline__ void ovl_count(uint32_t* hist, int& cur, uint32_t& run, int bin) {
+    if (bin != cur) {
+        if (run) atomicAdd(&hist[cur], run);
+        cur = bin;
+        run = 0u;
+    }
+    ++run;
+}
+
+// Histogram round `round` (0, 1, 2) of the band of output rows blockIdx.x of plane (blockIdx.z, blockIdx.y).  The band's
+// latent rows plus the halo of the cubic taps are staged in LDS; wave v takes the band's rows v, v + 4, ..., lane l the
+// columns l, l + 64, ...
+__global__ __launch_bounds__(OVL_THREADS) void spx_overlap_hist_kernel(OvlPlanes a, int C, int h, int w, int H, int W, int band_rows,
+                                                                       int round, const uint32_t* __restrict__ state,
+                                                                       uint32_t* __restrict__ hist) {
+    __shared__ float s_stage[OVL_STAGE];
+    __shared__ uint32_t s_hist[2 * OVL_BINS];
+    __shared__ int s_oy[OVL_BAND * 4];
+    __shared__ float s_wy[OVL_BAND * 4];
+    const int tid = threadIdx.x, c = blockIdx.y, n = blockIdx.z;
+    const size_t plane = (size_t)n * C + c;
+    const int Y0 = blockIdx.x * band_rows, Y1 = min(H, Y0 + band_rows), rows = Y1 - Y0;
+    int i0, i1;
+    float t;
+    ovl_coord(Y0, h, H, i0, t);
+    ovl_coord(Y1 - 1, h, H, i1, t);
+    const int lo = ovl_clamp(i0 - 1, h - 1), hi = ovl_clamp(i1 + 2, h - 1);
+    const int nstage = (hi - lo + 1) * w;                       // <= OVL_STAGE: ovl_band_rows, checked again at the launch
+    for (int i = tid; i < 2 * OVL_BINS; i += OVL_THREADS) s_hist[i] = 0u;
+    for (int r = tid; r < rows; r += OVL_THREADS) ovl_axis(Y0 + r, h, H, lo, w, &s_oy[4 * r], &s_wy[4 * r]);
+    const float* src = a.p + (long long)n * a.sn + (long long)c * a.sc;
+    for (int i = tid; i < nstage; i += OVL_THREADS) {
+        const int y = i / w, x = i - y * w;
+        s_stage[i] = src[(long long)(lo + y) * a.sy + (long long)x * a.sx];
+    }
+    __syncthreads();
+    const uint32_t p0 = state[plane * 4 + 0], p1 = state[plane * 4 + 2];
+    const int wave = tid >> 6, lane = tid & 63;
+    int cur0 = 0, cur1 = 0;
+    uint32_t run0 = 0u, run1 = 0u;
+    for (int X = lane; X < W; X += 64) {
+        int ox[4];
+        float wx[4];
+        ovl_axis(X, w, W, 0, 1, ox, wx);
+        for (int r = wave; r < rows; r += 4) {
+            const uint32_t key = ovl_key(ovl_value(s_stage, &s_oy[4 * r], &s_wy[4 * r], ox, wx));
+            if (round == 0) {
+                ovl_count(s_hist, cur0, run0, (int)(key >> 21));
+            } else if (round == 1) {
+                if ((key >> 21) == p0) ovl_count(s_hist, cur0, run0, (int)((key >> 10) & 2047u));
+                if ((key >> 21) == p1) ovl_count(s_hist + OVL_BINS, cur1, run1, (int)((key >> 10) & 2047u));
+            } else {
+                if ((key >> 10) == p0) ovl_count(s_hist, cur0, run0, (int)(key & 1023u));
+                if ((key >> 10) == p1) ovl_count(s_hist + OVL_BINS, cur1, run1, (int)(key & 1023u));
+            }
+        }
+    }
+    if (run0) atomicAdd(&s_hist[cur0], run0);
+    if (run1) atomicAdd(&s_hist[OVL_BINS + cur1], run1);
+    __syncthreads();
+    uint32_t* hq = hist + plane * 2 * OVL_BINS;
+    for (int i = tid; i < 2 * OVL_BINS; i += OVL_THREADS) {
+        const uint32_t v = s_hist[i];
+        if (v) atomicAdd(&hq[i], v);
+    }
+}
+
+// Between the rounds, one workgroup per plane: for each of the two ranks the bin that holds it (the first bin whose running
+// count exceeds the rank), the rank inside that bin, the key prefix extended by the bin; the histograms zeroed for the next
+// round.  After the last round the keys are complete: T = numpy's _lerp of the two values, in fp32.
+__global__ __launch_bounds__(OVL_THREADS) void spx_overlap_scan_kernel(int round, uint32_t* __restrict__ state, uint32_t* __restrict__ hist,
+                                                                       float gamma, float* __restrict__ thresholds) {
+    __shared__ uint32_t s_sum[OVL_THREADS];
+    const int tid = threadIdx.x;
+    const size_t plane = blockIdx.x;
+    const int bits = round == 2 ? 10 : 11, per = (1 << bits) / OVL_THREADS;     // 8 or 4 consecutive bins per thread
+    uint32_t* hq = hist + plane * 2 * OVL_BINS;
+    for (int r = 0; r < 2; ++r) {
+        const uint32_t* hr = hq + (round == 0 ? 0 : r * OVL_BINS);              // round 0: one histogram serves both ranks
+        uint32_t mine = 0u;
+        for (int i = 0; i < per; ++i) mine += hr[tid * per + i];
+        s_sum[tid] = mine;
+        __syncthreads();
+        for (int off = 1; off < OVL_THREADS; off <<= 1) {
+            const uint32_t add = tid >= off ? s_sum[tid - off] : 0u;
+            __syncthreads();
+            s_sum[tid] += add;
+            __syncthreads();
+        }
+        const uint32_t rank = state[plane * 4 + 2 * r + 1];
+        uint32_t below = s_sum[tid] - mine;
+        __syncthreads();                                                         // every thread has read its rank and sums
+        if (rank >= below && rank < below + mine) {                              // exactly one thread
+            int b = tid * per;
+            for (;; ++b) {
+                const uint32_t cnt = hr[b];
+                if (rank < below + cnt) break;
+                below += cnt;
+            }
+            state[plane * 4 + 2 * r] = (state[plane * 4 + 2 * r] << bits) | (uint32_t)b;
+            state[plane * 4 + 2 * r + 1] = rank - below;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < 2 * OVL_BINS; i += OVL_THREADS) hq[i] = 0u;
+    if (round == 2 && tid == 0) {
+        const float lo = ovl_unkey(state[plane * 4 + 0]), hi = ovl_unkey(state[plane * 4 + 2]);
+        const float d = hi - lo;
+        thresholds[plane] = gamma >= 0.5f ? hi - d * (1.0f - gamma) : lo + d * gamma;
+    }
+}
+
+// rows of a band so that its latent footprint (rows i_first - 1 .. i_last + 2) fits the stage
+static int ovl_band_rows(int h, int w, int H) {
+    const int cap = OVL_STAGE / w;                               // >= 5: the entry point bounds w
+    if (cap >= h) return H < OVL_BAND ? H : OVL_BAND;
+    // (r - 1) * h / H <= cap - 5, so first and last row of a band are at most cap - 4 latent rows apart (the floors of two
+    // coordinates x apart differ by at most ceil(x)) and with the taps -1 .. +2 at most cap rows are staged
+    const long long r = 1 + (long long)(cap - 5) * H / h;
+    return (int)(r < OVL_BAND ? r : OVL_BAND);
+}
+// the most latent rows any band of `band` output rows stages, by the kernel's own coordinate rule (host copy of ovl_coord's
+// integer part): the launch refuses a band that would not fit instead of trusting the bound above
+static int ovl_max_staged_rows(int h, int H, int band) {
+    int most = 0;
+    for (int Y0 = 0; Y0 < H; Y0 += band) {
+        const int Y1 = Y0 + band < H ? Y0 + band : H;
+        const long long n0 = (2LL * Y0 + 1) * h - H, n1 = (2LL * (Y1 - 1) + 1) * h - H, den = 2LL * H;
+        const int i0 = n0 < 0 ? -1 : (int)(n0 / den), i1 = n1 < 0 ? -1 : (int)(n1 / den);
+        const int lo = i0 - 1 < 0 ? 0 : (i0 - 1 > h - 1 ? h - 1 : i0 - 1), hi = i1 + 2 > h - 1 ? h - 1 : (i1 + 2 < 0 ? 0 : i1 + 2);
+        if (hi - lo + 1 > most) most = hi - lo + 1;
+    }
+    return most;
+}
+
+static inline OvlPlanes ovl_planes(const float* p, const long long* st) {
+    OvlPlanes m;
+    m.p = p;
+    m.sn = st[0];
+    m.sc = st[1];
+    m.sy = st[2];
+    m.sx = st[3];
+    return m;
+}
+
+size_t spx_overlap_ws_bytes(int N, int C, int K) {
+    const long long planes = (long long)N * C;
+    return ovl_state_bytes(planes) + ovl_hist_bytes(planes) + (((size_t)N * K * 4 + 255) & ~(size_t)255);
+}
+
+hipError_t spx_launch_overlap_thresholds(const float* planes, const long long* st, int N, int C, int h, int w, int H, int W,
+                                         long long k, float gamma, void* workspace, float* thresholds, hipStream_t s) {
+    const long long np = (long long)N * C, HW = (long long)H * W;
+    uint32_t* state = (uint32_t*)workspace;
+    uint32_t* hist = (uint32_t*)((char*)workspace + ovl_state_bytes(np));
+    const long long k1 = k + 1 < HW ? k + 1 : HW - 1;
+    const int band = ovl_band_rows(h, w, H);
+    if (band < 1 || (long long)ovl_max_staged_rows(h, H, band) * w > OVL_STAGE) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spx_overlap_init_kernel, dim3((unsigned)np), dim3(OVL_THREADS), 0, s, state, hist, (uint32_t)k, (uint32_t)k1);
+    const dim3 grid((unsigned)((H + band - 1) / band), (unsigned)C, (unsigned)N);
+    const OvlPlanes a = ovl_planes(planes, st);
+    for (int round = 0; round < 3; ++round) {
+        hipLaunchKernelGGL(spx_overlap_hist_kernel, grid, dim3(OVL_THREADS), 0, s, a, C, h, w, H, W, band, round, state, hist);
+        hipLaunchKernelGGL(spx_overlap_scan_kernel, dim3((unsigned)np), dim3(OVL_THREADS), 0, s, round, state, hist, gamma, thresholds);
+    }
+    return hipGetLastError();
+}
+
+// ---- counting --------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ long long ovl_label(const void* labels, int label_bytes, size_t o) {
+    if (label_bytes == 1) return (long long)((const uint8_t*)labels)[o];
+    if (label_bytes == 4) return (long long)((const int32_t*)labels)[o];
+    return ((const long long*)labels)[o];
+}
+
+// presence[n][k] = 1 where class k (label k + 1) occurs in image n; presence is zeroed before the launch
+__global__ __launch_bounds__(OVL_THREADS) void spx_overlap_presence_kernel(const void* __restrict__ labels, int label_bytes, int K,
+                                                                           long long HW, int32_t* __restrict__ presence) {
+    __shared__ int s_seen[1024];
+    const int tid = threadIdx.x, n = blockIdx.y;
+    for (int i = tid; i < K; i += OVL_THREADS) s_seen[i] = 0;
+    __syncthreads();
+    for (long long i = (long long)blockIdx.x * OVL_THREADS + tid; i < HW; i += (long long)gridDim.x * OVL_THREADS) {
+        const long long ann = ovl_label(labels, label_bytes, (size_t)n * HW + i);
+        if (ann >= 1 && ann <= K) s_seen[ann - 1] = 1;
+    }
+    __syncthreads();
+    for (int i = tid; i < K; i += OVL_THREADS)
+        if (s_seen[i]) presence[(size_t)n * K + i] = 1;
+}
+
+// One tile of 64 columns x OVL_CNT_ROWS rows of image blockIdx.z for class blockIdx.y; a workgroup of an absent class leaves
+// at once.  Lane l owns column l of the tile, wave v the rows v, v + 4, ...; per row and slot one ballot of (u > T), kept in
+// LDS (every lane writes the same word); then lane l adds popcount(b_j & b_j') of the pairs l, l + 64, ... (j <= j' in
+// row-major order; j == j' is the area) to its registers.  Rows without any pixel above a threshold (most of them at
+// q = 0.95) skip the pairs.
+__global__ __launch_bounds__(OVL_THREADS) void spx_overlap_count_kernel(
+    OvlPlanes a, const float* __restrict__ thresholds, const int32_t* __restrict__ table, const int32_t* __restrict__ presence, int C,
+    int K, int J, int h, int w, int H, int W, int tiles_x, unsigned long long* __restrict__ inter, unsigned long long* __restrict__ area,
+    unsigned long long* __restrict__ images) {
+    __shared__ unsigned long long s_b[4][OVL_MAX_J];
+    __shared__ unsigned short s_pair[OVL_MAX_PAIRS];
+    __shared__ int s_ch[OVL_MAX_J];
+    __shared__ float s_T[OVL_MAX_J];
+    const int tid = threadIdx.x, k = blockIdx.y, n = blockIdx.z;
+    if (!presence[(size_t)n * K + k]) return;                    // workgroup-uniform
+    if (blockIdx.x == 0 && tid == 0) atomicAdd(&images[k], 1ull);
+    const int npairs = J * (J + 1) / 2;
+    for (int p = tid; p < npairs; p += OVL_THREADS) {
+        int j = 0, rem = p;
+        while (rem >= J - j) {
+            rem -= J - j;
+            ++j;
+        }
+        s_pair[p] = (unsigned short)(j | ((j + rem) << 8));
+    }
+    if (tid < J) {
+        const int ch = table[(size_t)k * J + tid];
+        const bool ok = ch >= 0 && ch < C;                       // anything else: the class has no such slot
+        s_ch[tid] = ok ? ch : -1;
+        s_T[tid] = ok ? thresholds[(size_t)n * C + ch] : 0.0f;
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+    const int X = tx * 64 + lane;
+    const bool col_ok = X < W;
+    int ox[4], oy[4];
+    float wx[4], wy[4];
+    ovl_axis(col_ok ? X : W - 1, w, W, 0, (int)a.sx, ox, wx);
+    const float* img = a.p + (long long)n * a.sn;
+    uint32_t acc[OVL_PAIR_REGS];
+#pragma unroll
+    for (int i = 0; i < OVL_PAIR_REGS; ++i) acc[i] = 0u;
+    const int Yend = min(H, (ty + 1) * OVL_CNT_ROWS);
+    for (int Y = ty * OVL_CNT_ROWS + wave; Y < Yend; Y += 4) {
+        ovl_axis(Y, h, H, 0, (int)a.sy, oy, wy);
+        unsigned long long any = 0ull;
+        for (int j = 0; j < J; ++j) {
+            const int ch = s_ch[j];
+            unsigned long long b = 0ull;
+            if (ch >= 0) {                                       // wave-uniform
+                const float v = ovl_value(img + (long long)ch * a.sc, oy, wy, ox, wx);
+                b = __ballot(col_ok && v > s_T[j]);
+            }
+            s_b[wave][j] = b;
+            any |= b;
+        }
+        if (any) {
+#pragma unroll
+            for (int i = 0; i < OVL_PAIR_REGS; ++i) {
+                const int p = lane + 64 * i;
+                if (p < npairs) {
+                    const unsigned pr = s_pair[p];
+                    acc[i] += (uint32_t)__popcll(s_b[wave][pr & 255u] & s_b[wave][pr >> 8]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < OVL_PAIR_REGS; ++i) {
+        const int p = lane + 64 * i;
+        if (p < npairs && acc[i]) {
+            const unsigned pr = s_pair[p];
+            const int j = (int)(pr & 255u), j2 = (int)(pr >> 8);
+            if (j == j2) atomicAdd(&area[(size_t)k * J + j], (unsigned long long)acc[i]);
+            else atomicAdd(&inter[((size_t)k * J + j) * J + j2], (unsigned long long)acc[i]);
+        }
+    }
+}
+
+hipError_t spx_launch_overlap_accumulate(const float* planes, const long long* st, const float* thresholds, const void* labels,
+                                         int label_bytes, const int32_t* table, int N, int C, int K, int J, int h, int w, int H, int W,
+                                         unsigned long long* inter, unsigned long long* area, unsigned long long* images,
+                                         void* workspace, hipStream_t s) {
+    const long long np = (long long)N * C, HW = (long long)H * W;
+    int32_t* presence = (int32_t*)((char*)workspace + ovl_state_bytes(np) + ovl_hist_bytes(np));
+    hipError_t e = hipMemsetAsync(presence, 0, (size_t)N * K * 4, s);
+    if (e != hipSuccess) return e;
+    const long long chunks = (HW + OVL_THREADS * 16 - 1) / (OVL_THREADS * 16);
+    hipLaunchKernelGGL(spx_overlap_presence_kernel, dim3((unsigned)(chunks < 1024 ? chunks : 1024), (unsigned)N), dim3(OVL_THREADS), 0, s,
+                       labels, label_bytes, K, HW, presence);
+    const int tiles_x = (W + 63) / 64, tiles_y = (H + OVL_CNT_ROWS - 1) / OVL_CNT_ROWS;
+    hipLaunchKernelGGL(spx_overlap_count_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)K, (unsigned)N), dim3(OVL_THREADS), 0, s,
+                       ovl_planes(planes, st), thresholds, table, presence, C, K, J, h, w, H, W, tiles_x, inter, area, images);
+    return hipGetLastError();
+}
