@@ -218,15 +218,19 @@ def check(status: int) -> None:
         raise SpxError(load().spx_last_error().decode("utf-8", "replace"))
 
 
+def require_gpu(t, what: str = "input") -> None:
+    """Raise unless ``t`` (a tensor or a ``torch.device``) is on the GPU: the package's one statement of 'no CPU fallback'."""
+    if not (t.type == "cuda" if isinstance(t, torch.device) else t.is_cuda):
+        dev = t if isinstance(t, torch.device) else t.device
+        raise SpxError(f"{what} is on {dev}: scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+
+
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     """Raw device pointer of a dense GPU tensor (None -> NULL)."""
     if t is None:
         return None
-    if not t.is_cuda:
-        raise SpxError(
-            "scaleprotoseg_amd operators run on an AMD GPU only (tensor is on "
-            f"{t.device}); there is no CPU fallback"
-        )
+    if not t.is_cuda:            # (tested here first: ptr() runs a hundred times per step, the call is for the message)
+        require_gpu(t)
     if not t.is_contiguous():
         raise SpxError("tensor must be contiguous")
     return t.data_ptr()

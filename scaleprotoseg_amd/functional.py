@@ -60,10 +60,15 @@ class BankLayout:
     channels_per_scale: int
     scale_ranges: Tuple[Tuple[int, int], ...]
 
+    @property
+    def key(self) -> tuple:
+        """The layout by value (P, K, S, Cs, scale ranges): what the plan and the packed operands depend on."""
+        return (self.num_prototypes, self.num_classes, self.num_scales, self.channels_per_scale,
+                tuple(tuple(int(v) for v in r) for r in self.scale_ranges))
+
     def plan(self) -> SpxPlan:
         """The kernels' panel plan (spx_make_plan); cached per layout value - it is pure host work."""
-        key = (self.num_prototypes, self.num_classes, self.num_scales, self.channels_per_scale,
-               tuple(tuple(int(v) for v in r) for r in self.scale_ranges))
+        key = self.key
         plan = _PLAN_CACHE.get(key)
         if plan is None:
             lo = [r[0] for r in self.scale_ranges]
@@ -99,8 +104,7 @@ class _CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels0):
         lib = _lib.load()
-        if not logits.is_cuda:
-            raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+        _lib.require_gpu(logits)
         K = int(logits.shape[-1])
         lg = logits.detach().reshape(-1, K).contiguous().float()
         M = int(lg.shape[0])
@@ -204,8 +208,8 @@ def _rows_gemm(A: torch.Tensor, a_strides, B: torch.Tensor, b_strides, M: int, N
                E: Optional[torch.Tensor] = None) -> torch.Tensor:
     """C[i][j] = sum_k A(i, k) B(j, k) on row-major fp32 device tensors through the fp32 MFMA kernels of csrc/spx_gemm.hip
     (include/spx_hip.h: spx_rows_gemm); ``*_strides`` = (row stride, k stride) in elements."""
-    if not (A.is_cuda and B.is_cuda):
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(A)
+    _lib.require_gpu(B)
     if A.dtype != torch.float32 or B.dtype != torch.float32 or not A.is_contiguous() or not B.is_contiguous():
         raise SpxError("spx_rows_gemm takes contiguous float32 operands")
     lib = _lib.load()
@@ -223,8 +227,7 @@ def _pixel_outer(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     19 x 57) in the fp32 FMA kernel spx_pixel_outer; larger ones (the heads wider than the fused kernels: 450 x 1800) in the
     MFMA product kernel with the pixels as the contraction index (split over workgroups, slabs summed in a fixed order)."""
     M, n1, n2 = a.shape[0], a.shape[1], b.shape[1]
-    if not a.is_cuda:
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(a)
     a, b = a.contiguous().float(), b.contiguous().float()
     if n1 * n2 <= 8192:
         lib = _lib.load()
@@ -380,26 +383,24 @@ class _GroupDenseFn(torch.autograd.Function):
 
 def group_dense(tables: "GroupTables", weights) -> torch.Tensor:
     weights = list(weights)
-    if not weights or not weights[0].is_cuda:
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    if not weights:
+        raise SpxError("group_dense: the weights do not match the index tables")
+    _lib.require_gpu(weights[0])
     return _GroupDenseFn.apply(tables, *weights)
 
 
 def group_exp(units: torch.Tensor) -> torch.Tensor:
-    if not units.is_cuda:
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(units)
     return _ExpFn.apply(units)
 
 
 def wide_group_tail(units: torch.Tensor, wg: torch.Tensor) -> torch.Tensor:
-    if not units.is_cuda:
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(units)
     return _WideGroupTailFn.apply(units, wg)
 
 
 def wide_linear(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    if not a.is_cuda:
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(a)
     return _WideLinearFn.apply(a, w)
 
 
@@ -527,9 +528,7 @@ class _ProtoHeadFn(torch.autograd.Function):
                 raise SpxError("the fused group tail needs the dense head and no class gather")
             if tail2d.dim() != 2 or tail2d.shape[1] != K or tail2d.shape[0] > 32:
                 raise SpxError(f"group tail must be [K2 <= 32, {K}], got {tuple(tail2d.shape)}")
-        plan_key = (layout.num_prototypes, layout.num_classes, layout.num_scales, layout.channels_per_scale,
-                    tuple(tuple(int(v) for v in r_) for r_ in layout.scale_ranges))
-        packs = _cached_packs(plan_key, plan, bank, head, tail, bank2d, head2d, tail2d, need_bwd)
+        packs = _cached_packs(layout.key, plan, bank, head, tail, bank2d, head2d, tail2d, need_bwd)
         f32 = dict(dtype=torch.float32, device=x.device)
         act = torch.empty((B * HW, P), **f32) if want_act else None
         logits = torch.empty((B * HW, K), **f32) if head is not None else None
@@ -788,8 +787,7 @@ def proto_head_forward(
     (the only entries the reference's KLDLoss reads, segmentation/model/loss.py:89-107)."""
     if activation not in ACT_FN:
         raise SpxError(f"activation {activation!r} has no fused kernel (use 'log' or 'linear')")
-    if not x.is_cuda:
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(x)
     logits, dist, act, gact, ce_loss, ce_pred = _ProtoHeadFn.apply(
         x, bank, head, layout, want_distances or class_gather is not None, want_activations, epsilon, activation,
         class_gather, group_tail, ce_labels,
@@ -866,8 +864,7 @@ def push_min_from_features(
     ``labels`` [B, H, W] in the push's convention (``void_class`` as in ``push_masked_argmin``); ``class_identity`` must be
     one-hot per row (``identity_is_one_hot``); ``keys``: a cached ``class_gather_table(layout, class_identity, device)[0]``."""
     lib = _lib.load()
-    if not conv_features.is_cuda:
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(conv_features)
     B, HW = _check_x(conv_features, layout)
     H, W = conv_features.shape[2], conv_features.shape[3]
     if tuple(labels.shape) != (B, H, W):
@@ -882,9 +879,7 @@ def push_min_from_features(
     lab = labels.to(device=dev, dtype=torch.int32).reshape(B, HW).contiguous()
     bank2d = bank.detach().reshape(P, layout.channels_per_scale).contiguous().float()
     plan = layout.plan()
-    plan_key = (layout.num_prototypes, layout.num_classes, layout.num_scales, layout.channels_per_scale,
-                tuple(tuple(int(v) for v in r_) for r_ in layout.scale_ranges))
-    packs = _cached_packs(plan_key, plan, bank, None, None, bank2d, None, None, False)
+    packs = _cached_packs(layout.key, plan, bank, None, None, bank2d, None, None, False)
     idx = torch.empty((B, P), dtype=torch.int64, device=dev)
     val = torch.empty((B, P), dtype=torch.float32, device=dev)
     scratch = torch.empty((B * P,), dtype=torch.int64, device=dev)
@@ -909,8 +904,7 @@ def prune_nearest_from_map(distances: torch.Tensor, labels: torch.Tensor, *, voi
     lib = _lib.load()
     if distances.dim() != 4:
         raise SpxError("distances must be [B, P, H, W]")
-    if not distances.is_cuda:
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(distances)
     B, P, H, W = distances.shape
     d = distances.detach().contiguous().float()
     lab = _prune_labels(labels, B, H, W, d.device)
@@ -934,8 +928,7 @@ def prune_nearest_from_features(
     [B, P, H, W] map is never written.  Bit-identical to ``prune_nearest_from_map`` on the map ``proto_head_forward``
     writes."""
     lib = _lib.load()
-    if not conv_features.is_cuda:
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(conv_features)
     B, HW = _check_x(conv_features, layout)
     H, W = conv_features.shape[2], conv_features.shape[3]
     x = conv_features.detach().contiguous()
@@ -944,9 +937,7 @@ def prune_nearest_from_features(
     P = layout.num_prototypes
     bank2d = bank.detach().reshape(P, layout.channels_per_scale).contiguous().float()
     plan = layout.plan()
-    plan_key = (layout.num_prototypes, layout.num_classes, layout.num_scales, layout.channels_per_scale,
-                tuple(tuple(int(v) for v in r_) for r_ in layout.scale_ranges))
-    packs = _cached_packs(plan_key, plan, bank, None, None, bank2d, None, None, False)
+    packs = _cached_packs(layout.key, plan, bank, None, None, bank2d, None, None, False)
     nrows = plan.npanels * plan.npb * 32
     rows = _prune_rows_cache.get((nrows, str(dev)))
     if rows is None:                     # the kernel reads a row table of the plan; the prune mode masks nothing with it
@@ -973,8 +964,8 @@ def prune_footprint(labels: torch.Tensor, keys: torch.Tensor, grid: Tuple[int, i
     lib = _lib.load()
     if labels.dim() != 3:
         raise SpxError("labels must be [B, Hf, Wf]")
-    if not (labels.is_cuda and keys.is_cuda):
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(labels)
+    _lib.require_gpu(keys)
     B, Hf, Wf = labels.shape
     H, W = int(grid[0]), int(grid[1])
     if keys.dim() != 2 or keys.shape[0] != B or keys.dtype != torch.int64:

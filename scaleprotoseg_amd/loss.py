@@ -18,7 +18,10 @@ from typing import Dict, Optional, Tuple, Union
 import torch
 from torch import nn
 
+from . import _lib
+from ._cache import cached
 from ._lib import SpxError
+from .functional import cross_entropy_from_logits
 
 
 @dataclass
@@ -102,25 +105,22 @@ class PixelWiseCrossEntropyLoss(nn.Module):
         self.ignore_index = ignore_index
 
     def forward(self, predicted_logits: torch.Tensor, target_labels: torch.Tensor):
+        _lib.require_gpu(predicted_logits, "cross entropy: logits")
         fused = getattr(predicted_logits, "spx_ce", None)
         K = predicted_logits.size(-1)
-        if predicted_logits.is_cuda:
-            from .functional import cross_entropy_from_logits
-
-            ignores_a_class = self.ignore_index is not None and 0 <= self.ignore_index < K
-            stale = fused is not None and (fused.target is not target_labels or fused.target_version != target_labels._version)
-            if fused is not None and not stale and not ignores_a_class and not self.return_correct:
-                return fused.loss                       # the epilogue's value: not one more launch here
-            labels0 = target_labels.reshape(-1).to(predicted_logits.device) - 1                  # loss.py:32
-            if fused is None or stale or ignores_a_class:
-                lab = labels0 if not ignores_a_class else torch.where(labels0 == self.ignore_index, torch.full_like(labels0, -1), labels0)
-                fused = cross_entropy_from_logits(predicted_logits, lab)
-            if not self.return_correct:
-                return fused.loss
-            correct = fused.pred.reshape(-1).to(labels0.dtype) == labels0
-            mask = (labels0 != self.ignore_index).nonzero().squeeze()                             # loss.py:43-46
-            return fused.loss, correct[mask]
-        raise SpxError(f"cross entropy: logits on {predicted_logits.device}; the loss runs on the GPU only (no CPU fallback)")
+        ignores_a_class = self.ignore_index is not None and 0 <= self.ignore_index < K
+        stale = fused is not None and (fused.target is not target_labels or fused.target_version != target_labels._version)
+        if fused is not None and not stale and not ignores_a_class and not self.return_correct:
+            return fused.loss                       # the epilogue's value: not one more launch here
+        labels0 = target_labels.reshape(-1).to(predicted_logits.device) - 1                  # loss.py:32
+        if fused is None or stale or ignores_a_class:
+            lab = labels0 if not ignores_a_class else torch.where(labels0 == self.ignore_index, torch.full_like(labels0, -1), labels0)
+            fused = cross_entropy_from_logits(predicted_logits, lab)
+        if not self.return_correct:
+            return fused.loss
+        correct = fused.pred.reshape(-1).to(labels0.dtype) == labels0
+        mask = (labels0 != self.ignore_index).nonzero().squeeze()                             # loss.py:43-46
+        return fused.loss, correct[mask]
 
 
 def _kld_kernels_usable(vals: torch.Tensor, K: int, J: int) -> bool:
@@ -135,8 +135,6 @@ def _kld_segment_passes(lib, v, lab, K, Wk, s):
     scale double [1]).  One zero-filled workspace holds the integer tables: [a_fx | ssum_fx | scale | keys | counts | range keys];
     the fixed-point scale of the pair sums is derived on the device (segment-lse kernel) from the value range pass 0 collects:
     |p_j (l_k - l_j)| is bounded by twice the range, and HW terms must stay inside int64 - no host sync, no torch glue."""
-    from . import _lib
-
     B, J, HW = v.shape
     dev = v.device
     n_a, n_s = B * K * J * J, B * K * J
@@ -160,8 +158,6 @@ class _KLDFusedLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vals, labels, K, W, pair_ok):
-        from . import _lib
-
         lib = _lib.load()
         B, J, HW = vals.shape
         v = vals.detach().contiguous()
@@ -181,8 +177,6 @@ class _KLDFusedLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
-
         lib = _lib.load()
         v, lab, lse, A, cf, loss = ctx.saved_tensors
         B, J, HW = v.shape
@@ -197,8 +191,6 @@ def segment_pair_sums(planes: torch.Tensor, labels0: torch.Tensor, K: int, W: in
     """A [B, K, J, J] = sum over the segment's pixels of p_j (l_k - l_j) (= -KL(j || k); diagonal 0) of class-gathered planes
     [B, J, H*W] through the three reduction passes of csrc/spx_kld.hip - what ``KLDLoss`` builds its value from (no autograd;
     diagnostics and tests).  ``W``: row length of the pixel grid (0 = unknown: linear walk)."""
-    from . import _lib
-
     lib = _lib.load()
     v = planes.detach().contiguous()
     B, J, HW = v.shape
@@ -210,7 +202,14 @@ def segment_pair_sums(planes: torch.Tensor, labels0: torch.Tensor, K: int, W: in
     return (a_fx.to(torch.float64) / scale).float()
 
 
-class KLDLoss(nn.Module):
+class _SlotTable:
+    def _slot_table(self) -> torch.Tensor:
+        """class_slot_table of the loss's identity, built once per identity object and in-place version."""
+        ident = self.prototype_class_identity
+        return cached(self, "_slot_table_cache", (ident,), (), lambda: class_slot_table(ident))
+
+
+class KLDLoss(_SlotTable, nn.Module):
     """Drop-in for segmentation/model/loss.py:51-146: same constructor, same ``forward(prototype_distances,
     target_labels)`` (labels 0 = void, 1..K = class); ``prototype_distances`` may be the [B, P, H, W] map or a
     ``ClassDistances``.  One pass of segment reductions instead of the reference's (image, class, scale, pair)
@@ -222,37 +221,17 @@ class KLDLoss(nn.Module):
         self.num_scales = num_scales
         self.scale_num_prototypes = scale_num_prototypes
 
-    def _slot_table(self) -> torch.Tensor:
-        """class_slot_table of the loss's identity, built once per identity OBJECT and in-place version (a strong
-        reference is kept, so neither an id nor a device address can be recycled under the cache)."""
-        ident = self.prototype_class_identity
-        c = getattr(self, "_slot_table_cache", None)
-        if c is None or c[0] is not ident or c[1] != ident._version:
-            c = (ident, ident._version, class_slot_table(ident))
-            self._slot_table_cache = c
-        return c[2]
-
     def _pair_mask(self, table: torch.Tensor) -> torch.Tensor:
-        """[K, J, J] bool: slots j < k of class c are prototypes of the same scale (loss.py:99-104, :118-121).
-        Cached per (table object + its in-place version, scale table): it is host-side work with a device read-back,
-        not something to redo per step.  The cache holds the table itself, so the key cannot alias a recycled tensor."""
+        """[K, J, J] bool: slots j < k of class c are prototypes of the same scale (loss.py:99-104, :118-121); host-side work
+        with a device read-back, not something to redo per step."""
         scales = tuple(sorted((int(s), tuple(r)) for s, r in self.scale_num_prototypes.items()))
-        cached = getattr(self, "_pair_mask_cache", None)
-        if cached is not None and cached[0] is table and cached[1] == (table._version, scales):
-            return cached[2]
-        mask = self._pair_mask_build(table).to(table.device)
-        self._pair_mask_cache = (table, (table._version, scales), mask)
-        return mask
+        return cached(self, "_pair_mask_cache", (table,), (scales,), lambda: self._pair_mask_build(table).to(table.device))
 
     def _table_on(self, table: torch.Tensor, dev) -> torch.Tensor:
         """``table`` on ``dev`` (the same object every step, so the pair-mask cache keyed on it holds)."""
         if table.device == dev:
             return table
-        c = getattr(self, "_table_dev_cache", None)
-        if c is None or c[0] is not table or c[1] != (table._version, str(dev)):
-            c = (table, (table._version, str(dev)), table.to(dev))
-            self._table_dev_cache = c
-        return c[2]
+        return cached(self, "_table_dev_cache", (table,), (str(dev),), lambda: table.to(dev))
 
     def _pair_mask_build(self, table: torch.Tensor) -> torch.Tensor:
         K, J = table.shape
@@ -306,11 +285,7 @@ class KLDLoss(nn.Module):
     def _pair_mask_u8(self, table: torch.Tensor, dev) -> torch.Tensor:
         """The [K, J, J] pair mask as uint8 on ``dev`` (cached with the mask it is made from)."""
         m = self._pair_mask(table)
-        c = getattr(self, "_pair_u8_cache", None)
-        if c is None or c[0] is not m or c[1].device != torch.device(dev):
-            c = (m, m.to(device=dev, dtype=torch.uint8).contiguous())
-            self._pair_u8_cache = c
-        return c[1]
+        return cached(self, "_pair_u8_cache", (m,), (torch.device(dev),), lambda: m.to(device=dev, dtype=torch.uint8).contiguous())
 
 
 class KLDLossGroup(KLDLoss):
@@ -319,35 +294,32 @@ class KLDLossGroup(KLDLoss):
     pair of a class is compared, loss.py:527-536), so the segment kernels are shared; ``list_group_activation`` may
     also be the concatenated [M, n_projections * num_groups] tensor the grouping head produces."""
 
+    scale_num_prototypes: Dict[int, Tuple[int, int]] = {}      # no scales here: every group pair of a class is compared
+
     def __init__(self, prototype_class_identity: torch.Tensor, group_class_identity: torch.Tensor, num_groups: int) -> None:
         nn.Module.__init__(self)
         self.prototype_class_identity = prototype_class_identity
         self.group_class_identity = group_class_identity
         self.num_groups = num_groups
-        self._tables = None
 
     def _class_tables(self):
-        """(projection of class c or -1 [K], stand-in slot table [K, G]: slot ids where the class has a projection)."""
-        if self._tables is None:
-            ident, gci, G = self.prototype_class_identity, self.group_class_identity, self.num_groups
-            K = ident.shape[1]
-            has = ident.sum(dim=0) > 0                                              # loss.py:504
-            proj = torch.where(has, gci.argmax(dim=0) // G, torch.full((K,), -1, dtype=torch.long)).cpu()   # :507
-            table = torch.where(has.cpu().unsqueeze(1), torch.arange(G).unsqueeze(0).expand(K, G), torch.full((K, G), -1, dtype=torch.long))
-            self._tables = (proj, table.contiguous())
-        return self._tables
+        """(projection of class c or -1 [K], stand-in slot table [K, G]: slot ids where the class has a projection), rebuilt when
+        either identity is edited in place or re-assigned (finetune_wandb_group.py:77-78)."""
+        ident, gci, G = self.prototype_class_identity, self.group_class_identity, self.num_groups
+        return cached(self, "_class_tables_cache", (ident, gci), (G,), lambda: self._class_tables_build(ident, gci, G))
+
+    @staticmethod
+    def _class_tables_build(ident, gci, G):
+        K = ident.shape[1]
+        has = ident.sum(dim=0) > 0                                              # loss.py:504
+        proj = torch.where(has, gci.argmax(dim=0) // G, torch.full((K,), -1, dtype=torch.long)).cpu()   # :507
+        table = torch.where(has.cpu().unsqueeze(1), torch.arange(G).unsqueeze(0).expand(K, G), torch.full((K, G), -1, dtype=torch.long))
+        return proj, table.contiguous()
 
     def _pair_mask_build(self, table: torch.Tensor) -> torch.Tensor:
         K, J = table.shape
         upper = torch.triu(torch.ones(J, J, dtype=torch.bool), diagonal=1)
         return upper.unsqueeze(0) & (table.cpu()[:, :1] >= 0).unsqueeze(2)
-
-    def _pair_mask(self, table: torch.Tensor) -> torch.Tensor:
-        cached = getattr(self, "_pair_mask_cache", None)
-        if cached is None or cached[0] is not table or cached[1] != table._version:
-            cached = (table, table._version, self._pair_mask_build(table).to(table.device))
-            self._pair_mask_cache = cached
-        return cached[2]
 
     def _gather_groups(self, list_group_activation, target_labels: torch.Tensor):
         """(vals [B, HW, G]: the group activations of the pixel's class, labels0 [B, HW], stand-in slot table [K, G])."""
@@ -382,8 +354,6 @@ class _RegSpec:
     forward leaves zeroed) and the constant part of the spx_reg descriptor."""
 
     def __init__(self, tables, ident, terms: int, weights, epsilon: float, device):
-        from . import _lib
-
         self.tables, self.ident, self.terms = tables, ident, int(terms)
         r = _lib.SpxReg()
         if terms & _GROUP_TERMS:
@@ -406,8 +376,6 @@ class _RegSpec:
         self.workspace = torch.zeros(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
 
     def bind(self, wd: Optional[torch.Tensor], head: Optional[torch.Tensor]):
-        from . import _lib
-
         r = self.desc
         if self.terms & _GROUP_TERMS:
             if tuple(wd.shape) != (r.U, r.P):
@@ -426,8 +394,6 @@ class _RegFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, wd, head, spec):
-        from . import _lib
-
         lib = _lib.load()
         wd_c = wd.detach().contiguous() if wd is not None else None
         head_c = head.detach().contiguous() if head is not None else None
@@ -443,8 +409,6 @@ class _RegFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_total, g_terms):
-        from . import _lib
-
         if g_total is None and g_terms is None:
             return None, None, None
         wd, head = ctx.saved_tensors
@@ -463,37 +427,29 @@ def _is_group_model(ppnet) -> bool:
 
 def _check_weights(ws, what: str) -> None:
     for w in ws:
-        if not w.is_cuda:
-            raise SpxError(f"{what}: weights on {w.device}; the regularisers run on the GPU only (no CPU fallback)")
+        _lib.require_gpu(w, f"{what}: a weight")
         if w.dtype != torch.float32:
             raise SpxError(f"{what}: weights are {w.dtype}; the kernels take fp32")
-
-
-def _same_key(a, b) -> bool:
-    # objects (tables, identity tensors) by identity - the cache holds them, so an id cannot be recycled - numbers by value
-    return a is not None and len(a) == len(b) and all(x is y or (isinstance(x, (int, str)) and x == y) for x, y in zip(a, b))
 
 
 def _reg_spec(net, terms: int, weights, epsilon: float, device, holder) -> _RegSpec:
     """The kernel-side spec of ``net``, cached in ``holder._spx_reg_spec`` on the group tables' identity (rebuilt with every
     table version: a pruned bank or re-assigned identity gives new tables), the L1 identity tensor and its version."""
-    tables = None
+    tables = src = version = None
     if terms & _GROUP_TERMS:
         _, _, _, tables = net._group_index(device)
         if tables is None or getattr(tables, "reg", None) is None:
             raise SpxError("regularisers: the group tables are outside the kernels' domain (GPU, <= 192 classes with "
                            "prototypes, the same number of groups <= 16 for every class, <= 16 scales)")
-    key = (tables, str(device))
     if terms & REG_L1:
         src = net.group_class_identity if _is_group_model(net) else net.prototype_class_identity
-        key = key + (src, src._version, getattr(net, "_tables_version", 0))
-    c = getattr(holder, "_spx_reg_spec", None)
-    if c is not None and _same_key(c[0], key):
-        return c[1]
-    ident = src.detach().to(device=device, dtype=torch.float32).contiguous() if terms & REG_L1 else None
-    spec = _RegSpec(tables, ident, terms, weights, epsilon, device)
-    object.__setattr__(holder, "_spx_reg_spec", (key, spec))
-    return spec
+        version = getattr(net, "_tables_version", 0)
+
+    def build():
+        ident = src.detach().to(device=device, dtype=torch.float32).contiguous() if terms & REG_L1 else None
+        return _RegSpec(tables, ident, terms, weights, epsilon, device)
+
+    return cached(holder, "_spx_reg_spec", (tables, src), (str(device), version), build)
 
 
 def _reg_apply(net, terms: int, weights, epsilon: float, holder, logits: Optional[torch.Tensor] = None):
@@ -609,8 +565,6 @@ def slot_scale_table(table: torch.Tensor, num_scales: int, scale_num_prototypes)
 
 
 def _act_desc(v, lab, sid, cfg):
-    from . import _lib
-
     B, J, HW = v.shape
     d = _lib.SpxActLoss()
     d.vals, d.labels, d.slot_scale = _lib.ptr(v), _lib.ptr(lab), _lib.ptr(sid)
@@ -627,8 +581,6 @@ class _ActLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vals, labels, sid, cfg):
-        from . import _lib
-
         lib = _lib.load()
         v = vals.detach().contiguous()
         lab = labels.to(device=v.device, dtype=torch.int32).contiguous()
@@ -651,8 +603,6 @@ class _ActLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_total, g_terms):
-        from . import _lib
-
         if g_total is None and g_terms is None:
             return None, None, None, None
         v, lab, sid, coef = ctx.saved_tensors
@@ -664,7 +614,7 @@ class _ActLossFn(torch.autograd.Function):
         return grad, None, None, None
 
 
-class ActivationRegularizers(nn.Module):
+class ActivationRegularizers(_SlotTable, nn.Module):
     """The activation-side terms of the training objective (segmentation/model/loss.py:149-348; module_multiscale.py:170-175,
     module_multiscale_group_train.py:189-190) in one pipeline: ``forward(prototype_activations, target_labels)`` returns
     ``(total, terms)`` with terms = [spatial entropy, sample entropy, norm] (fp32 [3], for logging without a sync) and total =
@@ -702,36 +652,18 @@ class ActivationRegularizers(nn.Module):
         self.activation = activation
         self._terms, self._weights = int(terms), tuple(float(w) for w in weights)
 
-    def _slot_table(self) -> torch.Tensor:
-        ident = self.prototype_class_identity
-        c = getattr(self, "_slot_table_cache", None)
-        if c is None or c[0] is not ident or c[1] != ident._version:
-            c = (ident, ident._version, class_slot_table(ident))
-            self._slot_table_cache = c
-        return c[2]
-
     def _tables_on(self, table: torch.Tensor, dev):
-        """(table on ``dev``, its slot-scale table on ``dev``), cached per table OBJECT, in-place version, scale ranges and
-        device: host work with a read-back, done once.  A few entries, so that one module can serve the model's table (a
-        ``ClassDistances``) and its own (an activation tensor) in turn; an entry holds its table, so an id cannot be recycled."""
+        """(table on ``dev``, its slot-scale table on ``dev``), cached per table, scale ranges and device: host work with a
+        read-back, done once.  A few entries, so that one module can serve the model's table (a ``ClassDistances``) and its
+        own (an activation tensor) in turn."""
         scales = tuple((int(s), tuple(int(x) for x in self.scale_num_prototypes[s])) for s in range(int(self.num_scales)))
-        key = (table._version, scales, str(dev))
-        cache = getattr(self, "_act_tables_cache", None)
-        if cache is None:
-            cache = self._act_tables_cache = []
-        for c in cache:
-            if c[0] is table and c[1] == key:
-                return c[2], c[3]
-        sid = slot_scale_table(table, self.num_scales, self.scale_num_prototypes).to(dev)
-        cache.insert(0, (table, key, table.to(dev), sid))
-        del cache[4:]
-        return cache[0][2], cache[0][3]
+        build = lambda: (table.to(dev), slot_scale_table(table, self.num_scales, self.scale_num_prototypes).to(dev))
+        return cached(self, "_act_tables_cache", (table,), (scales, str(dev)), build, ways=4)
 
     def _run(self, prototype_activations, target_labels: torch.Tensor):
         cd = prototype_activations if isinstance(prototype_activations, ClassDistances) else None
         src = cd.values if cd is not None else prototype_activations
-        if not src.is_cuda:
-            raise SpxError(f"activation losses: input on {src.device}; the losses run on the GPU only (no CPU fallback)")
+        _lib.require_gpu(src, "activation losses: input")
         if src.dtype != torch.float32:
             raise SpxError(f"activation losses: input is {src.dtype}; the kernels take fp32")
         dev = src.device

@@ -23,8 +23,7 @@ _LABEL_BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
 
 
 def _dev_ptr(t: torch.Tensor, name: str) -> int:
-    if not t.is_cuda:
-        raise SpxError(f"{name} is on {t.device}: scaleprotoseg_amd metrics run on an AMD GPU only (no CPU fallback)")
+    _lib.require_gpu(t, name)
     return t.data_ptr()
 
 
@@ -173,8 +172,7 @@ class SegmentationMetrics:
 
     def __init__(self, num_classes: int, prototype_class_identity: Optional[torch.Tensor], device):
         self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise SpxError(f"SegmentationMetrics runs on an AMD GPU only (device {self.device}); there is no CPU fallback")
+        _lib.require_gpu(self.device, "SegmentationMetrics")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.num_classes = K = int(num_classes)

@@ -15,8 +15,10 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
+from ._cache import cached
 from .functional import (MAX_FUSED_HEAD_ROWS, BankLayout, ClassGather, SpxError, class_gather_table,
-                         cross_entropy_from_logits, proto_head_forward, shifted_labels_i32, wide_linear)
+                         cross_entropy_from_logits, identity_is_one_hot, invalidate_pack_cache, proto_head_forward,
+                         push_min_from_features, shifted_labels_i32, wide_linear)
 from .loss import ClassDistances
 
 
@@ -117,12 +119,8 @@ class _PrototypeBankMixin:
         until prototype_class_identity is re-assigned (prune_prototypes, attribute assignment), edited in place
         (tensor version counter) or the scale table changes."""
         ident = self.prototype_class_identity
-        tag = (self._tables_version, ident._version, layout.scale_ranges, str(device))
-        cache = getattr(self, "_gather_cache", None)
-        if cache is None or cache[0] is not ident or cache[1] != tag:
-            cache = (ident, tag, class_gather_table(layout, ident, device))      # holds ident: its id cannot be recycled
-            self._gather_cache = cache
-        keys, width, table = cache[2]
+        keys, width, table = cached(self, "_gather_cache", (ident,), (self._tables_version, layout.scale_ranges, str(device)),
+                                    lambda: class_gather_table(layout, ident, device))
         B = target_labels.shape[0]
         labels0 = shifted_labels_i32(target_labels.reshape(B, -1), device)
         return ClassGather(labels=labels0, keys=keys, width=width, table=table)
@@ -191,25 +189,19 @@ class _PrototypeBankMixin:
         ``labels_for_grid((H, W))`` returns the label map [B, H, W] at the latent resolution (the grid is only known after
         the backbone has run).  Returns None when the fused kernel does not apply (MSC list input, a
         prototype_class_identity that is not one-hot, features off the GPU): the caller then reduces the written map."""
-        from .functional import class_gather_table, identity_is_one_hot, push_min_from_features
-
         conv = self.conv_features(x)
         if isinstance(conv, list) or not conv.is_cuda:
             return None
         self._check_fusable()
         layout = self._layout(1)
         ident = self.prototype_class_identity
-        tag = (self._tables_version, ident._version, layout.scale_ranges, str(conv.device))
-        cache = getattr(self, "_push_key_cache", None)
-        if cache is None or cache[0] is not ident or cache[1] != tag:
-            keys = class_gather_table(layout, ident, conv.device)[0] if identity_is_one_hot(ident) else None
-            cache = (ident, tag, keys)
-            self._push_key_cache = cache
-        if cache[2] is None:
+        keys = cached(self, "_push_key_cache", (ident,), (self._tables_version, layout.scale_ranges, str(conv.device)),
+                      lambda: class_gather_table(layout, ident, conv.device)[0] if identity_is_one_hot(ident) else None)
+        if keys is None:
             return None
         labels = labels_for_grid((conv.shape[2], conv.shape[3]))
         return push_min_from_features(conv, self.prototype_vectors, layout, labels, ident, void_class=void_class,
-                                      max_dist=max_dist, keys=cache[2])
+                                      max_dist=max_dist, keys=keys)
 
     def forward(self, x, **kwargs):
         conv = self.conv_features(x)
@@ -347,8 +339,6 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         """+1 own class / incorrect_strength elsewhere (model_multiscale.py:449-464)."""
         pos = torch.t(self.prototype_class_identity).to(self.last_layer.weight.device)
         self.last_layer.weight.data.copy_(1 * pos + incorrect_strength * (1 - pos))
-        from .functional import invalidate_pack_cache
-
         invalidate_pack_cache()
 
     def _initialize_weights(self):

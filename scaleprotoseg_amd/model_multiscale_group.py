@@ -18,8 +18,10 @@ from typing import Any, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
+from ._cache import cached
 from .functional import (MAX_FUSED_HEAD_ROWS, MAX_FUSED_TAIL_CLASSES, GroupTables, SpxError, cross_entropy_from_logits,
-                         group_dense, group_exp, proto_head_forward, shifted_labels_i32, wide_group_tail, wide_linear)
+                         group_dense, group_exp, invalidate_pack_cache, proto_head_forward, shifted_labels_i32, wide_group_tail,
+                         wide_linear)
 from .model_multiscale import _PrototypeBankMixin, _build_add_on, _first_add_on_channels
 from .utils import projection_simplex_sort
 
@@ -135,10 +137,10 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         # (the scale ranges: the ScaleMax spans hang on these tables, and ``scale_num_prototypes[s] = ...`` is an item edit of a
         # dict that passes no __setattr__)
         scales = tuple(tuple(int(v) for v in self.scale_num_prototypes[s]) for s in range(self.num_scales))
-        key = (self._tables_version, ident._version, tuple(gp.weight.shape for gp in self.group_projection), scales, str(device))
-        c = self._group_index_cache
-        if c is not None and c[0] is ident and c[1] == key:
-            return c[2]
+        extras = (self._tables_version, tuple(gp.weight.shape for gp in self.group_projection), scales, str(device))
+        return cached(self, "_group_index_cache", (ident,), extras, lambda: self._group_index_build(ident, device))
+
+    def _group_index_build(self, ident: torch.Tensor, device):
         P = self.num_prototypes
         rows, cols, r0 = [], [], 0
         col_block, col_local = torch.full((P,), -1, dtype=torch.int32), torch.zeros(P, dtype=torch.int32)
@@ -167,9 +169,7 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
             if gs and all(g == gs[0] for g in gs) and 1 <= gs[0] <= 16 and 1 <= self.num_scales <= 16:
                 info, spans, nspans = group_scale_spans(ident, self.scale_num_prototypes, self.num_scales, gs[0])
                 tables.reg = GroupRegTables(i32(info), i32(spans), nspans, gs[0], self.num_scales)
-        out = (rows_.to(device), cols_.to(device), r0, tables)
-        self._group_index_cache = (ident, key, out)
-        return out
+        return rows_.to(device), cols_.to(device), r0, tables
 
     def _dense_group_matrix(self) -> torch.Tensor:
         dev = self.prototype_vectors.device
@@ -305,8 +305,6 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
     def set_last_layer_incorrect_connection(self):
         pos = torch.t(self.group_class_identity).to(self.last_layer_group.weight.device)  # :480-491
         self.last_layer_group.weight.data.copy_(1 * pos + self.incorrect_strength * (1 - pos))
-        from .functional import invalidate_pack_cache
-
         invalidate_pack_cache()
 
     def _initialize_weights(self, equiv_path=None, equiv_scale_weight: float = 0.25):

@@ -136,8 +136,7 @@ class ActivationOverlap:
 
     def __init__(self, num_classes: int, slot_table: torch.Tensor, device, quantile: float = 0.95):
         self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise SpxError(f"ActivationOverlap runs on an AMD GPU only (device {self.device}); there is no CPU fallback")
+        _lib.require_gpu(self.device, "ActivationOverlap")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.num_classes = K = int(num_classes)

@@ -196,8 +196,7 @@ def find_k_nearest_patches_to_prototypes(
         raise SpxError(f"batch_size = {batch_size} must be positive")
     net.eval()
     dev = torch.device(device or str(net.prototype_vectors.device))
-    if dev.type != "cuda":
-        raise SpxError("scaleprotoseg_amd runs on an AMD GPU only; there is no CPU fallback")
+    _lib.require_gpu(dev, "the model")
     rank, world = _dp_world(group)
     if image_range is not None:
         rng, world = image_range, 1

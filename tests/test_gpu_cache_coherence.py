@@ -1,7 +1,7 @@
 """Coherence of the host-side caches that sit between the caller and the kernels: the pack cache
-(``functional._cached_packs``), the modules' ``_gather_cache`` / ``_push_key_cache`` / ``_group_index_cache`` and the
-``spx_group`` tag, the losses' slot / pair / device tables, ``_act_tables_cache``, ``_spx_reg_spec`` and the ``target`` /
-``target_version`` attachment of ``ClassDistances``.
+(``functional._cached_packs``), every table cache that goes through ``scaleprotoseg_amd/_cache.py`` (the modules' gather, push-key
+and group-index tables, the losses' slot / pair / device / class tables, the regularisers' kernel spec), the ``spx_group`` tag and
+the ``target`` / ``target_version`` attachment of ``ClassDistances``.
 
 Every result that follows an edit is held against the CPU oracle (oracle/ppnet_oracle.py, the float64 restatements of the
 loss tests) evaluated on the values AS THEY ARE NOW, with the bounds the suite already states:
@@ -936,6 +936,53 @@ def test_group_table_caches_follow_the_edit(edit):
         _assert_discriminates(before, dict(wd=_dense_reference(net), groups=before["groups"]), ("wd",))
     _check_group_tables(net, dev, reg)
     _check_group_tables(net, dev, reg)
+
+
+def _group_acts():
+    """Group activations [B * GH * GW, GG] of every projection, made so that the class -> projection table decides the value: the
+    groups of projection j nearly agree on the pixels of class j and disagree elsewhere, so a class that is served another
+    class's projection loses most of its term."""
+    def make():
+        g = _gen(11)
+        lab = _labels(0, group=True).reshape(-1, 1)
+        acts = []
+        for j in range(GK):
+            base, noise = torch.randn(lab.numel(), 1, generator=g), torch.randn(lab.numel(), GG, generator=g)
+            acts.append(base + torch.where(lab == j + 1, 0.3 * noise, 3.0 * noise))
+        return acts
+
+    return _once("group_acts", make)
+
+
+def test_the_group_kld_tables_follow_the_group_identity():
+    """A long-lived ``KLDLossGroup`` after an in-place swap of two classes' row blocks of ``group_class_identity`` and after a
+    re-assignment to such a swapped copy (finetune_wandb_group.py:77-78 re-assigns it)."""
+    import scaleprotoseg_amd as spx
+
+    dev = _dev()
+    net = _group_net(dev)
+    target, acts = _labels(0, group=True), _group_acts()
+    tgt, dacts = target.to(dev), [a.to(dev) for a in acts]
+    kld = spx.KLDLossGroup(net.prototype_class_identity, net.group_class_identity, GG)
+
+    def check(what):
+        ref = O.kld_loss_group([a.double() for a in acts], target, kld.prototype_class_identity.cpu(), kld.group_class_identity.cpu(), GG)
+        _scalar_close(kld(dacts, tgt), ref, KLD_TOL, f"group KLD {what}")
+        return dict(kld=ref)
+
+    def swapped(a, b):
+        rows = list(range(GG * GK))
+        rows[a * GG:(a + 1) * GG], rows[b * GG:(b + 1) * GG] = rows[b * GG:(b + 1) * GG], rows[a * GG:(a + 1) * GG]
+        return rows
+
+    first = check("as built")
+    kld.group_class_identity[swapped(0, 1)] = kld.group_class_identity.clone()          # in place
+    second = check("after the in-place swap")
+    _assert_losses_discriminate(first, second, ("kld",))
+    kld.group_class_identity = kld.group_class_identity[swapped(2, 3)]                   # re-assigned
+    third = check("after the re-assignment")
+    _assert_losses_discriminate(second, third, ("kld",))
+    check("once more")
 
 
 def test_an_in_place_edit_of_the_returned_activations_voids_the_group_tag():

@@ -322,6 +322,34 @@ def test_kld_loss_group_module_matches_reference(golden):
     assert LO.kld_group_loss(m, acts, torch.zeros_like(t)).item() == 0.0   # void only: no term (loss.py:541-542)
 
 
+def test_kld_loss_group_tables_follow_edits_of_the_identities():
+    """The class -> projection table of a long-lived KLDLossGroup follows an in-place edit and a re-assignment of
+    ``group_class_identity`` (finetune_wandb_group.py:77-78 re-assigns it): after each, the module gathers what a freshly
+    built one gathers.  K = 4, G = 2, projection i holds i + 1, every class labelled."""
+    from oracle import ppnet_oracle as O
+    from scaleprotoseg_amd.loss import KLDLossGroup
+
+    K, G = 4, 2
+    ident = O.default_class_identity(8, K, 1)
+    gci = torch.zeros(G * K, K)
+    for k in range(K):
+        gci[G * k:G * k + G, k] = 1
+    swap = [2, 3, 0, 1, 4, 5, 6, 7]                                # the row blocks of classes 0 and 1 change places
+    acts = [torch.full((9, G), float(i + 1)) for i in range(K)]
+    target = torch.tensor([[[1, 2, 3], [4, 1, 2], [3, 4, 0]]])
+    gather = lambda m: m._gather_groups(acts, target)[0]
+    fresh = lambda g: gather(KLDLossGroup(ident, g.clone(), G))
+    before, after = fresh(gci), fresh(gci[swap])
+    assert not torch.equal(before, after)                          # the edit is visible in what is gathered
+    m = KLDLossGroup(ident, gci.clone(), G)
+    assert torch.equal(gather(m), before)
+    m.group_class_identity[swap] = m.group_class_identity.clone()  # (a) in place
+    assert torch.equal(m.group_class_identity, gci[swap])
+    assert torch.equal(gather(m), fresh(m.group_class_identity)) and torch.equal(gather(m), after)
+    m.group_class_identity = m.group_class_identity[swap]          # (b) re-assigned to a swapped copy: the first table again
+    assert torch.equal(gather(m), fresh(m.group_class_identity)) and torch.equal(gather(m), before)
+
+
 def test_kld_loss_refuses_inputs_outside_the_kernels():
     """Without the explicit opt-in the loss modules do not leave the GPU path: a CPU tensor is an error, not a fallback."""
     from oracle import ppnet_oracle as O
