@@ -343,8 +343,8 @@ def _edit_sgd(net, dev):
 
 
 def _edit_adam_foreach(net, dev):
-    """The suite's bounds are stated for a bf16-representable bank (tests/test_gpu_parity.py: the forward takes bf16(p), the
-    p . sum(G) term of dPrototypes the fp32 p, so off that grid the gradient has no reference within GRAD_TOL): as with SGD
+    """This file's references are stated for a bf16-representable bank (off that grid the gradient's reference is the per-site
+    restatement of DESIGN.md 4 "operand sites", held by tests/test_gpu_offgrid.py, not plain autograd): as with SGD
     the step is made to land on the new values.  The first Adam step moves an element by lr g / (|g| + eps); with eps = 1
     a move of r lr, |r| < 1/2, takes g = r / (1 - |r|).  In fp32 that lands within a few 1e-7 of the target."""
     b2, h2 = _new_values(net)
