@@ -78,8 +78,15 @@ static_assert(spx_bwd_lds_bytes<6, 1, false>() <= 80 * 1024 && spx_bwd_lds_bytes
 // DACT: a gradient arrives on the [pixel][P] activations (kept out of the default instance).
 // ACC: bf16 features and a scale that spans several panels: its partial dX is summed in the fp32 scratch a.dx_acc (its own
 // instances: as a run-time branch the code cost the default instance 0.02-0.035 ms - it sits at the register cliff).
-template <int NPB, int NCB, bool XF32, int VM, bool GATHER, bool DACT, bool ACC = false>
+// ONEP: no two panels of the plan share a scale (every bank of at most 192 prototypes per scale), so no panel ever adds onto
+// another's dX: phase 2 neither loads nor unpacks a previous partial and needs no first / last-of-scale bookkeeping.  The
+// launcher picks it from the plan; it exists for one class block without a dAct gradient (spx_bwd_has_onep), every other
+// combination runs the general code, which computes the same for such a plan.
+template <int NCB, bool DACT>
+__host__ __device__ constexpr bool spx_bwd_has_onep() { return NCB == 1 && !DACT; }
+template <int NPB, int NCB, bool XF32, int VM, bool GATHER, bool DACT, bool ACC = false, bool ONEP = false>
 __global__ __launch_bounds__(256, SPX_BWD_WAVES) void spx_bwd_kernel(const SpxBwdArgs a) {
+    static_assert(!(ACC && ONEP), "a plan whose scales are single panels accumulates nothing");
     constexpr bool VEC = VM != 0, RAG = VM == 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const spx_plan& pl = a.plan;
@@ -127,7 +134,6 @@ __global__ __launch_bounds__(256, SPX_BWD_WAVES) void spx_bwd_kernel(const SpxBw
     const uint32_t voff_a = px_ok ? ((uint32_t)px * (uint32_t)P + (uint32_t)(4 * h)) * 4u : SPX_OOB;   // [px][row] fp32
     const spx_rsrc htr = make_rsrc(a.packed_headT);
     const spx_rsrc btr = make_rsrc_pred(a.packed_bankT);
-    const spx_rsrc p2r = make_rsrc(a.p2);
     const spx_rsrc htp = make_rsrc_pred(a.packed_headT);
     const spx_rsrc p2p = make_rsrc_pred(a.p2);
     // GATHER: this pixel's class (0xFFFE = none; padding rows carry class 0xFFFF) and its [px][slot] row offset
@@ -433,17 +439,20 @@ __global__ __launch_bounds__(256, SPX_BWD_WAVES) void spx_bwd_kernel(const SpxBw
                 return;
             }
             const spx_rsrc ddr = make_rsrc_pred(a.d_dist + ((size_t)b * P + p0 + pb * 32) * a.HW);
+            // row stride in bytes; its 15 multiples are formed here (see spx_opaque_s).  Not in the dAct instances: they live
+            // with scratch at the register cliff, and the different allocation cost six of them 4 to 76 more bytes of it.
+            const uint32_t row4 = (DACT ? HW : spx_opaque_s(HW)) * 4u;
             if (pb * 32 + 32 <= np) {     // wave-uniform: whole block real, no row predication
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
                     const int rb = (reg & 3) + 8 * (reg >> 2);
-                    dst[reg] = buf_load_f32(ddr, voff_d, (uint32_t)rb * HW * 4u);
+                    dst[reg] = buf_load_f32(ddr, voff_d, (uint32_t)rb * row4);
                 }
             } else {
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
                     const int rb = (reg & 3) + 8 * (reg >> 2);
-                    dst[reg] = buf_load_f32(ddr, (pb * 32 + rb + 4 * h < np) ? voff_d : SPX_OOB, (uint32_t)rb * HW * 4u);
+                    dst[reg] = buf_load_f32(ddr, (pb * 32 + rb + 4 * h < np) ? voff_d : SPX_OOB, (uint32_t)rb * row4);
                 }
             }
         };
@@ -567,7 +576,17 @@ __global__ __launch_bounds__(256, SPX_BWD_WAVES) void spx_bwd_kernel(const SpxBw
                         gv[i] = pair_of(ga, i) + pair_of(ddc, i);        // act' = -1 (folded into ga)
                     }
                 }
-                if (full && tile_full) {
+                // A partial block (padded prototype rows) of a full tile takes the unmasked path too where the activations go
+                // to the d_W stage (DW; the dAct instances keep their code as it is, see load_ddist).  Padded rows need no mask
+                // there: (1) their G is +0 without it - their head^T fragments are zeros (spx_pack: row_ok), so ga = +0;
+                // their dDist loads are dropped by the row predication (the gathered form: padding keys match no class), so
+                // ddc = +0; 1/((d+1)(d+eps)) is finite wherever dr > 0, so gv = fma(+0, rp, +0) = +0, and where dr > 0 fails
+                // the select below zeroes it as the masked path would.  (2) Their activations are finite (d = relu(dr) >= 0)
+                // but not zero; they reach only the d_W partial's columns of the padded prototypes - every output column of
+                // that product depends on its own prototype alone - which spx_dw_reduce_kernel sums into slab rows >= panel_np
+                // that spx_bank_reduce_kernel never reads (row < panel_np).  The activation BLOB of the wide heads is different:
+                // its block exponent is the maximum over all 32 rows, so those instances keep the mask.
+                if ((full || (DW && !DACT)) && tile_full) {
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         gv[i][0] = dr[i][0] > 0.0f ? gv[i][0] : 0.0f;
@@ -762,11 +781,11 @@ __global__ __launch_bounds__(256, SPX_BWD_WAVES) void spx_bwd_kernel(const SpxBw
         // ---- phase 2: dX^T[ch x px] = 2 rs * x + (-2 P)^T . G, one 32-channel block per (rolled) iteration ----
         const float rs_tot = rs + __shfl_xor(rs, 32);
         if (h == 0) rss[32 * wave + r] = 2.0f * rs_tot;      // the finish below wants 2 rs (the P^T fragments carry -2 p)
-        const bool first_of_scale = (panel == q_begin) || (pl.panel_ch0[panel - 1] != ch0);
+        const bool first_of_scale = ONEP || (panel == q_begin) || (pl.panel_ch0[panel - 1] != ch0);
         // A scale of more than 192 prototypes spans several panels, each adding its share of dX.  With fp32 features the sum
         // runs in dX itself; with bf16 features it runs in the caller's fp32 scratch a.dx_acc ([B][C][HW rounded up to 4]) and
         // only the scale's LAST panel writes dX, rounded once (through the bf16 buffer it was one rounding per panel).
-        const bool last_of_scale = (panel + 1 == q_end) || (pl.panel_ch0[panel + 1] != ch0);
+        const bool last_of_scale = ONEP || (panel + 1 == q_end) || (pl.panel_ch0[panel + 1] != ch0);
         const bool acc32 = ACC && !XF32 && !(first_of_scale && last_of_scale);     // workgroup-uniform
 
         constexpr int BT = spx_bwd_bt_bytes<NPB>();
@@ -819,7 +838,8 @@ __global__ __launch_bounds__(256, SPX_BWD_WAVES) void spx_bwd_kernel(const SpxBw
                     const uint32_t vo = (ch_ok && (fpx + (v + 1) * PV <= a.HW)) ? fvo + 16u * v : SPX_OOB;
                     xw[v] = buf_load_b128(xir, vo, 0);
                     // first panel of a scale: nothing to accumulate onto (dropped load returns 0)
-                    pw[v] = buf_load_b128(dxr, (first_of_scale || acc32) ? SPX_OOB : vo, 0);
+                    if (ONEP) pw[v] = u32x4{0u, 0u, 0u, 0u};
+                    else pw[v] = buf_load_b128(dxr, (first_of_scale || acc32) ? SPX_OOB : vo, 0);
                 }
             }
         };
@@ -979,13 +999,18 @@ template <int NPB, int NCB, bool GATHER, bool DACT>
 static hipError_t launch_bwd_gd(const SpxBwdArgs& a, int x_dtype, dim3 grid, hipStream_t s) {
     constexpr size_t lds = (size_t)spx_bwd_lds_bytes<NPB, NCB, DACT>();
     // ACC instances exist for bf16 features only
-    bool acc = false;
-    if (x_dtype != 1 && a.dx_acc && a.dx) {
-        for (int q = 1; q < a.plan.npanels; ++q) acc |= a.plan.panel_ch0[q] == a.plan.panel_ch0[q - 1];
-    }
+    bool acc = false, onep = true;      // onep: every scale is one panel (panels of a scale are neighbours in the plan)
+    for (int q = 1; q < a.plan.npanels; ++q) onep &= a.plan.panel_ch0[q] != a.plan.panel_ch0[q - 1];
+    if (x_dtype != 1 && a.dx_acc && a.dx) acc = !onep;
     spx_dispatch_x(x_dtype, a.vec_ok, [&](auto xf32, auto vm) {
         constexpr bool XF32 = decltype(xf32)::value;
         constexpr int VM = decltype(vm)::value;
+        if constexpr (spx_bwd_has_onep<NCB, DACT>()) {
+            if (onep) {
+                hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, XF32, VM, GATHER, DACT, false, true>), grid, dim3(256), lds, s, a);
+                return;
+            }
+        }
         if constexpr (!XF32) {
             if (acc) {
                 hipLaunchKernelGGL((spx_bwd_kernel<NPB, NCB, false, VM, GATHER, DACT, true>), grid, dim3(256), lds, s, a);

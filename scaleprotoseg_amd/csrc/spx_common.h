@@ -114,6 +114,13 @@ __device__ __forceinline__ int spx_opaque(int v) {
     asm volatile("" : "+v"(v));
     return v;
 }
+// The same for a wave-uniform value.  Multiples of it (the row strides rb * HW * 4 of a 16-row access, ...) are then formed by
+// one scalar multiply each where they are used; hoisted out of the panel loop there are more of them than scalar registers,
+// and each comes back through a v_readlane_b32 plus the wait states a VALU-written SGPR needs before a buffer access reads it.
+__device__ __forceinline__ uint32_t spx_opaque_s(uint32_t v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
 
 // Row of a 32x32 MFMA accumulator held in register `reg` of lane half `h`
 // (cdna guide §3: row = (reg&3) + 8*(reg>>2) + 4*(lane>>5), col = lane&31).
