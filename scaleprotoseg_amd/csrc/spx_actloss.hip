@@ -18,7 +18,6 @@
 //   finish  terms, reciprocal item counts, weighted total, and per (segment, slot) the coefficients of the gradient pass
 //   backward  d/da = -p (a - lse_j + H_j) cS  +  sample-entropy term recomputed per pixel  +  sign(a) [tie mask] cN, times a'(d)
 #include "spx_kld_walk.h"
-#include <algorithm>
 
 #define SPX_ACT_TABLE_LDS (60 * 1024)        // LDS budget of the per-class tables of pass B and the gradient pass (class blocks beyond it)
 #define SPX_ACT_COEFS 6                      // per (segment, slot): lse, H, max |a|, cS, cN, cG
@@ -166,58 +165,31 @@ __global__ __launch_bounds__(SPX_KLD_THREADS) void spx_act_max_kernel(const floa
         m[j] = -3.0e38f;
         ma[j] = 0.0f;
     }
-    int cur = -1;
     unsigned int run = 0;
-    auto publish = [&]() {
-        if (cur < 0) return;
-        const unsigned int pmc = pm[cur];
+    unsigned int pmc;
+    float a[JT], aa[JT];
+    spx_segment_walk<JT>(
+        v, lab, w, J, HW, 0, K,
+        [&](const float (&raw)[JT], int c, bool ok) SPX_WALK_INLINE {
+            pmc = ok ? pm[c] : 0u;
+            spx_act_apply(a, raw, mode, eps);
 #pragma unroll
-        for (int j = 0; j < JT; ++j)
-            if (j < J && ((pmc >> j) & 1u)) {
-                const float wm = wave_max_f32(m[j]), wa = wave_max_f32(ma[j]);
-                if (lane == 0) {
-                    atomicMax(&tmax[cur * J + j], float_key(wm));
-                    atomicMax(&tabs[cur * J + j], float_key(wa));
-                }
-                m[j] = -3.0e38f;
-                ma[j] = 0.0f;
+            for (int j = 0; j < JT; ++j) {
+                const bool in = (pmc >> j) & 1u;               // (bits at or beyond J are never set)
+                aa[j] = in ? fabsf(a[j]) : 0.0f;
+                a[j] = in ? a[j] : -3.0e38f;
+                gm = fmaxf(gm, aa[j]);
             }
-        if (lane == 0) atomicAdd(&cnt[cur], run);
-        run = 0;
-    };
-    SpxKldStep<JT> nx;
-    spx_kld_fetch(nx, v, lab, w, 0, J, HW);
-    for (int step = 0; step < w.nsteps; ++step) {
-        const SpxKldStep<JT> cs = nx;
-        spx_kld_fetch(nx, v, lab, w, step + 1, J, HW);
-        const int c = step < w.nvalid ? cs.c : -1;
-        const bool ok = c >= 0 && c < K;
-        const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
-        const int c0 = okm ? __builtin_amdgcn_readlane(c, __builtin_ffsll((long long)okm) - 1) : -1;
-        const bool uniform = __builtin_amdgcn_ballot_w64(ok && c != c0) == 0;
-        if (okm == 0) continue;                            // a step without a class pixel
-        const unsigned int pmc = ok ? pm[c] : 0u;
-        float a[JT], aa[JT];
-        spx_act_apply(a, cs.d, mode, eps);
-#pragma unroll
-        for (int j = 0; j < JT; ++j) {
-            const bool in = (pmc >> j) & 1u;               // (bits at or beyond J are never set)
-            aa[j] = in ? fabsf(a[j]) : 0.0f;
-            a[j] = in ? a[j] : -3.0e38f;
-            gm = fmaxf(gm, aa[j]);
-        }
-        if (uniform) {
-            if (c0 != cur) {
-                publish();
-                cur = c0;
-            }
+        },
+        [&](unsigned long long okm) SPX_WALK_INLINE {
             run += (unsigned)__builtin_popcountll(okm);
 #pragma unroll
             for (int j = 0; j < JT; ++j) {
                 m[j] = fmaxf(m[j], a[j]);
                 ma[j] = fmaxf(ma[j], aa[j]);
             }
-        } else if (ok) {
+        },
+        [&](int c) SPX_WALK_INLINE {
             atomicAdd(&cnt[c], 1u);
 #pragma unroll
             for (int j = 0; j < JT; ++j)
@@ -225,9 +197,23 @@ __global__ __launch_bounds__(SPX_KLD_THREADS) void spx_act_max_kernel(const floa
                     atomicMax(&tmax[c * J + j], float_key(a[j]));
                     atomicMax(&tabs[c * J + j], float_key(aa[j]));
                 }
-        }
-    }
-    publish();
+        },
+        [&](int cur) SPX_WALK_INLINE {
+            const unsigned int pmc = pm[cur];
+#pragma unroll
+            for (int j = 0; j < JT; ++j)
+                if (j < J && ((pmc >> j) & 1u)) {
+                    const float wm = wave_max_f32(m[j]), wa = wave_max_f32(ma[j]);
+                    if (lane == 0) {
+                        atomicMax(&tmax[cur * J + j], float_key(wm));
+                        atomicMax(&tabs[cur * J + j], float_key(wa));
+                    }
+                    m[j] = -3.0e38f;
+                    ma[j] = 0.0f;
+                }
+            if (lane == 0) atomicAdd(&cnt[cur], run);
+            run = 0;
+        });
     const float wg = wave_max_f32(gm);
     if (lane == 0 && wg > 0.0f) atomicMax(gmx, float_key(wg));
     __syncthreads();
@@ -288,6 +274,7 @@ __global__ __launch_bounds__(SPX_KLD_THREADS) void spx_act_sums_kernel(const flo
     for (int j = 0; j < JT; ++j) a0[j] = a1[j] = aa[j] = at[j] = 0.0f;
 #pragma unroll
     for (int g = 0; g < GT; ++g) ah[g] = 0.0f;
+    // own copy of spx_segment_walk's loop: on the walker three of the four instances lose an occupancy step (profiles/segment_walk_summary.md)
     int cur = -1;
     auto publish = [&]() {
         if (cur < 0) return;
@@ -583,46 +570,32 @@ __global__ __launch_bounds__(SPX_KLD_THREADS) void spx_act_backward_kernel(const
     }
 }
 
-static int spx_act_tile_rows(int B, int HW, int W, dim3& grid) {
-    // rows of a workgroup's tile and the grid of the reduction passes: as spx_launch_kld
-    int trows = SPX_KLD_TILE;
-    grid = dim3((unsigned)((HW + SPX_KLD_PX_PER_WG - 1) / SPX_KLD_PX_PER_WG), (unsigned)B);
-    if (W > 0) {
-        const int tiles_x = (W + SPX_KLD_TILE - 1) / SPX_KLD_TILE, H = HW / W;
-        while (trows > 16 && (long long)B * tiles_x * ((H + trows - 1) / trows) < SPX_KLD_MIN_WGS) trows >>= 1;
-        grid.x = (unsigned)(tiles_x * ((H + trows - 1) / trows));
-    }
-    return trows;
-}
-
-#define SPX_ACT_DISPATCH(KERNEL, ...)                                                              \
-    do {                                                                                           \
-        if (J <= 4) hipLaunchKernelGGL(KERNEL<4>, grid, dim3(SPX_KLD_THREADS), lds, s, __VA_ARGS__);        \
-        else if (J <= 8) hipLaunchKernelGGL(KERNEL<8>, grid, dim3(SPX_KLD_THREADS), lds, s, __VA_ARGS__);   \
-        else if (J <= 12) hipLaunchKernelGGL(KERNEL<12>, grid, dim3(SPX_KLD_THREADS), lds, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERNEL<16>, grid, dim3(SPX_KLD_THREADS), lds, s, __VA_ARGS__);              \
-    } while (0)
-
 hipError_t spx_launch_actloss_max(const spx_actloss* p, void* workspace, hipStream_t s) {
     const int B = p->B, J = p->J, HW = p->HW, W = p->W, K = p->K;
     dim3 grid;
-    const int trows = spx_act_tile_rows(B, HW, W, grid);
+    const int trows = spx_segment_tile_rows(B, HW, W, grid);
     const size_t lds = ((size_t)2 * K * J + 2 * K + 1) * 4;
     const SpxActWs ws = spx_act_ws(workspace, B, K, J);
-    SPX_ACT_DISPATCH(spx_act_max_kernel, p->vals, p->labels, p->slot_scale, J, HW, W, trows, K, p->mode, p->epsilon, ws);
+    spx_dispatch_jt(J, [&](auto jt) {
+        hipLaunchKernelGGL(spx_act_max_kernel<decltype(jt)::value>, grid, dim3(SPX_KLD_THREADS), lds, s, p->vals, p->labels, p->slot_scale, J, HW, W,
+                           trows, K, p->mode, p->epsilon, ws);
+    });
     return hipGetLastError();
 }
 
 hipError_t spx_launch_actloss_sums(const spx_actloss* p, void* workspace, hipStream_t s) {
     const int B = p->B, J = p->J, HW = p->HW, W = p->W, K = p->K;
     dim3 grid;
-    const int trows = spx_act_tile_rows(B, HW, W, grid);
+    const int trows = spx_segment_tile_rows(B, HW, W, grid);
     const size_t per_class = (size_t)J * (4 * 8 + 3 * 4) + 8 + 4;
-    const int KB = (int)std::min<size_t>((size_t)K, std::max<size_t>(1, (SPX_ACT_TABLE_LDS - 16) / per_class));
+    const int KB = spx_segment_class_block(K, per_class, SPX_ACT_TABLE_LDS - 16);
     grid.z = (unsigned)((K + KB - 1) / KB);
     const size_t lds = (size_t)KB * per_class + 16;
     const SpxActWs ws = spx_act_ws(workspace, B, K, J);
-    SPX_ACT_DISPATCH(spx_act_sums_kernel, p->vals, p->labels, p->slot_scale, J, HW, W, trows, K, KB, p->mode, p->epsilon, p->terms, ws);
+    spx_dispatch_jt(J, [&](auto jt) {
+        hipLaunchKernelGGL(spx_act_sums_kernel<decltype(jt)::value>, grid, dim3(SPX_KLD_THREADS), lds, s, p->vals, p->labels, p->slot_scale, J, HW, W,
+                           trows, K, KB, p->mode, p->epsilon, p->terms, ws);
+    });
     return hipGetLastError();
 }
 
@@ -636,15 +609,15 @@ hipError_t spx_launch_actloss_finish(const spx_actloss* p, void* workspace, floa
 hipError_t spx_launch_actloss_backward(const spx_actloss* p, const float* coef, const float* g_total, const float* g_terms, float* grad,
                                        hipStream_t s) {
     const int B = p->B, J = p->J, HW = p->HW, K = p->K;
-    const int JT = J <= 4 ? 4 : (J <= 8 ? 8 : (J <= 12 ? 12 : 16));
-    const size_t per_class = (size_t)SPX_ACT_COEFS * JT * 4 + 8 + 4;
-    const int KB = (int)std::min<size_t>((size_t)K, std::max<size_t>(1, SPX_ACT_TABLE_LDS / per_class));
-    // pixels per workgroup: as the KLD gradient pass
-    int ppw = SPX_KLD_PX_PER_WG;
-    while (ppw > SPX_KLD_THREADS && (long long)B * ((HW + ppw - 1) / ppw) < 512) ppw >>= 1;
-    dim3 grid((unsigned)((HW + ppw - 1) / ppw), (unsigned)B, (unsigned)((K + KB - 1) / KB));
-    const size_t lds = (size_t)KB * per_class;
-    SPX_ACT_DISPATCH(spx_act_backward_kernel, p->vals, p->labels, p->slot_scale, J, HW, K, KB, p->mode, p->epsilon, p->terms, p->norm_type,
-                     p->weights[0], p->weights[1], p->weights[2], coef, g_total, g_terms, ppw, grad);
+    spx_dispatch_jt(J, [&](auto jt) {
+        constexpr int JT = decltype(jt)::value;
+        const size_t per_class = (size_t)SPX_ACT_COEFS * JT * 4 + 8 + 4;
+        const int KB = spx_segment_class_block(K, per_class, SPX_ACT_TABLE_LDS);
+        const int ppw = spx_segment_px_per_wg(B, HW);
+        const dim3 grid((unsigned)((HW + ppw - 1) / ppw), (unsigned)B, (unsigned)((K + KB - 1) / KB));
+        hipLaunchKernelGGL(spx_act_backward_kernel<JT>, grid, dim3(SPX_KLD_THREADS), (size_t)KB * per_class, s, p->vals, p->labels, p->slot_scale, J,
+                           HW, K, KB, p->mode, p->epsilon, p->terms, p->norm_type, p->weights[0], p->weights[1], p->weights[2], coef, g_total,
+                           g_terms, ppw, grad);
+    });
     return hipGetLastError();
 }

@@ -849,13 +849,13 @@ static int kld_check_w(const char* fn, int32_t HW, int32_t W) {
 int spx_kld_segment_max(const float* vals, const int32_t* labels, int32_t B, int32_t J, int32_t HW, int32_t W, int32_t K,
                         uint32_t* smax_keys, uint32_t* counts, uint32_t* range_keys, void* stream) {
     if (kld_check("spx_kld_segment_max", vals, labels, B, J, HW, K, smax_keys, 0) || kld_check_w("spx_kld_segment_max", HW, W)) return 1;
-    return hip_status(spx_launch_kld(0, vals, labels, B, J, HW, W, K, (const float*)counts, (const float*)range_keys, nullptr, nullptr, smax_keys, (hipStream_t)stream), "spx_kld_segment_max");
+    return hip_status(spx_launch_kld_max(vals, labels, B, J, HW, W, K, smax_keys, counts, range_keys, (hipStream_t)stream), "spx_kld_segment_max");
 }
 int spx_kld_segment_sumexp(const float* vals, const int32_t* labels, int32_t B, int32_t J, int32_t HW, int32_t W, int32_t K,
                            const uint32_t* smax_keys, uint64_t* ssum_fx, void* stream) {
     if (kld_check("spx_kld_segment_sumexp", vals, labels, B, J, HW, K, ssum_fx, 0) || !smax_keys) return smax_keys ? 1 : fail("spx_kld_segment_sumexp: NULL smax_keys");
     if (kld_check_w("spx_kld_segment_sumexp", HW, W)) return 1;
-    return hip_status(spx_launch_kld(1, vals, labels, B, J, HW, W, K, (const float*)smax_keys, nullptr, nullptr, nullptr, ssum_fx, (hipStream_t)stream), "spx_kld_segment_sumexp");
+    return hip_status(spx_launch_kld_sumexp(vals, labels, B, J, HW, W, K, smax_keys, ssum_fx, (hipStream_t)stream), "spx_kld_segment_sumexp");
 }
 int spx_kld_segment_lse(const uint32_t* smax_keys, const uint64_t* ssum_fx, int32_t n, float* lse, const uint32_t* range_keys, int32_t HW,
                         double* scale, void* stream) {
@@ -875,13 +875,13 @@ int spx_kld_pair_sums(const float* vals, const int32_t* labels, int32_t B, int32
                       const float* lse, const double* scale, int64_t* a_fx, void* stream) {
     if (kld_check("spx_kld_pair_sums", vals, labels, B, J, HW, K, a_fx, 1) || !lse || !scale) return (lse && scale) ? 1 : fail("spx_kld_pair_sums: NULL lse / scale");
     if (kld_check_w("spx_kld_pair_sums", HW, W)) return 1;
-    return hip_status(spx_launch_kld(2, vals, labels, B, J, HW, W, K, lse, nullptr, nullptr, scale, a_fx, (hipStream_t)stream), "spx_kld_pair_sums");
+    return hip_status(spx_launch_kld_pairs(vals, labels, B, J, HW, W, K, lse, scale, a_fx, (hipStream_t)stream), "spx_kld_pair_sums");
 }
 int spx_kld_backward(const float* vals, const int32_t* labels, int32_t B, int32_t J, int32_t HW, int32_t K,
                      const float* lse, const float* A, const float* Cf, const float* cf_scale, float* grad, void* stream) {
     if (kld_check("spx_kld_backward", vals, labels, B, J, HW, K, grad, 1)) return 1;
     if (!lse || !A || !Cf) return fail("spx_kld_backward: NULL table");
-    return hip_status(spx_launch_kld(3, vals, labels, B, J, HW, 0, K, lse, A, Cf, nullptr, grad, (hipStream_t)stream, cf_scale), "spx_kld_backward");
+    return hip_status(spx_launch_kld_backward(vals, labels, B, J, HW, K, lse, A, Cf, cf_scale, grad, (hipStream_t)stream), "spx_kld_backward");
 }
 
 // ptrs = 0: the workspace query, which needs the sizes only

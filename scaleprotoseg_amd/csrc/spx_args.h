@@ -221,5 +221,12 @@ hipError_t spx_launch_actloss_sums(const spx_actloss* p, void* workspace, hipStr
 hipError_t spx_launch_actloss_finish(const spx_actloss* p, void* workspace, float* coef, float* out, hipStream_t s);
 hipError_t spx_launch_actloss_backward(const spx_actloss* p, const float* coef, const float* g_total, const float* g_terms, float* grad,
                                        hipStream_t s);
-hipError_t spx_launch_kld(int pass, const float* vals, const int32_t* labels, int B, int J, int HW, int W, int K, const float* t0,
-                          const float* t1, const float* t2, const double* scale, void* out, hipStream_t s, const float* cf_scale = nullptr);
+// the four streaming passes of the KLD loss (spx_kld.hip)
+hipError_t spx_launch_kld_max(const float* vals, const int32_t* labels, int B, int J, int HW, int W, int K, uint32_t* smax_keys,
+                              uint32_t* counts, uint32_t* range_keys, hipStream_t s);
+hipError_t spx_launch_kld_sumexp(const float* vals, const int32_t* labels, int B, int J, int HW, int W, int K, const uint32_t* smax_keys,
+                                 uint64_t* ssum_fx, hipStream_t s);
+hipError_t spx_launch_kld_pairs(const float* vals, const int32_t* labels, int B, int J, int HW, int W, int K, const float* lse,
+                                const double* scale, int64_t* a_fx, hipStream_t s);
+hipError_t spx_launch_kld_backward(const float* vals, const int32_t* labels, int B, int J, int HW, int K, const float* lse, const float* A,
+                                   const float* Cf, const float* cf_scale, float* grad, hipStream_t s);

@@ -233,6 +233,14 @@ __device__ __forceinline__ void ce_best(float v, int cls, float& m, int& best) {
 __device__ __forceinline__ float ce_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504089f); }
 __device__ __forceinline__ float ce_log(float x) { return __builtin_amdgcn_logf(x) * 0.69314718056f; }
 
+// __shfl_xor of a 64-bit key (the packed (value, index) minima of the push and prune reductions)
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    lo = __shfl_xor(lo, m);
+    hi = __shfl_xor(hi, m);
+    return ((uint64_t)hi << 32) | lo;
+}
+
 // monotone float -> uint32 key (total order incl. negatives), for packed (value,index) minima
 __device__ __forceinline__ uint32_t float_key(float v) {
     uint32_t u = __float_as_uint(v);

@@ -10,7 +10,6 @@
 // tables and INTEGER atomics (ordered float keys for the max, 64-bit fixed point for the sums), so results do not
 // depend on the order of arrival: the loss is run-to-run bit-identical like the rest of the path.
 #include "spx_kld_walk.h"
-#include <algorithm>
 
 
 // pass 0: smax_key[b][c][j] = max over the segment's pixels of vals (ordered-uint key of the float)
@@ -31,6 +30,7 @@ __global__ __launch_bounds__(SPX_KLD_THREADS) void spx_kld_max_kernel(const floa
     float m[SPX_KLD_MAXJ];
 #pragma unroll
     for (int j = 0; j < SPX_KLD_MAXJ; ++j) m[j] = -3.0e38f;
+    // own copy of spx_segment_walk's loop: on the walker this pass measured slower than the parent (profiles/segment_walk_summary.md)
     int cur = -1;                                          // class of the running maxima (wave-uniform)
     unsigned int run = 0;                                  // its pixels so far
     auto publish = [&]() {
@@ -52,8 +52,6 @@ __global__ __launch_bounds__(SPX_KLD_THREADS) void spx_kld_max_kernel(const floa
         spx_kld_fetch(nx, v, lab, w, step + 1, J, HW);
         const int c = step < w.nvalid ? cs.c : -1;
         const bool ok = c >= 0 && c < K;
-        // lanes without a class (void pixels, lanes past the map) contribute neutral values either way: a step is uniform when
-        // the lanes that HAVE a class agree on it (void borders and ragged tile edges do not send it down the per-lane path)
         const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
         const int c0 = okm ? __builtin_amdgcn_readlane(c, __builtin_ffsll((long long)okm) - 1) : -1;
         const bool uniform = __builtin_amdgcn_ballot_w64(ok && c != c0) == 0;
@@ -123,50 +121,34 @@ __global__ __launch_bounds__(SPX_KLD_THREADS) void spx_kld_sumexp_kernel(const f
     float acc[SPX_KLD_MAXJ];                               // <= 16 terms (steps of the walk) of (0, 1] each: fp32 is ample
 #pragma unroll
     for (int j = 0; j < SPX_KLD_MAXJ; ++j) acc[j] = 0.0f;
-    int cur = -1;
-    auto publish = [&]() {
-        if (cur < 0) return;
+    float e[SPX_KLD_MAXJ];
+    spx_segment_walk<SPX_KLD_MAXJ>(
+        v, lab, w, J, HW, 0, K,
+        [&](const float (&raw)[SPX_KLD_MAXJ], int c, bool ok) SPX_WALK_INLINE {
 #pragma unroll
-        for (int j = 0; j < SPX_KLD_MAXJ; ++j)
-            if (j < J) {
-                const double s = wave_sum_f64((double)acc[j]);
-                if (lane == 0) atomicAdd(&tab[cur * J + j], (unsigned long long)(s * FX + 0.5));
-                acc[j] = 0.0f;
-            }
-    };
-    SpxKldStep<SPX_KLD_MAXJ> nx;
-    spx_kld_fetch(nx, v, lab, w, 0, J, HW);
-    for (int step = 0; step < w.nsteps; ++step) {
-        const SpxKldStep<SPX_KLD_MAXJ> cs = nx;
-        spx_kld_fetch(nx, v, lab, w, step + 1, J, HW);
-        const int c = step < w.nvalid ? cs.c : -1;
-        const bool ok = c >= 0 && c < K;
-        // lanes without a class (void pixels, lanes past the map) contribute neutral values either way: a step is uniform when
-        // the lanes that HAVE a class agree on it (void borders and ragged tile edges do not send it down the per-lane path)
-        const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
-        const int c0 = okm ? __builtin_amdgcn_readlane(c, __builtin_ffsll((long long)okm) - 1) : -1;
-        const bool uniform = __builtin_amdgcn_ballot_w64(ok && c != c0) == 0;
-        float e[SPX_KLD_MAXJ];
+            for (int j = 0; j < SPX_KLD_MAXJ; ++j) e[j] = raw[j];
+            const float* smc = sm + (ok ? c : 0) * J;
 #pragma unroll
-        for (int j = 0; j < SPX_KLD_MAXJ; ++j) e[j] = cs.d[j];
-        const float* smc = sm + (ok ? c : 0) * J;
-#pragma unroll
-        for (int j = 0; j < SPX_KLD_MAXJ; ++j) e[j] = (ok && j < J) ? __expf(e[j] - smc[min(j, J - 1)]) : 0.0f;
-        if (uniform) {
-            if (okm == 0) continue;
-            if (c0 != cur) {
-                publish();
-                cur = c0;
-            }
+            for (int j = 0; j < SPX_KLD_MAXJ; ++j) e[j] = (ok && j < J) ? __expf(e[j] - smc[min(j, J - 1)]) : 0.0f;
+        },
+        [&](unsigned long long) SPX_WALK_INLINE {
 #pragma unroll
             for (int j = 0; j < SPX_KLD_MAXJ; ++j) acc[j] += e[j];
-        } else if (ok) {
+        },
+        [&](int c) SPX_WALK_INLINE {
 #pragma unroll
             for (int j = 0; j < SPX_KLD_MAXJ; ++j)
                 if (j < J) atomicAdd(&tab[c * J + j], (unsigned long long)((double)e[j] * FX + 0.5));
-        }
-    }
-    publish();
+        },
+        [&](int cur) SPX_WALK_INLINE {
+#pragma unroll
+            for (int j = 0; j < SPX_KLD_MAXJ; ++j)
+                if (j < J) {
+                    const double s = wave_sum_f64((double)acc[j]);
+                    if (lane == 0) atomicAdd(&tab[cur * J + j], (unsigned long long)(s * FX + 0.5));
+                    acc[j] = 0.0f;
+                }
+        });
     __syncthreads();
     for (int i = tid; i < K * J; i += SPX_KLD_THREADS)
         if (tab[i]) atomicAdd(&ssum_fx[(size_t)b * K * J + i], tab[i]);
@@ -201,6 +183,7 @@ __global__ __launch_bounds__(SPX_KLD_THREADS) void spx_kld_pairs_kernel(const fl
     for (int j = 0; j < JT; ++j)
 #pragma unroll
         for (int k = 0; k < JT; ++k) acc[j][k] = 0.0f;
+    // own copy of spx_segment_walk's loop: on the walker this pass measured slower than the parent (profiles/segment_walk_summary.md)
     int cur = -1;                                          // class the accumulators belong to (wave-uniform)
     auto publish = [&]() {
         if (cur < 0) return;
@@ -221,8 +204,6 @@ __global__ __launch_bounds__(SPX_KLD_THREADS) void spx_kld_pairs_kernel(const fl
         spx_kld_fetch(nx, v, lab, w, step + 1, J, HW);
         const int c = step < w.nvalid ? cs.c - c_lo : -1;
         const bool ok = c >= 0 && c < K;
-        // lanes without a class (void pixels, lanes past the map) contribute neutral values either way: a step is uniform when
-        // the lanes that HAVE a class agree on it (void borders and ragged tile edges do not send it down the per-lane path)
         const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
         const int c0 = okm ? __builtin_amdgcn_readlane(c, __builtin_ffsll((long long)okm) - 1) : -1;
         const bool uniform = __builtin_amdgcn_ballot_w64(ok && c != c0) == 0;
@@ -476,53 +457,45 @@ hipError_t spx_launch_kld_gram_loss(const int64_t* a_fx, const double* scale, co
     return hipGetLastError();
 }
 
-// (pass 0: t0 = counts, t1 = range keys)
-hipError_t spx_launch_kld(int pass, const float* vals, const int32_t* labels, int B, int J, int HW, int W, int K, const float* t0,
-                          const float* t1, const float* t2, const double* scale, void* out, hipStream_t s, const float* cf_scale) {
-    dim3 grid((unsigned)((HW + SPX_KLD_PX_PER_WG - 1) / SPX_KLD_PX_PER_WG), (unsigned)B);
-    dim3 blk(SPX_KLD_THREADS);
-    // rows of a workgroup's tile: 64 (16 steps per wave) on large maps; on small ones (training crops) 32 or 16, so that there
-    // are enough workgroups to fill the chip.  (Two workgroups per CU are enough since the passes fetch a step ahead: at 2 Mpx
-    // 64-row tiles = 512 workgroups run the max / sum-exp / pair passes in 27 / 22 / 39 us, 32-row tiles = 1024 in 39 / 25 / 52 -
-    // half the class-run publishes per pixel; 128-row tiles = 256 workgroups in 35 / 38 / 59.)
-    int trows = SPX_KLD_TILE;
-    if (W > 0 && pass != 3) {
-        const int tiles_x = (W + SPX_KLD_TILE - 1) / SPX_KLD_TILE, H = HW / W;
-        while (trows > 16 && (long long)B * tiles_x * ((H + trows - 1) / trows) < SPX_KLD_MIN_WGS) trows >>= 1;
-        grid.x = (unsigned)(tiles_x * ((H + trows - 1) / trows));
-    }
-    if (pass == 0)
-        hipLaunchKernelGGL(spx_kld_max_kernel, grid, blk, (size_t)(K * J + K + 2) * 4, s, vals, labels, J, HW, W, trows, K, (unsigned int*)out, (unsigned int*)t0, (unsigned int*)t1);
-    else if (pass == 1)
-        hipLaunchKernelGGL(spx_kld_sumexp_kernel, grid, blk, (size_t)K * J * 12, s, vals, labels, J, HW, W, trows, K, (const unsigned int*)t0, (unsigned long long*)out);
-    else if (pass == 2) {
-        // class blocks (grid.z) so that a block's tables fit SPX_KLD_TABLE_LDS
-        const size_t per_class = (size_t)J * J * 8 + (size_t)J * 4;
-        const int KB = (int)std::min<size_t>((size_t)K, std::max<size_t>(1, SPX_KLD_TABLE_LDS / per_class));
-        grid.z = (unsigned)((K + KB - 1) / KB);
-        const size_t lds = (size_t)KB * per_class;
-        unsigned long long* o = (unsigned long long*)out;
-        if (J <= 4) hipLaunchKernelGGL(spx_kld_pairs_kernel<4>, grid, blk, lds, s, vals, labels, J, HW, W, trows, K, KB, t0, scale, o);
-        else if (J <= 8) hipLaunchKernelGGL(spx_kld_pairs_kernel<8>, grid, blk, lds, s, vals, labels, J, HW, W, trows, K, KB, t0, scale, o);
-        else if (J <= 12) hipLaunchKernelGGL(spx_kld_pairs_kernel<12>, grid, blk, lds, s, vals, labels, J, HW, W, trows, K, KB, t0, scale, o);
-        else hipLaunchKernelGGL(spx_kld_pairs_kernel<16>, grid, blk, lds, s, vals, labels, J, HW, W, trows, K, KB, t0, scale, o);
-    } else {
-        const int JT = J <= 4 ? 4 : (J <= 8 ? 8 : (J <= 12 ? 12 : 16));
+hipError_t spx_launch_kld_max(const float* vals, const int32_t* labels, int B, int J, int HW, int W, int K, uint32_t* smax_keys,
+                              uint32_t* counts, uint32_t* range_keys, hipStream_t s) {
+    dim3 grid;
+    const int trows = spx_segment_tile_rows(B, HW, W, grid);
+    hipLaunchKernelGGL(spx_kld_max_kernel, grid, dim3(SPX_KLD_THREADS), (size_t)(K * J + K + 2) * 4, s, vals, labels, J, HW, W, trows, K, smax_keys,
+                       counts, range_keys);
+    return hipGetLastError();
+}
+hipError_t spx_launch_kld_sumexp(const float* vals, const int32_t* labels, int B, int J, int HW, int W, int K, const uint32_t* smax_keys,
+                                 uint64_t* ssum_fx, hipStream_t s) {
+    dim3 grid;
+    const int trows = spx_segment_tile_rows(B, HW, W, grid);
+    hipLaunchKernelGGL(spx_kld_sumexp_kernel, grid, dim3(SPX_KLD_THREADS), (size_t)K * J * 12, s, vals, labels, J, HW, W, trows, K, smax_keys,
+                       (unsigned long long*)ssum_fx);
+    return hipGetLastError();
+}
+hipError_t spx_launch_kld_pairs(const float* vals, const int32_t* labels, int B, int J, int HW, int W, int K, const float* lse,
+                                const double* scale, int64_t* a_fx, hipStream_t s) {
+    dim3 grid;
+    const int trows = spx_segment_tile_rows(B, HW, W, grid);
+    const size_t per_class = (size_t)J * J * 8 + (size_t)J * 4;
+    const int KB = spx_segment_class_block(K, per_class, SPX_KLD_TABLE_LDS);
+    grid.z = (unsigned)((K + KB - 1) / KB);
+    spx_dispatch_jt(J, [&](auto jt) {
+        hipLaunchKernelGGL(spx_kld_pairs_kernel<decltype(jt)::value>, grid, dim3(SPX_KLD_THREADS), (size_t)KB * per_class, s, vals, labels, J, HW, W,
+                           trows, K, KB, lse, scale, (unsigned long long*)a_fx);       // (two's complement)
+    });
+    return hipGetLastError();
+}
+hipError_t spx_launch_kld_backward(const float* vals, const int32_t* labels, int B, int J, int HW, int K, const float* lse, const float* A,
+                                   const float* Cf, const float* cf_scale, float* grad, hipStream_t s) {
+    spx_dispatch_jt(J, [&](auto jt) {
+        constexpr int JT = decltype(jt)::value;
         const size_t per_class = (size_t)(2 * JT * JT + 2 * JT) * 4;
-        const int KB = (int)std::min<size_t>((size_t)K, std::max<size_t>(1, SPX_KLD_TABLE_LDS / per_class));
-        grid.z = (unsigned)((K + KB - 1) / KB);
-        const size_t lds = (size_t)KB * per_class;
-        float* o = (float*)out;
-        // pixels per workgroup: 2048 on large maps; small maps (training crops) get enough workgroups to fill the chip - a thread
-        // then takes one pixel instead of walking eight in sequence behind the table set-up (80 -> ~20 us at 10 x 65 x 65)
-        // (2 Mpx, same box: 512 / 1024 / 2048 / 4096 / 8192 pixels per workgroup = 65 / 51 / 45 / 55 / 82 us)
-        int ppw = SPX_KLD_PX_PER_WG;
-        while (ppw > SPX_KLD_THREADS && (long long)B * ((HW + ppw - 1) / ppw) < 512) ppw >>= 1;
-        grid.x = (unsigned)((HW + ppw - 1) / ppw);
-        if (J <= 4) hipLaunchKernelGGL(spx_kld_backward_kernel<4>, grid, blk, lds, s, vals, labels, J, HW, K, KB, t0, t1, t2, cf_scale, ppw, o);
-        else if (J <= 8) hipLaunchKernelGGL(spx_kld_backward_kernel<8>, grid, blk, lds, s, vals, labels, J, HW, K, KB, t0, t1, t2, cf_scale, ppw, o);
-        else if (J <= 12) hipLaunchKernelGGL(spx_kld_backward_kernel<12>, grid, blk, lds, s, vals, labels, J, HW, K, KB, t0, t1, t2, cf_scale, ppw, o);
-        else hipLaunchKernelGGL(spx_kld_backward_kernel<16>, grid, blk, lds, s, vals, labels, J, HW, K, KB, t0, t1, t2, cf_scale, ppw, o);
-    }
+        const int KB = spx_segment_class_block(K, per_class, SPX_KLD_TABLE_LDS);
+        const int ppw = spx_segment_px_per_wg(B, HW);
+        const dim3 grid((unsigned)((HW + ppw - 1) / ppw), (unsigned)B, (unsigned)((K + KB - 1) / KB));
+        hipLaunchKernelGGL(spx_kld_backward_kernel<JT>, grid, dim3(SPX_KLD_THREADS), (size_t)KB * per_class, s, vals, labels, J, HW, K, KB, lse, A, Cf,
+                           cf_scale, ppw, grad);
+    });
     return hipGetLastError();
 }

@@ -15,13 +15,6 @@
 #define SPX_PRUNE_CHUNK 4096    // pixels per workgroup of the map reduction
 #define SPX_PRUNE_BINS 1024     // LDS histogram of the footprint mode: labels -1 .. 1022; others are counted pairwise
 
-__device__ __forceinline__ uint64_t prune_shfl_xor_u64(uint64_t v, int m) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = __shfl_xor(lo, m);
-    hi = __shfl_xor(hi, m);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 __device__ __forceinline__ uint32_t prune_dist_key(float d, bool is_void) {
     // + 0.0f: -0.0 and +0.0 get one key; fmaxf(d, 0) maps NaN to 0 (the distance kernel's relu does the same)
     return __float_as_uint(fmaxf(d, 0.0f) + 0.0f) | (is_void ? 0x80000000u : 0u);
@@ -55,7 +48,7 @@ __global__ __launch_bounds__(256) void spx_prune_argmin_kernel(const float* __re
         unsigned long long m = best[pp];
 #pragma unroll
         for (int s = 32; s >= 1; s >>= 1) {
-            const unsigned long long o = prune_shfl_xor_u64(m, s);
+            const unsigned long long o = shfl_xor_u64(m, s);
             m = o < m ? o : m;
         }
         if ((tid & 63) == 0) s_min[tid >> 6][pp] = m;
@@ -133,7 +126,7 @@ __global__ __launch_bounds__(256) void spx_prune_footprint_kernel(const int32_t*
     }
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) {
-        const unsigned long long x = prune_shfl_xor_u64(best, s);
+        const unsigned long long x = shfl_xor_u64(best, s);
         best = x > best ? x : best;
     }
     if ((tid & 63) == 0) s_best[tid >> 6] = best;

@@ -7,13 +7,6 @@
 
 #define SPX_PUSH_CHUNK 8192   // pixels per workgroup
 
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    lo = __shfl_xor(lo, m);
-    hi = __shfl_xor(hi, m);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 __global__ __launch_bounds__(256) void spx_push_argmin_kernel(const float* __restrict__ dist,
                                                               const int32_t* __restrict__ labels,
                                                               const float* __restrict__ ident, int P, int K, int HW,
