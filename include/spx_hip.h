@@ -555,6 +555,31 @@ int spx_overlap_accumulate(const float* planes, const int64_t* host_strides, con
                            int32_t w, int32_t H, int32_t W, int64_t* inter, int64_t* area, int64_t* images, void* workspace,
                            void* stream);
 
+/* Push bounding boxes (additive to ABI 17; segmentation/push_multiscale_optimization.py:416-497, helpers.py:53-87): for every
+ * pushed prototype the box of its latent patch in image pixels and the rectangle of the highly activated region around it.
+ *   planes, host_strides, u, labels   as spx_overlap_accumulate takes them (labels [N, H, W]: 0 = void, k + 1 = class k)
+ *   rows        int32 [R, 4] on the device = (n, c, class k, flat latent index f): plane (n, c), the prototype's class, the pushed
+ *               latent pixel.  host_rows: the same table in host memory, or NULL.  Given, every row is checked on the host
+ *               (0 <= n < N, 0 <= c < C, k >= 0, 0 <= f < h*w) and a bad one refuses the call; with NULL the kernel writes -1 to
+ *               the eight outputs of such a row and reads nothing for it.
+ *   thresholds  fp32 [N, C]; only the entries the rows name are read.  The reference's threshold is np.percentile(u, 95) =
+ *               spx_overlap_thresholds at q = 0.95 for the same planes and size.
+ *   rf box      ph = H / h, pw = W / w, i = f / w, j = f % w, in double as Python's floats:
+ *               rf = [int(i*ph), int(i*ph + ph) + 1, int(j*pw), int(j*pw + pw) + 1]; the ends may exceed H, W and are stored so
+ *   hit(Y, X)   labels[n, Y, X] == k + 1 ? u[n, c, Y, X] >= T : 0 >= T   (non-strict; with T <= 0 every pixel outside the class hits)
+ *   crop        from (sh, eh, sw, ew) = rf with four sticky `stopped` flags, until all are set, a pass does in this order, each step
+ *               on the box as the step before left it:
+ *                 0: not stopped[0], sh > 0     and a hit in row sh - 1, columns sw..ew (clipped to W - 1): sh -= 1, else stopped[0]
+ *                 1: not stopped[1], eh < H - 1 and a hit in row eh + 1, the same columns:                  eh += 1, else stopped[1]
+ *                 2: not stopped[2], sw > 0     and a hit in column sw - 1, rows sh..eh (clipped to H - 1): sw -= 1, else stopped[2]
+ *                 3: not stopped[3], ew < W - 1 and a hit in column ew + 1, the same rows:                  ew += 1, else stopped[3]
+ *               then m = add_margin: crop = (max(sh - m, 0), min(eh + m, H - 1) + 1, max(sw - m, 0), min(ew + m, W - 1) + 1)
+ * Outputs int32 [R, 4] each: rf_boxes and crops, (h0, h1, w0, w1) with exclusive ends.  Integer results of a serial walk: run-to-run
+ * identical.  One launch of R workgroups, no workspace.  Limits: those of spx_overlap_accumulate, R <= 2^24, 0 <= add_margin <= 32768. */
+int spx_push_boxes(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                   const int32_t* host_rows, const float* thresholds, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
+                   int32_t W, int32_t add_margin, int32_t* rf_boxes, int32_t* crops, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,8 @@ Public surface mirrors the reference's module/function names for this path:
     ActivationOverlap, high_activation_threshold    (segmentation/analysis/prototype_overlap.py, group_overlap.py: overlap
                                                      mIoU of the high-activation masks of one class's prototypes / groups;
                                                      cubic upsample + exact quantile threshold, recomputed, never stored)
+    push_bounding_boxes, push_box_tables            (segmentation/push_multiscale_optimization.py:416-497, helpers.py:53-87:
+                                                     the push's patch box and greedy high-activation crop per prototype)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -68,8 +70,10 @@ from .push import (  # noqa: F401
     compute_distances,
     global_min,
     min_across_dataset,
+    push_box_tables,
     push_prototypes_multiscale,
 )
+from .pushbox import push_bounding_boxes  # noqa: F401
 from .prune import NearestPatches, find_k_nearest_patches_to_prototypes, prune_prototypes  # noqa: F401
 from .utils import projection_simplex_sort, resize_label  # noqa: F401
 

@@ -832,6 +832,29 @@ int spx_overlap_accumulate(const float* planes, const int64_t* host_strides, con
                                                     (unsigned long long*)images, workspace, (hipStream_t)stream), who);
 }
 
+#define SPX_PBX_MAX_ROWS (1 << 24)
+
+int spx_push_boxes(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                   const int32_t* host_rows, const float* thresholds, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
+                   int32_t W, int32_t add_margin, int32_t* rf_boxes, int32_t* crops, void* stream) {
+    static const char* who = "spx_push_boxes";
+    if (!labels || !rows || !thresholds || !rf_boxes || !crops) return fail("%s: NULL labels / rows / thresholds / boxes", who);
+    if (label_bytes != 1 && label_bytes != 4 && label_bytes != 8)
+        return fail("%s: label byte code %d (1 = uint8, 4 = int32, 8 = int64)", who, label_bytes);
+    if (R < 1 || R > SPX_PBX_MAX_ROWS) return fail("%s: %d rows (1..%d)", who, R, SPX_PBX_MAX_ROWS);
+    if (add_margin < 0 || add_margin > SPX_OVL_MAX_OUT) return fail("%s: add_margin %d outside 0..%d", who, add_margin, SPX_OVL_MAX_OUT);
+    if (int e = overlap_check(who, planes, host_strides, N, C, h, w, H, W, rows)) return e;
+    if (host_rows)
+        for (int r = 0; r < R; ++r) {
+            const int32_t* q = host_rows + 4 * (size_t)r;
+            if (q[0] < 0 || q[0] >= N || q[1] < 0 || q[1] >= C || q[2] < 0 || q[3] < 0 || q[3] >= h * w)
+                return fail("%s: row %d = (n %d, c %d, class %d, flat index %d) out of range (N=%d C=%d, class >= 0, h*w=%d)", who, r,
+                            q[0], q[1], q[2], q[3], N, C, h * w);
+        }
+    return hip_status(spx_launch_push_boxes(planes, (const long long*)host_strides, labels, label_bytes, rows, thresholds, R, N, C, h, w,
+                                            H, W, add_margin, rf_boxes, crops, (hipStream_t)stream), who);
+}
+
 static int kld_check(const char* who, const float* vals, const int32_t* labels, int32_t B, int32_t J, int32_t HW, int32_t K,
                      const void* out, int pairs) {
     if (!vals || !labels || !out) return fail("%s: NULL buffer", who);

@@ -1,0 +1,78 @@
+// What the activation-overlap metrics (spx_overlap.hip) and the push bounding boxes (spx_pushbox.hip) share: the upsampled
+// value of a pixel recomputed from the latent plane, the strided view of the planes and the label read.  ONE function,
+// compiled with -ffp-contract=off, gives a pixel the same bits in every pass of either file.
+#ifndef SPX_OVERLAP_SAMPLE_H
+#define SPX_OVERLAP_SAMPLE_H
+#include "spx_common.h"
+
+struct OvlPlanes {                // element strides of a 4-D fp32 tensor, in (n, channel, y, x) order
+    const float* p;
+    long long sn, sc, sy, sx;
+};
+
+static inline OvlPlanes ovl_planes(const float* p, const long long* st) {
+    OvlPlanes m;
+    m.p = p;
+    m.sn = st[0];
+    m.sc = st[1];
+    m.sy = st[2];
+    m.sx = st[3];
+    return m;
+}
+
+// ---- the upsampled value ---------------------------------------------------------------------------------------------
+// Source coordinate of output index d for `in` source and `out` output samples: s = (d + 0.5) * in / out - 0.5, taken
+// EXACTLY as the fraction num / den with num = (2d + 1) * in - out, den = 2 * out: i = floor(s), t = s - i = r / den with one
+// rounding (fits int32: the entry points bound out <= 32768, in <= 16384).  Taps i - 1 .. i + 2, clamped to the grid.
+__device__ __forceinline__ void ovl_coord(int d, int in, int out, int& i, float& t) {
+    const int num = (2 * d + 1) * in - out, den = 2 * out;
+    int r;
+    if (num < 0) {                // only -out < num < 0: i = -1
+        i = -1;
+        r = num + den;
+    } else {
+        i = (int)((unsigned)num / (unsigned)den);
+        r = num - i * den;
+    }
+    t = (float)r / (float)den;
+}
+// Keys' cubic convolution weights at a = -0.75 (OpenCV's INTER_CUBIC, torch's bicubic) for the taps at distance
+// t + 1, t, 1 - t, 2 - t.
+__device__ __forceinline__ float ovl_cc1(float x) { return ((1.25f * x - 2.25f) * x) * x + 1.0f; }            // |x| <= 1
+__device__ __forceinline__ float ovl_cc2(float x) { return ((-0.75f * x + 3.75f) * x - 6.0f) * x + 3.0f; }    // 1 < |x| < 2
+__device__ __forceinline__ void ovl_weights(float t, float* wgt) {
+    wgt[0] = ovl_cc2(t + 1.0f);
+    wgt[1] = ovl_cc1(t);
+    wgt[2] = ovl_cc1(1.0f - t);
+    wgt[3] = ovl_cc2(2.0f - t);
+}
+__device__ __forceinline__ int ovl_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+// taps of one axis: element offsets (clamped index - origin) * stride and the four weights
+__device__ __forceinline__ void ovl_axis(int d, int in, int out, int origin, int stride, int* off, float* wgt) {
+    int i;
+    float t;
+    ovl_coord(d, in, out, i, t);
+    ovl_weights(t, wgt);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) off[a] = (ovl_clamp(i - 1 + a, in - 1) - origin) * stride;
+}
+// THE value of an upsampled pixel: rows first, left to right, then the four rows top to bottom.  p may point to LDS or to
+// memory; the arithmetic is the same sequence of fp32 operations either way.
+__device__ __forceinline__ float ovl_value(const float* p, const int* oy, const float* wy, const int* ox, const float* wx) {
+    float v = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const float* q = p + oy[a];
+        const float row = ((q[ox[0]] * wx[0] + q[ox[1]] * wx[1]) + q[ox[2]] * wx[2]) + q[ox[3]] * wx[3];
+        v = a == 0 ? row * wy[0] : v + row * wy[a];
+    }
+    return v;
+}
+
+__device__ __forceinline__ long long ovl_label(const void* labels, int label_bytes, size_t o) {
+    if (label_bytes == 1) return (long long)((const uint8_t*)labels)[o];
+    if (label_bytes == 4) return (long long)((const int32_t*)labels)[o];
+    return ((const long long*)labels)[o];
+}
+
+#endif  // SPX_OVERLAP_SAMPLE_H

@@ -1,12 +1,15 @@
 """Prototype push on the MI355X kernels.
 
 Mirrors the numerical part of segmentation/push_multiscale_optimization.py (lines 34-190 and 323-335):
-``compute_distances`` -> ``min_across_dataset`` -> ``global_min`` -> commit + de-dup.  The plotting half
-(``update_prototypes_on_image``, :341-685) is visualisation and is not part of this package.
+``compute_distances`` -> ``min_across_dataset`` -> ``global_min`` -> commit + de-dup.  Of the plotting half
+(``update_prototypes_on_image``, :341-685) the two integer tables ``proto_rf_boxes`` / ``proto_bound_boxes`` are computed
+(``push_box_tables``, the kernel behind ``pushbox.push_bounding_boxes``); every image and plot dump and the class-restricted
+threshold ``threshold_gt`` (used for a PNG crop only, never stored) are visualisation and are not part of this package.
 
 Dataset protocol (image decoding / normalisation is the data layer, out of scope): ``len(dataset)`` and
 ``dataset[i] -> (image, target)`` with ``image`` a normalised float tensor [3, h, w] and ``target`` an
-integer label map [h, w] (0 = void, 1..K), optionally ``dataset.convert_targets``.
+integer label map [h, w] (0 = void, 1..K), optionally ``dataset.convert_targets``.  For the box tables the target's own
+shape is the image size ``(H, W)`` the boxes are expressed in (the reference reads it from the annotation file, :385-404).
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from ._lib import SpxError
 from .functional import argmin_over_images, push_masked_argmin
 from .utils import resize_label
 
@@ -149,6 +153,71 @@ def commit_push(ppnet, patches: Sequence[np.ndarray], root_dir: Optional[os.Path
     return dup
 
 
+@torch.no_grad()
+def push_box_tables(best: torch.Tensor, list_min_patch: Sequence[torch.Tensor], dataset, ppnet,
+                    device: Optional[str] = None, q: float = 0.95, add_margin: int = 5) -> Tuple[np.ndarray, np.ndarray]:
+    """(proto_rf_boxes, proto_bound_boxes), int64 [P, 6] = [image index, h0, h1, w0, w1, class] of every prototype's winning
+    patch (push_multiscale_optimization.py:254-321, 416-497), on the model as it is BEFORE the bank is overwritten.
+
+    The winners' images and flat indices come to the host in one copy; each winning image is encoded once and its labels are
+    uploaded once (the reference re-runs the backbone once per prototype); ``distance_2_similarity`` runs on the channels of
+    that image's winners only; the thresholds and the crops are ``pushbox.push_bounding_boxes``."""
+    from .metrics import prototype_classes
+    from .pushbox import push_bounding_boxes
+
+    device = device or str(ppnet.prototype_vectors.device)
+    P = ppnet.num_prototypes
+    best = torch.as_tensor(best).to(device)
+    flat = torch.cat(list(list_min_patch), dim=0).to(device)[best, torch.arange(P, device=device)]
+    host = torch.stack([best, flat]).cpu()                                   # the one device-to-host copy of the winners
+    img_of, flat_of = host[0].tolist(), host[1].tolist()
+    cls_of = prototype_classes(ppnet.prototype_class_identity).tolist()
+    by_image: Dict[int, List[int]] = {}
+    for p in range(P):
+        by_image.setdefault(int(img_of[p]), []).append(p)
+    order, parts = [], []
+    for i in sorted(by_image):
+        protos = by_image[i]
+        img, target = dataset[i]
+        if getattr(dataset, "convert_targets", None) is not None:
+            target = dataset.convert_targets(target)
+        x = img.unsqueeze(0).to(device) if img.dim() == 3 else img.to(device)
+        conv, dist = ppnet.push_forward(x)
+        if isinstance(conv, list):
+            raise SpxError("push boxes need one feature map per image (MSC list input is not supported)")
+        chans = torch.tensor(protos, dtype=torch.int64, device=dist.device)
+        act = ppnet.distance_2_similarity(dist[:, chans]).float()            # [1, winners of this image, h, w]
+        labels = torch.as_tensor(np.ascontiguousarray(target))
+        if labels.dim() != 2:
+            raise SpxError(f"target of image {i} must be [H, W] (got {tuple(labels.shape)})")
+        if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
+            labels = labels.to(torch.int64)
+        rows = torch.tensor([[0, j, cls_of[p], int(flat_of[p])] for j, p in enumerate(protos)], dtype=torch.int32)
+        rf, box = push_bounding_boxes(act, labels.unsqueeze(0).to(device), rows, q=q, add_margin=add_margin)
+        order += protos
+        parts.append(torch.cat([rf, box], dim=1))
+    got = torch.cat(parts, dim=0).cpu().numpy()                              # [P, 8] in `order`
+    proto_rf_boxes = np.full((P, 6), -1, dtype=np.int64)
+    proto_bound_boxes = np.full((P, 6), -1, dtype=np.int64)
+    for r, p in enumerate(order):
+        proto_rf_boxes[p] = [img_of[p], *got[r, :4], cls_of[p]]
+        proto_bound_boxes[p] = [img_of[p], *got[r, 4:], cls_of[p]]
+    return proto_rf_boxes, proto_bound_boxes
+
+
+def save_box_tables(proto_rf_boxes: np.ndarray, proto_bound_boxes: np.ndarray, root_dir: os.PathLike, prefix: str,
+                    epoch_number: int) -> Tuple[str, str]:
+    """The reference's two files (push_multiscale_optimization.py:275-279, 311-321): ``<root>/epoch-<n>/<prefix>-receptive_field<n>.npy``
+    and ``<root>/epoch-<n>/<prefix><n>.npy``."""
+    epoch_dir = os.path.join(root_dir, "epoch-" + str(epoch_number))
+    os.makedirs(epoch_dir, exist_ok=True)
+    rf_path = os.path.join(epoch_dir, prefix + "-receptive_field" + str(epoch_number) + ".npy")
+    box_path = os.path.join(epoch_dir, prefix + str(epoch_number) + ".npy")
+    np.save(rf_path, proto_rf_boxes)
+    np.save(box_path, proto_bound_boxes)
+    return rf_path, box_path
+
+
 def _dp_world(group) -> Tuple[int, int]:
     import torch.distributed as dist
 
@@ -164,9 +233,18 @@ def push_prototypes_multiscale(
     log: Callable = print,
     device: Optional[str] = None,
     group=None,
+    boxes: bool = False,
+    epoch_number: Optional[int] = None,
+    proto_bound_boxes_filename_prefix: Optional[str] = None,
     **_ignored,
 ):
-    """Numerical part of push_multiscale_optimization.py:193-338 (plot/file-dump arguments are accepted and ignored).
+    """Numerical part of push_multiscale_optimization.py:193-338 (the image / plot dump arguments are accepted and ignored).
+
+    With ``boxes=True``, or when ``proto_bound_boxes_filename_prefix`` is given, the reference's ``proto_rf_boxes`` and
+    ``proto_bound_boxes`` tables (int64 [P, 6], ``push_box_tables``) are computed before the bank is overwritten and appended
+    to the result: (best, flat indices, dropped duplicates, proto_rf_boxes, proto_bound_boxes).  With
+    ``root_dir_for_saving_prototypes``, the prefix and ``epoch_number`` all set they are also saved under the reference's names
+    (``save_box_tables``).  Not under a sharded push: with more than one rank this raises ``SpxError``.
 
     Data-parallel form (SURVEY.md 8e "Push"; new capability, the reference is single-process): when
     ``torch.distributed`` is initialised with more than one rank, every rank scans a contiguous shard of the image list
@@ -186,12 +264,19 @@ def push_prototypes_multiscale(
     num_classes = net.num_classes
     device = device or str(net.prototype_vectors.device)
     rank, world = _dp_world(group)
+    want_boxes = bool(boxes) or proto_bound_boxes_filename_prefix is not None
+    if want_boxes and world > 1:
+        raise SpxError(f"push bounding boxes are not available under a sharded push ({world} ranks): run the push with boxes in "
+                       "one process, or drop boxes=True / proto_bound_boxes_filename_prefix")
     if world == 1:
         best, tot_idx = min_across_dataset(dataset, net, num_classes, void_class=0, device=device)
+        tables = push_box_tables(best, tot_idx, dataset, net, device=device) if want_boxes else None
         patches = global_min(best, tot_idx, dataset, net, device=device)
         dup = commit_push(net, patches, root_dir_for_saving_prototypes, log=log)
+        if tables is not None and None not in (root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number):
+            save_box_tables(tables[0], tables[1], root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number)
         log("\tpush time: \t{0}".format(time.time() - start))
-        return best, tot_idx, dup
+        return (best, tot_idx, dup) if tables is None else (best, tot_idx, dup, tables[0], tables[1])
 
     P = net.num_prototypes
     rng = dp.shard_range(len(dataset), rank, world)

@@ -1,0 +1,117 @@
+"""Bounding boxes of pushed prototypes on the GPU (segmentation/push_multiscale_optimization.py:416-497, the greedy crop
+helpers.py:53-87): the ``proto_rf_boxes`` / ``proto_bound_boxes`` tables every "what does this prototype look like" step reads.
+
+Definition, per row ``(n, c, k, f)`` = activation plane ``a[n, c]`` (fp32, latent grid ``h x w``), the prototype's class ``k``, the
+flat latent index ``f`` of the pushed patch; labels ``y[n]`` of size ``H x W`` (0 = void, ``k + 1`` = class ``k``):
+
+* patch box, in Python's float64: ``ph = H / h``, ``pw = W / w``, ``i = f // w``, ``j = f % w``,
+  ``rf = [int(i*ph), int(i*ph + ph) + 1, int(j*pw), int(j*pw + pw) + 1]``; the ends may exceed ``H`` or ``W`` (the reference's
+  behaviour) and are stored as they are.
+* ``u`` = the plane upsampled to ``H x W`` by the rule of ``overlap.py``; ``T = np.percentile(u, 95)`` over the whole image
+  = ``high_activation_threshold(q=0.95)``.
+* ``hit = v >= T`` with ``v = u`` where ``y == k + 1`` and 0 elsewhere (non-strict, unlike the overlap masks; with ``T <= 0``
+  every pixel outside the class is a hit).
+* greedy crop from ``(sh, eh, sw, ew) = rf`` with four sticky ``stopped`` flags, until all four are set; a pass does, in this
+  order and each step on the box as the step before left it:
+  0. not stopped[0], ``sh > 0`` and a hit in row ``sh - 1``, columns ``sw..ew`` (inclusive, clipped to the image): ``sh -= 1``,
+     else stopped[0];  1. the same below: ``eh < H - 1``, row ``eh + 1``: ``eh += 1``, else stopped[1];
+  2. ``sw > 0`` and a hit in column ``sw - 1``, rows ``sh..eh``: ``sw -= 1``, else stopped[2];  3. ``ew < W - 1``, column
+  ``ew + 1``: ``ew += 1``, else stopped[3].  Then ``box = (max(sh - m, 0), min(eh + m, H - 1) + 1, max(sw - m, 0),
+  min(ew + m, W - 1) + 1)`` with ``m = add_margin``.
+
+The reference resizes, sorts and walks NumPy rows on the host once per prototype.  Here ``spx_push_boxes`` walks the same
+steps with one workgroup per row on values recomputed from the latent plane (the function the threshold select uses, so the
+two agree on every pixel); the ``[H, W]`` map is never written.
+
+Not built: the class-restricted threshold ``threshold_gt`` (the reference uses it for a PNG crop only and never stores it; it
+needs a masked select), every image and plot dump, and boxes under a sharded (``torch.distributed``) push.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+from ._lib import SpxError
+from .metrics import _LABEL_BYTES, _dev_ptr, _strides
+from .overlap import _planes, _rank, _thresholds, _workspace
+
+_MAX_SELECT_PLANES = 4096       # channels of one spx_overlap_thresholds call
+
+
+def _select_for(lib, planes: torch.Tensor, pairs: torch.Tensor, size, q: float) -> torch.Tensor:
+    """fp32 [N, C] thresholds, selected for the planes ``pairs`` ([U, 2] device int64 = (n, c)) names and NaN elsewhere."""
+    N, Cn = int(planes.shape[0]), int(planes.shape[1])
+    out = torch.full((N, Cn), float("nan"), dtype=torch.float32, device=planes.device)
+    for lo in range(0, int(pairs.shape[0]), _MAX_SELECT_PLANES):
+        part = pairs[lo:lo + _MAX_SELECT_PLANES]
+        named = planes[part[:, 0], part[:, 1]].unsqueeze(0)                      # [1, U', h, w], a copy of the named planes
+        thr = _thresholds(lib, named, size, q, _workspace(lib, 1, int(named.shape[1]), 1, planes.device))
+        out.index_put_((part[:, 0], part[:, 1]), thr[0])
+    return out
+
+
+def push_bounding_boxes(activations: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, *, thresholds: Optional[torch.Tensor] = None,
+                        q: float = 0.95, add_margin: int = 5, grid: Optional[Tuple[int, int]] = None):
+    """(rf_boxes, bound_boxes), int64 [R, 4] device tensors ``(h0, h1, w0, w1)`` with exclusive ends, as the module's header
+    defines them.
+
+    ``activations``: fp32 [N, C, h, w] with any strides, or pixel-major [M, C] with ``grid`` = (h, w).  ``labels``: [N, H, W]
+    uint8 / int32 / int64 on the device; its shape is the image size.  ``rows``: integer [R, 4] = (n, c, class, flat latent
+    index).  A host tensor is checked on the host (a row out of range raises) and uploaded; a device tensor is never read by
+    the host, and a row out of range comes back as -1.  ``thresholds``: fp32 [N, C] as ``high_activation_threshold`` returns
+    them; None selects them at ``q`` for exactly the planes the rows name.  Enqueues work on the current stream only; never
+    synchronises."""
+    lib = _lib.load()
+    _rank(q, 2)
+    planes = _planes(activations, grid, "activations")
+    _dev_ptr(planes, "activations")
+    _dev_ptr(labels, "labels")
+    if labels.dim() != 3 or labels.dtype not in _LABEL_BYTES:
+        raise SpxError(f"labels must be uint8, int32 or int64 [N, H, W] (got {labels.dtype} {tuple(labels.shape)})")
+    N, Cn, h, w = (int(v) for v in planes.shape)
+    if labels.shape[0] != N:
+        raise SpxError(f"labels hold {labels.shape[0]} images, activations {N}")
+    if labels.device != planes.device:
+        raise SpxError(f"labels are on {labels.device}, activations on {planes.device}")
+    H, W = int(labels.shape[1]), int(labels.shape[2])
+    if not isinstance(rows, torch.Tensor):
+        rows = torch.as_tensor(rows)
+    if rows.dim() != 2 or rows.shape[1] != 4 or rows.shape[0] < 1 or rows.is_floating_point():
+        raise SpxError(f"rows must be integer [R, 4] with R >= 1 (got {rows.dtype} {tuple(rows.shape)})")
+    R = int(rows.shape[0])
+    host_rows = None
+    if not rows.is_cuda:
+        host_rows = rows.detach().to(torch.int32).contiguous()
+        if not torch.equal(host_rows.to(torch.int64), rows.detach().to(torch.int64)):
+            raise SpxError("rows do not fit int32")
+        dev_rows = host_rows.to(planes.device)
+    else:
+        if rows.device != planes.device:
+            raise SpxError(f"rows are on {rows.device}, activations on {planes.device}")
+        dev_rows = rows.detach().to(torch.int32).contiguous()
+    if thresholds is None:
+        if host_rows is not None:
+            bad = (host_rows[:, 0] < 0) | (host_rows[:, 0] >= N) | (host_rows[:, 1] < 0) | (host_rows[:, 1] >= Cn)
+            if bool(bad.any()):
+                r = int(bad.nonzero()[0])
+                raise SpxError(f"row {r} names plane ({int(host_rows[r, 0])}, {int(host_rows[r, 1])}) outside [{N}, {Cn}]")
+            pairs = torch.unique(host_rows[:, :2].to(torch.int64), dim=0).to(planes.device)
+        else:                                      # no host read: one select per row, rows out of range fold onto plane (0, 0)
+            pairs = dev_rows[:, :2].to(torch.int64)
+            ok = (pairs[:, 0] >= 0) & (pairs[:, 0] < N) & (pairs[:, 1] >= 0) & (pairs[:, 1] < Cn)
+            pairs = pairs * ok.unsqueeze(1)
+        thresholds = _select_for(lib, planes, pairs, (H, W), q)
+    else:
+        _dev_ptr(thresholds, "thresholds")
+        if thresholds.dtype != torch.float32 or tuple(thresholds.shape) != (N, Cn) or thresholds.device != planes.device:
+            raise SpxError(f"thresholds must be fp32 [{N}, {Cn}] on {planes.device}")
+        thresholds = thresholds.detach().contiguous()
+    lab = labels.detach().contiguous()
+    rf = torch.empty(R, 4, dtype=torch.int32, device=planes.device)
+    box = torch.empty(R, 4, dtype=torch.int32, device=planes.device)
+    _lib.check(lib.spx_push_boxes(planes.data_ptr(), _strides(planes, (0, 1, 2, 3)), lab.data_ptr(), _LABEL_BYTES[lab.dtype],
+                                  _lib.ptr(dev_rows), None if host_rows is None else host_rows.data_ptr(), _lib.ptr(thresholds), R, N,
+                                  Cn, h, w, H, W, int(add_margin), _lib.ptr(rf), _lib.ptr(box), _lib.stream_ptr()))
+    return rf.to(torch.int64), box.to(torch.int64)
