@@ -580,6 +580,29 @@ int spx_push_boxes(const float* planes, const int64_t* host_strides, const void*
                    const int32_t* host_rows, const float* thresholds, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
                    int32_t W, int32_t add_margin, int32_t* rf_boxes, int32_t* crops, void* stream);
 
+/* Single-pass push (additive to ABI 17; segmentation/push_multiscale_optimization.py:135-137, :162-188): merge the per-image
+ * minima of B consecutive images (global indices image0 .. image0 + B - 1, later than every image already merged - the
+ * precondition of spx_prune_merge) into the running winner of every prototype, and gather the winner's feature vector while the
+ * batch's features are still on the device.
+ *   indices int64 [B, P], values fp32 [B, P]   what spx_dist_push_min / spx_push_argmin wrote for the batch
+ *   x            [B, C, HW] contiguous NCHW features of the batch; x_dtype 0 = bf16, 1 = fp32 (as spx_dist_push_min)
+ *   proto_scale  int32 [P]: channel block of every prototype (the reference's p / (P / S)); block s is channels s*Cs .. s*Cs + Cs - 1
+ * State, owned by the caller and updated in place: best_value fp32 [P] (initialise to +inf), best_image int64 [P] (-1),
+ * best_flat int64 [P] (0), best_patch fp32 [P, Cs] (0).
+ * Rule, per prototype p: (v, b) = the lexicographic minimum of (values[b, p], b) over b under fp32 `<` (the lowest image of the
+ * batch on ties; a NaN is never below anything and never wins).  If v < best_value[p], strictly:
+ *   best_value[p] = v;  best_image[p] = image0 + b;  best_flat[p] = f = indices[b, p];
+ *   best_patch[p, c] = (float) x[b, proto_scale[p] * Cs + c, f] for c < Cs   (bf16 -> fp32 widens exactly)
+ * otherwise nothing of row p is written, not even the same bits.  Because batches arrive in image order and an equal value
+ * does not replace, the state after all batches is values.argmin(dim=0) over all images with the lowest image on ties (:135-137)
+ * and the patches the reference gathers from it (:162-188); a prototype whose class never appears ends at image 0, flat 0, value
+ * max_dist.  Preconditions: 0 <= indices < HW (true of the two producers) and (proto_scale[p] + 1) * Cs <= C; a row that breaks
+ * one is left unchanged and nothing is read for it.  One wave per prototype: no atomics, run-to-run identical.  One launch, no
+ * workspace, nothing allocated. */
+int spx_push_merge(const int64_t* indices, const float* values, const void* x, int32_t x_dtype, int32_t B, int32_t P, int32_t C,
+                   int32_t HW, int32_t Cs, const int32_t* proto_scale, int64_t image0, float* best_value, int64_t* best_image,
+                   int64_t* best_flat, float* best_patch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

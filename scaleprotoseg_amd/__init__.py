@@ -26,6 +26,9 @@ Public surface mirrors the reference's module/function names for this path:
                                                      cubic upsample + exact quantile threshold, recomputed, never stored)
     push_bounding_boxes, push_box_tables            (segmentation/push_multiscale_optimization.py:416-497, helpers.py:53-87:
                                                      the push's patch box and greedy high-activation crop per prototype)
+    PushTable, push_single_pass                     (the same push in ONE pass over the data set, images encoded in batches:
+                                                     running winners and their feature vectors kept on the GPU;
+                                                     push_prototypes_multiscale(batch_size=...))
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -67,6 +70,8 @@ from .overlap import ActivationOverlap, OverlapResult, high_activation_threshold
 from .model_multiscale import PPNetMultiScale, construct_PPNet  # noqa: F401
 from .model_multiscale_group import PPNetMultiScaleGroup, construct_PPNet_Group  # noqa: F401
 from .push import (  # noqa: F401
+    PushTable,
+    push_single_pass,
     compute_distances,
     global_min,
     min_across_dataset,

@@ -697,6 +697,20 @@ int spx_argmin_images(const float* values, int32_t N, int32_t P, int64_t* best, 
     return hip_status(spx_launch_argmin_images(values, N, P, best, (hipStream_t)stream), "spx_argmin_images");
 }
 
+int spx_push_merge(const int64_t* indices, const float* values, const void* x, int32_t x_dtype, int32_t B, int32_t P, int32_t C,
+                   int32_t HW, int32_t Cs, const int32_t* proto_scale, int64_t image0, float* best_value, int64_t* best_image,
+                   int64_t* best_flat, float* best_patch, void* stream) {
+    static const char* who = "spx_push_merge";
+    if (!indices || !values || !x || !proto_scale) return fail("%s: NULL candidates / features / scale table", who);
+    if (!best_value || !best_image || !best_flat || !best_patch) return fail("%s: NULL state", who);
+    if (x_dtype != 0 && x_dtype != 1) return fail("%s: feature dtype code %d (0 = bf16, 1 = fp32)", who, x_dtype);
+    if (B < 1 || P < 1 || C < 1 || HW < 1 || Cs < 1) return fail("%s: empty input (B=%d P=%d C=%d HW=%d Cs=%d)", who, B, P, C, HW, Cs);
+    if (Cs > C) return fail("%s: %d channels per scale, features have %d", who, Cs, C);
+    if (image0 < 0 || image0 > INT64_MAX - B) return fail("%s: image index %lld outside 0 .. 2^63 - 1 - B", who, (long long)image0);
+    return hip_status(spx_launch_push_merge(indices, values, x, x_dtype, B, P, C, HW, Cs, proto_scale, image0, best_value, best_image,
+                                            best_flat, best_patch, (hipStream_t)stream), who);
+}
+
 int spx_upsample_argext(const float* src, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
                         int32_t take_max, int64_t* indices, float* values, void* stream) {
     if (!src || !indices) return fail("spx_upsample_argext: NULL buffer");

@@ -165,6 +165,9 @@ hipError_t spx_launch_push_argmin(const float* dist, const int32_t* labels, cons
                                   int HW, int void_class, float max_dist, int64_t* idx, float* val,
                                   uint64_t* scratch, hipStream_t s);
 hipError_t spx_launch_argmin_images(const float* values, int N, int P, int64_t* best, hipStream_t s);
+hipError_t spx_launch_push_merge(const int64_t* indices, const float* values, const void* x, int x_dtype, int B, int P, int C, int HW,
+                                 int Cs, const int32_t* proto_scale, long long image0, float* best_value, int64_t* best_image,
+                                 int64_t* best_flat, float* best_patch, hipStream_t s);
 hipError_t spx_launch_upsample_argext(const float* src, int N, int C, int h, int w, int H, int W, int take_max,
                                       int64_t* idx, float* val, hipStream_t s);
 hipError_t spx_launch_eval_accumulate(const float* logits, const long long* lst, const float* dist, const long long* dst,

@@ -157,6 +157,70 @@ __global__ void spx_argmin_images_kernel(const float* __restrict__ values, int N
     best[p] = bn;
 }
 
+// Single-pass push (spx_push_merge): the batch's per-image minima merged into the running winner of every prototype, and the
+// winner's feature vector gathered while the batch's features are still on the device.  One wave owns one prototype's row of
+// the state (SPX_PMG_WAVES rows per workgroup), so the in-place update needs no atomics, no LDS and no barrier:
+//   lanes stride over the images b, each keeping its first strict minimum (its b only grow: lowest b on ties, a NaN never
+//   passes `<`); a shuffle reduction on (value, b) makes the batch's winner wave-uniform; the row is rewritten only if that
+//   value is strictly below the running one (batches arrive in image order: the earlier image stays on a tie, which is
+//   argmin(dim=0) over all images); then the lanes stride over the Cs channels of the winner's latent pixel.
+// The gather is element-granular with stride HW (uncoalesced by nature) and happens only for rows that improve.
+#define SPX_PMG_WAVES 4
+
+template <bool XF32>
+__global__ __launch_bounds__(64 * SPX_PMG_WAVES) void spx_push_merge_kernel(
+    const int64_t* __restrict__ indices, const float* __restrict__ values, const void* __restrict__ x, int B, int P, int C, int HW,
+    int Cs, const int32_t* __restrict__ proto_scale, long long image0, float* __restrict__ best_value,
+    int64_t* __restrict__ best_image, int64_t* __restrict__ best_flat, float* __restrict__ best_patch) {
+    const int lane = threadIdx.x & 63;
+    const int p = blockIdx.x * SPX_PMG_WAVES + (threadIdx.x >> 6);
+    if (p >= P) return;                                       // wave-uniform
+    float bv = __builtin_inff();
+    int bb = -1;                                              // -1: no candidate (an empty lane, or only NaN / +inf values)
+    for (int b = lane; b < B; b += 64) {
+        const float v = values[(size_t)b * P + p];
+        if (v < bv) { bv = v; bb = b; }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ov = __shfl_xor(bv, m);
+        const int ob = __shfl_xor(bb, m);
+        const bool take = ob >= 0 && (bb < 0 || ov < bv || (ov == bv && ob < bb));
+        bv = take ? ov : bv;
+        bb = take ? ob : bb;
+    }
+    if (bb < 0 || !(bv < best_value[p])) return;              // wave-uniform: nothing of the row is written
+    const long long flat = indices[(size_t)bb * P + p];
+    const int s = proto_scale[p];
+    // outside the features (the entry's stated preconditions exclude it): the row is left as it was, nothing is read
+    if (flat < 0 || flat >= HW || s < 0 || (long long)(s + 1) * Cs > C) return;
+    const size_t src = ((size_t)bb * C + (size_t)s * Cs) * HW + (size_t)flat;
+    for (int c = lane; c < Cs; c += 64) {
+        float f;
+        if (XF32) f = ((const float*)x)[src + (size_t)c * HW];
+        else f = __uint_as_float((uint32_t)((const uint16_t*)x)[src + (size_t)c * HW] << 16);      // bf16 -> fp32 is exact
+        best_patch[(size_t)p * Cs + c] = f;
+    }
+    if (lane == 0) {
+        best_value[p] = bv;
+        best_image[p] = image0 + bb;
+        best_flat[p] = flat;
+    }
+}
+
+hipError_t spx_launch_push_merge(const int64_t* indices, const float* values, const void* x, int x_dtype, int B, int P, int C, int HW,
+                                 int Cs, const int32_t* proto_scale, long long image0, float* best_value, int64_t* best_image,
+                                 int64_t* best_flat, float* best_patch, hipStream_t s) {
+    const dim3 grid((P + SPX_PMG_WAVES - 1) / SPX_PMG_WAVES), block(64 * SPX_PMG_WAVES);
+    if (x_dtype == 1)
+        hipLaunchKernelGGL(spx_push_merge_kernel<true>, grid, block, 0, s, indices, values, x, B, P, C, HW, Cs, proto_scale, image0,
+                           best_value, best_image, best_flat, best_patch);
+    else
+        hipLaunchKernelGGL(spx_push_merge_kernel<false>, grid, block, 0, s, indices, values, x, B, P, C, HW, Cs, proto_scale, image0,
+                           best_value, best_image, best_flat, best_patch);
+    return hipGetLastError();
+}
+
 hipError_t spx_launch_push_argmin(const float* dist, const int32_t* labels, const float* ident, int B, int P, int K,
                                   int HW, int void_class, float max_dist, int64_t* idx, float* val,
                                   uint64_t* scratch, hipStream_t s) {

@@ -994,6 +994,20 @@ def argmin_over_images(values: torch.Tensor) -> torch.Tensor:
     return best
 
 
+def push_merge(indices: torch.Tensor, values: torch.Tensor, conv_features: torch.Tensor, proto_scale: torch.Tensor, image0: int,
+               best_value: torch.Tensor, best_image: torch.Tensor, best_flat: torch.Tensor, best_patch: torch.Tensor) -> None:
+    """One ``spx_push_merge``: the minima ``indices`` / ``values`` [B, P] of images ``image0 .. image0 + B - 1`` and their
+    features [B, C, H, W] (bf16 or fp32, contiguous) merged IN PLACE into the running winners ``best_value`` fp32 [P],
+    ``best_image`` / ``best_flat`` int64 [P] and ``best_patch`` fp32 [P, Cs]; ``proto_scale`` int32 [P] names every prototype's
+    channel block.  The rule is in include/spx_hip.h; ``push.PushTable.merge`` is the checked form."""
+    lib = _lib.load()
+    B, P = values.shape
+    C_, HW = int(conv_features.shape[1]), int(conv_features.shape[2]) * int(conv_features.shape[3])
+    _lib.check(lib.spx_push_merge(_lib.ptr(indices), _lib.ptr(values), _lib.ptr(conv_features), _x_dtype_code(conv_features), B, P,
+                                  C_, HW, int(best_patch.shape[1]), _lib.ptr(proto_scale), int(image0), _lib.ptr(best_value),
+                                  _lib.ptr(best_image), _lib.ptr(best_flat), _lib.ptr(best_patch), _lib.stream_ptr()))
+
+
 def upsample_argext(src: torch.Tensor, size: Tuple[int, int], largest: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """(indices int64 [N,H,W], values f32 [N,H,W]) of ``F.interpolate(src, size, mode="bilinear",
     align_corners=False)`` reduced with argmin (``largest=False``) / argmax over the channels, fused: the upsampled

@@ -189,7 +189,11 @@ class _PrototypeBankMixin:
         ``labels_for_grid((H, W))`` returns the label map [B, H, W] at the latent resolution (the grid is only known after
         the backbone has run).  Returns None when the fused kernel does not apply (MSC list input, a
         prototype_class_identity that is not one-hot, features off the GPU): the caller then reduces the written map."""
-        conv = self.conv_features(x)
+        return self.push_min_from_conv(self.conv_features(x), labels_for_grid, void_class=void_class, max_dist=max_dist)
+
+    def push_min_from_conv(self, conv, labels_for_grid, void_class=None, max_dist: float = 1e10):
+        """``push_min_distances`` on features that are already computed (the single-pass push encodes a run of images once and
+        keeps the features for the gather)."""
         if isinstance(conv, list) or not conv.is_cuda:
             return None
         self._check_fusable()

@@ -6,6 +6,10 @@ Mirrors the numerical part of segmentation/push_multiscale_optimization.py (line
 (``push_box_tables``, the kernel behind ``pushbox.push_bounding_boxes``); every image and plot dump and the class-restricted
 threshold ``threshold_gt`` (used for a PNG crop only, never stored) are visualisation and are not part of this package.
 
+``push_prototypes_multiscale(batch_size=...)`` runs the same push in ONE pass over the data set (``push_single_pass``): images
+are encoded in batches and a ``PushTable`` on the device keeps every prototype's running winner and its feature vector
+(spx_push_merge), so no image is encoded twice and the loop never synchronises.
+
 Dataset protocol (image decoding / normalisation is the data layer, out of scope): ``len(dataset)`` and
 ``dataset[i] -> (image, target)`` with ``image`` a normalised float tensor [3, h, w] and ``target`` an
 integer label map [h, w] (0 = void, 1..K), optionally ``dataset.convert_targets``.  For the box tables the target's own
@@ -21,8 +25,9 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _lib
 from ._lib import SpxError
-from .functional import argmin_over_images, push_masked_argmin
+from .functional import argmin_over_images, push_masked_argmin, push_merge
 from .utils import resize_label
 
 
@@ -153,23 +158,155 @@ def commit_push(ppnet, patches: Sequence[np.ndarray], root_dir: Optional[os.Path
     return dup
 
 
+class PushTable:
+    """The running winner of every prototype on the device (spx_push_merge), the push's counterpart of ``prune.NearestTable``:
+    ``best_value`` fp32 [P] (+inf = nothing merged), ``best_image`` int64 [P] (global image index, -1), ``best_flat`` int64 [P]
+    (flat latent index) and ``best_patch`` fp32 [P, Cs] (the winner's feature vector, gathered while its image's features were
+    on the device).  Batches are merged in increasing image order; a later image replaces the winner only with a strictly
+    smaller value, so the final state is ``argmin(dim=0)`` over all images with the lowest image on ties."""
+
+    def __init__(self, P: int, Cs: int, device):
+        if int(P) < 1 or int(Cs) < 1:
+            raise SpxError(f"a push table needs P >= 1 and Cs >= 1 (got P={P}, Cs={Cs})")
+        self.P, self.Cs = int(P), int(Cs)
+        self.best_value = torch.full((self.P,), float("inf"), dtype=torch.float32, device=device)
+        self.best_image = torch.full((self.P,), -1, dtype=torch.int64, device=device)
+        self.best_flat = torch.zeros((self.P,), dtype=torch.int64, device=device)
+        self.best_patch = torch.zeros((self.P, self.Cs), dtype=torch.float32, device=device)
+        self.next_image = 0                                   # host side: the first image index a later batch may start at
+
+    def check(self, idx: torch.Tensor, val: torch.Tensor, conv: torch.Tensor, proto_scale: torch.Tensor, image0: int) -> int:
+        """Shapes, dtypes, contiguity and image order of one batch (host integers only, no sync).  Returns B."""
+        if val.dim() != 2 or val.shape[1] != self.P:
+            raise SpxError(f"candidates for {tuple(val.shape)[-1] if val.dim() else 0} prototypes, table holds {self.P}")
+        B = int(val.shape[0])
+        if B < 1 or tuple(idx.shape) != (B, self.P):
+            raise SpxError(f"indices {tuple(idx.shape)} / values {tuple(val.shape)} must both be [B >= 1, {self.P}]")
+        if idx.dtype != torch.int64 or val.dtype != torch.float32:
+            raise SpxError(f"indices must be int64 and values float32 (got {idx.dtype}, {val.dtype})")
+        if conv.dim() != 4 or conv.shape[0] != B or conv.dtype not in (torch.bfloat16, torch.float32):
+            raise SpxError(f"features must be bfloat16 or float32 [{B}, C, H, W], got {conv.dtype} {tuple(conv.shape)}")
+        if conv.shape[1] < self.Cs or conv.shape[2] * conv.shape[3] < 1:
+            raise SpxError(f"features {tuple(conv.shape)} hold no block of {self.Cs} channels / no pixel")
+        if tuple(proto_scale.shape) != (self.P,) or proto_scale.dtype != torch.int32:
+            raise SpxError(f"proto_scale must be int32 [{self.P}], got {proto_scale.dtype} {tuple(proto_scale.shape)}")
+        for name, t in (("indices", idx), ("values", val), ("features", conv), ("proto_scale", proto_scale)):
+            if not t.is_contiguous():
+                raise SpxError(f"{name} must be contiguous")
+        if int(image0) < self.next_image:
+            raise SpxError(f"batches must arrive in increasing image order: image0 = {int(image0)} after image {self.next_image - 1}")
+        return B
+
+    def merge(self, idx: torch.Tensor, val: torch.Tensor, conv: torch.Tensor, proto_scale: torch.Tensor, image0: int) -> None:
+        """Merge the minima ``idx`` / ``val`` [B, P] of images image0 .. image0 + B - 1 and gather the new winners' feature
+        vectors from ``conv`` [B, C, H, W]; ``proto_scale`` int32 [P] = the channel block of every prototype."""
+        B = self.check(idx, val, conv, proto_scale, image0)
+        for name, t in (("indices", idx), ("values", val), ("features", conv), ("proto_scale", proto_scale),
+                        ("the push table", self.best_value)):
+            _lib.require_gpu(t, name)
+        push_merge(idx, val, conv, proto_scale, int(image0), self.best_value, self.best_image, self.best_flat, self.best_patch)
+        self.next_image = int(image0) + B
+
+    def to_host(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(best_image int64 [P], best_flat int64 [P], best_patch fp32 [P, Cs]) on the host, in ONE device-to-host copy."""
+        P, Cs = self.P, self.Cs
+        words = torch.cat([self.best_image.view(torch.int32), self.best_flat.view(torch.int32),
+                           self.best_patch.view(torch.int32).reshape(-1)]).cpu()
+        return (words[: 2 * P].view(torch.int64), words[2 * P : 4 * P].view(torch.int64),
+                words[4 * P :].view(torch.float32).reshape(P, Cs))
+
+
+def proto_scale_table(P: int, S: int) -> List[int]:
+    """Channel block of every prototype by the reference's rule ``p // (P // S)`` (push_multiscale_optimization.py:166).  When S
+    does not divide P the rule names blocks that do not exist: refused here, before any image is encoded."""
+    if S < 1 or P < S:
+        raise SpxError(f"{P} prototypes cannot be spread over {S} scales")
+    table = [p // (P // S) for p in range(P)]
+    if table[-1] >= S:
+        raise SpxError(f"the push's rule p // (P // S) puts prototype {P - 1} in channel block {table[-1]} of {S}: "
+                       f"{P} prototypes are not a multiple of {S} scales")
+    return table
+
+
+def push_run_minima(net, conv: torch.Tensor, labels: torch.Tensor, void_class: Optional[int], max_dist: float = 1e10):
+    """Device step 1 of the single-pass push: (indices int64 [B, P], values fp32 [B, P]) of a run's class-masked minima, taken
+    inside the distance kernel (the cached keys of ``push_min_distances``); a class identity that is not one-hot takes the
+    written map and ``push_masked_argmin``, as ``compute_distances`` does."""
+    out = net.push_min_from_conv(conv, lambda hw: labels, void_class=void_class, max_dist=max_dist)
+    if out is not None:
+        return out
+    _, distances = net.forward_from_conv_features(conv, return_activations=False)
+    return push_masked_argmin(distances, labels, net.prototype_class_identity, void_class=void_class, max_dist=max_dist)
+
+
+def push_run_merge(table: PushTable, idx: torch.Tensor, val: torch.Tensor, conv: torch.Tensor, proto_scale: torch.Tensor,
+                   image0: int) -> None:
+    """Device step 2 of the single-pass push: one ``PushTable.merge``."""
+    table.merge(idx, val, conv, proto_scale, image0)
+
+
 @torch.no_grad()
-def push_box_tables(best: torch.Tensor, list_min_patch: Sequence[torch.Tensor], dataset, ppnet,
-                    device: Optional[str] = None, q: float = 0.95, add_margin: int = 5) -> Tuple[np.ndarray, np.ndarray]:
+def push_single_pass(dataset, ppnet, batch_size: int = 8, void_class: Optional[int] = 0, image_range: Optional[range] = None,
+                     device: Optional[str] = None) -> PushTable:
+    """The push's scan in one pass over ``image_range`` (default: the whole data set): runs of consecutive, equally sized
+    images (``prune._batches``) are encoded ``batch_size`` at a time, their minima are taken inside the distance kernel and
+    merged into a ``PushTable`` together with the winners' feature vectors - no [N, P] value table, no per-image index list,
+    no second encoding of the winning images, no host sync inside the loop.  Image indices in the table are GLOBAL dataset
+    indices."""
+    from .prune import _batches
+
+    net = ppnet.module if hasattr(ppnet, "module") else ppnet
+    if int(batch_size) < 1:
+        raise SpxError(f"batch_size = {batch_size} must be positive")
+    net.eval()
+    dev = torch.device(device or str(net.prototype_vectors.device))
+    P, S, Cs = net.num_prototypes, net.num_scales, int(net.prototype_shape[1])
+    proto_scale = torch.tensor(proto_scale_table(P, S), dtype=torch.int32).to(dev)
+    rng = image_range if image_range is not None else range(len(dataset))
+    convert = getattr(dataset, "convert_targets", None)
+    table = PushTable(P, Cs, dev)
+    for run in _batches(dataset, rng, int(batch_size)):
+        # uploaded image by image and stacked on the device: one pageable copy of the whole stacked run measured 5 GB/s
+        # against 23 .. 55 GB/s for its images one by one, and the host-side stack cost as much again (profiles/push_single_pass_summary.md)
+        x = torch.stack([(img if img.dim() == 3 else img[0]).to(dev) for _, img, _ in run])
+        conv = net.conv_features(x)
+        if isinstance(conv, list):
+            raise SpxError("the single-pass push needs one feature map per image (MSC list input is not supported)")
+        if conv.dim() != 4 or conv.shape[1] != S * Cs:
+            raise SpxError(f"features {tuple(conv.shape)} are not [B, {S} x {Cs}, H, W]")
+        conv = conv.detach().contiguous()
+        H, W = int(conv.shape[2]), int(conv.shape[3])
+        labels = torch.stack([resize_label(np.asarray(convert(t) if convert is not None else t), (W, H)) for _, _, t in run])
+        idx, val = push_run_minima(net, conv, labels, void_class)
+        push_run_merge(table, idx, val, conv, proto_scale, run[0][0])
+    return table
+
+
+@torch.no_grad()
+def push_box_tables(best: torch.Tensor, list_min_patch: Optional[Sequence[torch.Tensor]], dataset, ppnet,
+                    device: Optional[str] = None, q: float = 0.95, add_margin: int = 5,
+                    flat: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray]:
     """(proto_rf_boxes, proto_bound_boxes), int64 [P, 6] = [image index, h0, h1, w0, w1, class] of every prototype's winning
     patch (push_multiscale_optimization.py:254-321, 416-497), on the model as it is BEFORE the bank is overwritten.
 
     The winners' images and flat indices come to the host in one copy; each winning image is encoded once and its labels are
     uploaded once (the reference re-runs the backbone once per prototype); ``distance_2_similarity`` runs on the channels of
-    that image's winners only; the thresholds and the crops are ``pushbox.push_bounding_boxes``."""
+    that image's winners only; the thresholds and the crops are ``pushbox.push_bounding_boxes``.
+
+    ``flat`` (int64 [P], the winners' flat latent indices, as the single-pass push keeps them) replaces the per-image index
+    list ``list_min_patch``, which may then be None."""
     from .metrics import prototype_classes
     from .pushbox import push_bounding_boxes
 
     device = device or str(ppnet.prototype_vectors.device)
     P = ppnet.num_prototypes
-    best = torch.as_tensor(best).to(device)
-    flat = torch.cat(list(list_min_patch), dim=0).to(device)[best, torch.arange(P, device=device)]
-    host = torch.stack([best, flat]).cpu()                                   # the one device-to-host copy of the winners
+    if flat is None:
+        best = torch.as_tensor(best).to(device)
+        flat = torch.cat(list(list_min_patch), dim=0).to(device)[best, torch.arange(P, device=device)]
+        host = torch.stack([best, flat]).cpu()                               # the one device-to-host copy of the winners
+    else:
+        flat = torch.as_tensor(flat).to(torch.int64)
+        host = torch.stack([torch.as_tensor(best).to(device=flat.device, dtype=torch.int64), flat]).cpu()
     img_of, flat_of = host[0].tolist(), host[1].tolist()
     cls_of = prototype_classes(ppnet.prototype_class_identity).tolist()
     by_image: Dict[int, List[int]] = {}
@@ -236,6 +373,7 @@ def push_prototypes_multiscale(
     boxes: bool = False,
     epoch_number: Optional[int] = None,
     proto_bound_boxes_filename_prefix: Optional[str] = None,
+    batch_size: Optional[int] = None,
     **_ignored,
 ):
     """Numerical part of push_multiscale_optimization.py:193-338 (the image / plot dump arguments are accepted and ignored).
@@ -252,7 +390,13 @@ def push_prototypes_multiscale(
     (value, global image index) - the reference's lowest-image tie-break (:137) - the winning feature vectors are
     assembled with one sum all-reduce (each row has exactly one contributor), and EVERY rank commits the same bank,
     de-dup and pruning; rank 0 alone writes ``unique_prototypes.json``.  Returns (best image per prototype [P] as GLOBAL
-    image indices, the local shard's per-image flat indices, dropped duplicates)."""
+    image indices, the local shard's per-image flat indices, dropped duplicates).
+
+    ``batch_size`` (an integer; None keeps the path above exactly) runs the single-pass push (``push_single_pass``): runs of
+    equally sized images are encoded ``batch_size`` at a time, every image exactly once, the winners and their feature
+    vectors are kept in a ``PushTable`` on the device, and one device-to-host copy brings them for the commit.  The second
+    entry of the result is then the winners' flat latent indices, int64 [P], instead of the per-image index list; under a
+    sharded push every rank makes the one pass over its shard and the same two collectives follow."""
     from . import dp
 
     net = prototype_network_parallel
@@ -268,6 +412,27 @@ def push_prototypes_multiscale(
     if want_boxes and world > 1:
         raise SpxError(f"push bounding boxes are not available under a sharded push ({world} ranks): run the push with boxes in "
                        "one process, or drop boxes=True / proto_bound_boxes_filename_prefix")
+    if batch_size is not None:
+        rng = dp.shard_range(len(dataset), rank, world) if world > 1 else range(len(dataset))
+        if world == 1 and len(rng) == 0:
+            raise SpxError("the push needs at least one image")
+        table = push_single_pass(dataset, net, batch_size=batch_size, void_class=0, image_range=rng, device=device)
+        if world == 1:
+            best, flat = table.best_image, table.best_flat
+            best_host, flat_host, patch_host = table.to_host()        # the push's one device-to-host copy
+            tables = push_box_tables(best_host, None, dataset, net, device=device, flat=flat_host) if want_boxes else None
+            patches = patch_host.numpy().reshape(tuple(net.prototype_shape))
+        else:                                                         # an empty shard keeps +inf and never wins
+            best, _, flat = dp.reduce_push_candidates(table.best_image, table.best_value, table.best_flat, 0, group=group)
+            owner = (best >= rng.start) & (best < rng.stop)
+            full = dp.gather_push_patches(table.best_patch, owner, group=group)        # [P, Cs], identical on every rank
+            tables = None
+            patches = full.cpu().numpy().reshape(tuple(net.prototype_shape))
+        dup = commit_push(net, patches, root_dir_for_saving_prototypes if rank == 0 else None, log=log)
+        if tables is not None and None not in (root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number):
+            save_box_tables(tables[0], tables[1], root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number)
+        log("\tpush time: \t{0}".format(time.time() - start))
+        return (best, flat, dup) if tables is None else (best, flat, dup, tables[0], tables[1])
     if world == 1:
         best, tot_idx = min_across_dataset(dataset, net, num_classes, void_class=0, device=device)
         tables = push_box_tables(best, tot_idx, dataset, net, device=device) if want_boxes else None
