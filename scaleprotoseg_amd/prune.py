@@ -32,6 +32,7 @@ import torch
 from . import _lib
 from ._lib import SpxError
 from .functional import prune_footprint, prune_nearest_from_features, prune_nearest_from_map
+from .scan import batches, dp_world, encode_run, scan_range, unwrap
 from .utils import resize_label
 
 MAX_K = 64
@@ -141,30 +142,6 @@ class NearestTable:
                           self.cell.long()], dim=2)
 
 
-def _batches(dataset, rng: range, batch_size: int):
-    """Runs of consecutive images of equal image and label size, at most ``batch_size`` long (image order kept)."""
-    run, shape = [], None
-    for i in rng:
-        img, target = dataset[i]
-        t = np.asarray(target)
-        s = (tuple(img.shape), t.shape)
-        if run and (s != shape or len(run) == batch_size):
-            yield run
-            run = []
-        run.append((i, img, t))
-        shape = s
-    if run:
-        yield run
-
-
-def _dp_world(group) -> Tuple[int, int]:
-    import torch.distributed as dist
-
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank(group), dist.get_world_size(group)
-    return 0, 1
-
-
 @torch.no_grad()
 def find_k_nearest_patches_to_prototypes(
     dataset,
@@ -189,7 +166,7 @@ def find_k_nearest_patches_to_prototypes(
     merged with one all-gather: every rank returns the single-process result."""
     from . import dp
 
-    net = ppnet.module if hasattr(ppnet, "module") else ppnet
+    net = unwrap(ppnet)
     if not 1 <= int(k) <= MAX_K:
         raise SpxError(f"k = {k} outside 1..{MAX_K}")
     if batch_size < 1:
@@ -197,31 +174,23 @@ def find_k_nearest_patches_to_prototypes(
     net.eval()
     dev = torch.device(device or str(net.prototype_vectors.device))
     _lib.require_gpu(dev, "the model")
-    rank, world = _dp_world(group)
-    if image_range is not None:
-        rng, world = image_range, 1
-    else:
-        rng = dp.shard_range(len(dataset), rank, world) if world > 1 else range(len(dataset))
+    rank, world = dp_world(group) if image_range is None else (0, 1)
     P = net.num_prototypes
     target_class = net.prototype_class_identity.detach().cpu().argmax(dim=1).to(torch.int32).to(dev)
     void_label = _NO_VOID if void_class is None else int(void_class)
-    convert = getattr(dataset, "convert_targets", None)
     table = NearestTable(P, k, dev)
-    for run in _batches(dataset, rng, batch_size):
-        x = torch.stack([img if img.dim() == 3 else img[0] for _, img, _ in run]).to(dev)
-        conv = net.conv_features(x)
-        if isinstance(conv, list):
-            raise SpxError("multi-scale (MSC) list features: the nearest patch of a prototype is ambiguous across the inputs")
+    for run in batches(dataset, scan_range(dataset, rank, world, image_range), batch_size):
+        conv, targets = encode_run(net, dataset, run, dev,
+                                   "multi-scale (MSC) list features: the nearest patch of a prototype is ambiguous across the inputs")
         net._check_fusable()
         H, W = int(conv.shape[2]), int(conv.shape[3])
-        targets = [np.asarray(convert(t) if convert is not None else t).astype(np.int64) for _, _, t in run]
         latent = torch.stack([resize_label(t, (W, H)) for t in targets])
         if fused:
             keys = prune_nearest_from_features(conv, net.prototype_vectors, net._layout(1), latent, void_label=void_label)
         else:
             dist_map = net._scale_l2_convolution(conv)
             keys = prune_nearest_from_map(dist_map, latent, void_label=void_label)
-        full = torch.from_numpy(np.stack(targets) - 1).to(device=dev, dtype=torch.int32)
+        full = torch.from_numpy(np.stack(targets).astype(np.int64) - 1).to(device=dev, dtype=torch.int32)
         label, box = prune_footprint(full, keys, (H, W), target_class)
         table.merge(keys, label, box, W, run[0][0])
     packed = table.packed()
@@ -248,7 +217,7 @@ def prune_prototypes(
     (``ppnet.prune_prototypes``).  Returns (prune_info int64 [n, 2] of (prototype, class), prototypes_to_keep).  With
     ``root_dir`` (rank 0 only under data parallelism) writes ``prune_info.npy`` and ``prototypes_to_keep.json`` there; the
     list loads through ``checkpoint.load_reference_state_dict(..., unique_prototypes=path)``."""
-    net = ppnet.module if hasattr(ppnet, "module") else ppnet
+    net = unwrap(ppnet)
     result = find_k_nearest_patches_to_prototypes(dataset, net, k, batch_size=batch_size, void_class=void_class, group=group,
                                                   fused=fused, log=log)
     P0 = net.num_prototypes
@@ -260,7 +229,7 @@ def prune_prototypes(
         if pruned else np.zeros((0, 2), dtype=np.int64)
     net.prune_prototypes(pruned)
     keep = sorted(set(range(P0)) - set(pruned))
-    if root_dir is not None and _dp_world(group)[0] == 0:
+    if root_dir is not None and dp_world(group)[0] == 0:
         os.makedirs(root_dir, exist_ok=True)
         np.save(os.path.join(root_dir, "prune_info.npy"), prune_info)
         with open(os.path.join(root_dir, "prototypes_to_keep.json"), "w") as fp:

@@ -28,6 +28,7 @@ import torch
 from . import _lib
 from ._lib import SpxError
 from .functional import argmin_over_images, push_masked_argmin, push_merge
+from .scan import batches, converted, dp_world as _dp_world, encode_run, image_batch, scan_range, unwrap
 from .utils import resize_label
 
 
@@ -48,9 +49,8 @@ def compute_distances(
     passes are one HIP reduction (spx_push_argmin)."""
     device = device or str(ppnet.prototype_vectors.device)
     ppnet.eval()
-    x = img.unsqueeze(0).to(device) if img.dim() == 3 else img.to(device)
-    if dataset is not None and getattr(dataset, "convert_targets", None) is not None:
-        target = dataset.convert_targets(target)
+    x = image_batch(img, device)
+    target = converted(dataset, target)
     fused = getattr(ppnet, "push_min_distances", None)
     if fused is not None:
         # the minimum is taken inside the distance kernel: the [1, P, H, W] map is never written (spx_dist_push_min)
@@ -79,9 +79,8 @@ def min_across_dataset(
     ``image_range`` restricts the scan to a shard of the image list (data-parallel push, see dp.py); the
     returned image ids are then positions inside the shard.  ``return_values=True`` appends the per-image minima
     ([n_images, P] fp32) the sharded reduction needs."""
-    rng = image_range if image_range is not None else range(len(dataset))
     list_idx, list_val = [], []
-    for i in rng:
+    for i in scan_range(dataset, image_range=image_range):
         img, target = dataset[i]
         idx, val = compute_distances(ppnet, dataset, img, target, num_classes, void_class=void_class, device=device)
         list_idx.append(idx)
@@ -91,34 +90,39 @@ def min_across_dataset(
     return (best, list_idx, tot) if return_values else (best, list_idx)
 
 
-def _winning_patches(best: Sequence[int], list_min_patch, dataset, ppnet, device, image_offset: int = 0,
+def _winners(best, list_min_patch: Optional[Sequence[torch.Tensor]], flat=None) -> torch.Tensor:
+    """int64 [2, P]: the winners' images and flat latent indices; the latter as given, else ``list_min_patch[best[p]][0, p]``."""
+    if flat is None:
+        tot = torch.cat(list(list_min_patch), dim=0)
+        best = torch.as_tensor(best).to(tot.device)
+        flat = tot[best, torch.arange(tot.shape[1], device=tot.device)]
+    flat = torch.as_tensor(flat).to(torch.int64)
+    return torch.stack([torch.as_tensor(best).to(device=flat.device, dtype=torch.int64), flat])
+
+
+def _by_winning_image(best: Sequence[int], only: Optional[Sequence[bool]] = None) -> Dict[int, List[int]]:
+    """Winning image -> its prototypes in increasing order (those outside ``only`` left out), images as first met."""
+    by_image: Dict[int, List[int]] = {}
+    for p, i in enumerate(best):
+        if only is None or only[p]:
+            by_image.setdefault(int(i), []).append(p)
+    return by_image
+
+
+@torch.no_grad()
+def _winning_patches(best: Sequence[int], flat: Sequence[int], dataset, ppnet, device, image_offset: int = 0,
                      only: Optional[Sequence[bool]] = None) -> torch.Tensor:
-    """[P, Cs] feature vectors of the winning latent pixels (rows outside ``only`` stay zero).  Each winning image is
-    encoded once, the reference re-runs the backbone once per prototype."""
+    """[P, Cs] feature vectors of the winning latent pixels (rows outside ``only`` stay zero); ``best`` / ``flat`` are the
+    winners' images and flat indices as host integers.  Each winning image is encoded once, the reference
+    re-runs the backbone once per prototype."""
     P, S = ppnet.num_prototypes, ppnet.num_scales
-    per_scale = P // S
-    conv_cache: Dict[int, torch.Tensor] = {}
-    out = None
-    for p in range(P):
-        if only is not None and not bool(only[p]):
-            continue
-        s = p // per_scale
-        i = int(best[p])
-        if i not in conv_cache:
-            img, _ = dataset[image_offset + i]
-            x = img.unsqueeze(0).to(device) if img.dim() == 3 else img.to(device)
-            conv_cache[i] = ppnet.conv_features(x)
-        conv = conv_cache[i]
+    out = torch.zeros((P, int(ppnet.prototype_shape[1])), dtype=torch.float32, device=device)
+    for i, protos in _by_winning_image(best, only).items():
+        conv = ppnet.conv_features(image_batch(dataset[image_offset + i][0], device))
         _, C, H, W = conv.shape
         cv = conv.view(S, C // S, H, W)
-        flat = int(list_min_patch[i][:, p].item())
-        r, c = flat // W, flat % W
-        if out is None:
-            out = torch.zeros((P, C // S), dtype=torch.float32, device=conv.device)
-        out[p] = cv[s, :, r, c].detach().float()
-    if out is None:
-        cs = int(ppnet.prototype_shape[1])
-        out = torch.zeros((P, cs), dtype=torch.float32, device=device)
+        for p in protos:
+            out[p] = cv[p // (P // S), :, flat[p] // W, flat[p] % W].detach().float()
     return out
 
 
@@ -133,7 +137,8 @@ def global_min(
 ) -> List[np.ndarray]:
     """Feature vector [Cs,1,1] of every prototype's winning latent pixel (push_multiscale_optimization.py:140-190)."""
     device = device or str(ppnet.prototype_vectors.device)
-    rows = _winning_patches(proto_min_dist.tolist(), list_min_patch, dataset, ppnet, device, image_offset).cpu().numpy()
+    best, flat = _winners(proto_min_dist, list_min_patch).tolist()       # the one device-to-host copy of the winners
+    rows = _winning_patches(best, flat, dataset, ppnet, device, image_offset).cpu().numpy()
     return [rows[p].reshape(-1, 1, 1) for p in range(rows.shape[0])]
 
 
@@ -156,6 +161,13 @@ def commit_push(ppnet, patches: Sequence[np.ndarray], root_dir: Optional[os.Path
         with open(os.path.join(root_dir, "unique_prototypes.json"), "w") as fp:
             json.dump([int(i) for i in sorted(unique_index)], fp)
     return dup
+
+
+def _winners_to_host(image: torch.Tensor, flat: torch.Tensor, patch: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(image int64 [P], flat int64 [P], patch fp32 [P, Cs]) on the host, in ONE device-to-host copy."""
+    P = image.shape[0]
+    words = torch.cat([image.view(torch.int32), flat.view(torch.int32), patch.view(torch.int32).reshape(-1)]).cpu()
+    return words[: 2 * P].view(torch.int64), words[2 * P : 4 * P].view(torch.int64), words[4 * P :].view(torch.float32).reshape(patch.shape)
 
 
 class PushTable:
@@ -209,11 +221,7 @@ class PushTable:
 
     def to_host(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(best_image int64 [P], best_flat int64 [P], best_patch fp32 [P, Cs]) on the host, in ONE device-to-host copy."""
-        P, Cs = self.P, self.Cs
-        words = torch.cat([self.best_image.view(torch.int32), self.best_flat.view(torch.int32),
-                           self.best_patch.view(torch.int32).reshape(-1)]).cpu()
-        return (words[: 2 * P].view(torch.int64), words[2 * P : 4 * P].view(torch.int64),
-                words[4 * P :].view(torch.float32).reshape(P, Cs))
+        return _winners_to_host(self.best_image, self.best_flat, self.best_patch)
 
 
 def proto_scale_table(P: int, S: int) -> List[int]:
@@ -249,34 +257,25 @@ def push_run_merge(table: PushTable, idx: torch.Tensor, val: torch.Tensor, conv:
 def push_single_pass(dataset, ppnet, batch_size: int = 8, void_class: Optional[int] = 0, image_range: Optional[range] = None,
                      device: Optional[str] = None) -> PushTable:
     """The push's scan in one pass over ``image_range`` (default: the whole data set): runs of consecutive, equally sized
-    images (``prune._batches``) are encoded ``batch_size`` at a time, their minima are taken inside the distance kernel and
+    images (``scan.batches``) are encoded ``batch_size`` at a time, their minima are taken inside the distance kernel and
     merged into a ``PushTable`` together with the winners' feature vectors - no [N, P] value table, no per-image index list,
     no second encoding of the winning images, no host sync inside the loop.  Image indices in the table are GLOBAL dataset
     indices."""
-    from .prune import _batches
-
-    net = ppnet.module if hasattr(ppnet, "module") else ppnet
+    net = unwrap(ppnet)
     if int(batch_size) < 1:
         raise SpxError(f"batch_size = {batch_size} must be positive")
     net.eval()
     dev = torch.device(device or str(net.prototype_vectors.device))
     P, S, Cs = net.num_prototypes, net.num_scales, int(net.prototype_shape[1])
     proto_scale = torch.tensor(proto_scale_table(P, S), dtype=torch.int32).to(dev)
-    rng = image_range if image_range is not None else range(len(dataset))
-    convert = getattr(dataset, "convert_targets", None)
     table = PushTable(P, Cs, dev)
-    for run in _batches(dataset, rng, int(batch_size)):
-        # uploaded image by image and stacked on the device: one pageable copy of the whole stacked run measured 5 GB/s
-        # against 23 .. 55 GB/s for its images one by one, and the host-side stack cost as much again (profiles/push_single_pass_summary.md)
-        x = torch.stack([(img if img.dim() == 3 else img[0]).to(dev) for _, img, _ in run])
-        conv = net.conv_features(x)
-        if isinstance(conv, list):
-            raise SpxError("the single-pass push needs one feature map per image (MSC list input is not supported)")
+    for run in batches(dataset, scan_range(dataset, image_range=image_range), int(batch_size)):
+        conv, targets = encode_run(net, dataset, run, dev,
+                                   "the single-pass push needs one feature map per image (MSC list input is not supported)")
         if conv.dim() != 4 or conv.shape[1] != S * Cs:
             raise SpxError(f"features {tuple(conv.shape)} are not [B, {S} x {Cs}, H, W]")
         conv = conv.detach().contiguous()
-        H, W = int(conv.shape[2]), int(conv.shape[3])
-        labels = torch.stack([resize_label(np.asarray(convert(t) if convert is not None else t), (W, H)) for _, _, t in run])
+        labels = torch.stack([resize_label(t, (conv.shape[3], conv.shape[2])) for t in targets])
         idx, val = push_run_minima(net, conv, labels, void_class)
         push_run_merge(table, idx, val, conv, proto_scale, run[0][0])
     return table
@@ -300,31 +299,17 @@ def push_box_tables(best: torch.Tensor, list_min_patch: Optional[Sequence[torch.
 
     device = device or str(ppnet.prototype_vectors.device)
     P = ppnet.num_prototypes
-    if flat is None:
-        best = torch.as_tensor(best).to(device)
-        flat = torch.cat(list(list_min_patch), dim=0).to(device)[best, torch.arange(P, device=device)]
-        host = torch.stack([best, flat]).cpu()                               # the one device-to-host copy of the winners
-    else:
-        flat = torch.as_tensor(flat).to(torch.int64)
-        host = torch.stack([torch.as_tensor(best).to(device=flat.device, dtype=torch.int64), flat]).cpu()
-    img_of, flat_of = host[0].tolist(), host[1].tolist()
+    img_of, flat_of = _winners(best, list_min_patch, flat).tolist()      # the one device-to-host copy of the winners
     cls_of = prototype_classes(ppnet.prototype_class_identity).tolist()
-    by_image: Dict[int, List[int]] = {}
-    for p in range(P):
-        by_image.setdefault(int(img_of[p]), []).append(p)
     order, parts = [], []
-    for i in sorted(by_image):
-        protos = by_image[i]
+    for i, protos in sorted(_by_winning_image(img_of).items()):
         img, target = dataset[i]
-        if getattr(dataset, "convert_targets", None) is not None:
-            target = dataset.convert_targets(target)
-        x = img.unsqueeze(0).to(device) if img.dim() == 3 else img.to(device)
-        conv, dist = ppnet.push_forward(x)
+        conv, dist = ppnet.push_forward(image_batch(img, device))
         if isinstance(conv, list):
             raise SpxError("push boxes need one feature map per image (MSC list input is not supported)")
         chans = torch.tensor(protos, dtype=torch.int64, device=dist.device)
         act = ppnet.distance_2_similarity(dist[:, chans]).float()            # [1, winners of this image, h, w]
-        labels = torch.as_tensor(np.ascontiguousarray(target))
+        labels = torch.as_tensor(np.ascontiguousarray(converted(dataset, target)))
         if labels.dim() != 2:
             raise SpxError(f"target of image {i} must be [H, W] (got {tuple(labels.shape)})")
         if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
@@ -355,12 +340,16 @@ def save_box_tables(proto_rf_boxes: np.ndarray, proto_bound_boxes: np.ndarray, r
     return rf_path, box_path
 
 
-def _dp_world(group) -> Tuple[int, int]:
-    import torch.distributed as dist
-
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank(group), dist.get_world_size(group)
-    return 0, 1
+def _two_pass_candidates(dataset, net, rng: range, device, world: int):
+    """The two-pass scan of ``rng``: ((best image as a GLOBAL index, its value, its flat index), each [P], and the per-image
+    index list)."""
+    if len(rng) == 0 and world > 1:                                    # more ranks than images: this rank never wins
+        zero = torch.zeros(net.num_prototypes, dtype=torch.int64, device=device)
+        return (zero, torch.full_like(zero, float("inf"), dtype=torch.float32), zero), []
+    # (an empty data set at one rank fails in min_across_dataset, as it always has)
+    best, tot_idx, tot_val = min_across_dataset(dataset, net, net.num_classes, void_class=0, device=device, image_range=rng,
+                                                return_values=True)     # tot_val: [n_local, P]
+    return (best + rng.start, tot_val[best, torch.arange(tot_val.shape[1], device=tot_val.device)], _winners(best, tot_idx)[1]), tot_idx
 
 
 def push_prototypes_multiscale(
@@ -377,93 +366,59 @@ def push_prototypes_multiscale(
     **_ignored,
 ):
     """Numerical part of push_multiscale_optimization.py:193-338 (the image / plot dump arguments are accepted and ignored).
+    Returns (best image per prototype [P] as GLOBAL image indices, this rank's per-image flat indices, dropped duplicates).
+
+    One flow for every form: this rank's shard of the image list (``dp.shard_range``; all of it at one rank, the reference's
+    case) is scanned into one candidate per prototype, the candidates are combined with one all-gather and a lexicographic
+    minimum on (value, global image index) - the reference's lowest-image tie-break (:137) - the winning feature vectors are
+    assembled with one sum all-reduce (each row has exactly one contributor; both collectives hand back their input at one
+    rank), and EVERY rank commits the same bank, de-dup and pruning; rank 0 alone writes ``unique_prototypes.json``.  The
+    data-parallel form is new capability (SURVEY.md 8e "Push").
+
+    ``batch_size=None`` scans in the reference's two passes (``min_across_dataset``, then the winning images once more).  An
+    integer runs the single-pass scan (``push_single_pass``): runs of equally sized images are encoded ``batch_size`` at a time,
+    every image exactly once, the winners and their feature vectors are kept in a ``PushTable`` on the device, and one
+    device-to-host copy brings them for the commit.  The second entry of the result is then the winners' flat latent indices,
+    int64 [P], instead of the per-image index list.
 
     With ``boxes=True``, or when ``proto_bound_boxes_filename_prefix`` is given, the reference's ``proto_rf_boxes`` and
     ``proto_bound_boxes`` tables (int64 [P, 6], ``push_box_tables``) are computed before the bank is overwritten and appended
-    to the result: (best, flat indices, dropped duplicates, proto_rf_boxes, proto_bound_boxes).  With
-    ``root_dir_for_saving_prototypes``, the prefix and ``epoch_number`` all set they are also saved under the reference's names
-    (``save_box_tables``).  Not under a sharded push: with more than one rank this raises ``SpxError``.
-
-    Data-parallel form (SURVEY.md 8e "Push"; new capability, the reference is single-process): when
-    ``torch.distributed`` is initialised with more than one rank, every rank scans a contiguous shard of the image list
-    (``dp.shard_range``), the per-prototype winners are combined with one all-gather and a lexicographic minimum on
-    (value, global image index) - the reference's lowest-image tie-break (:137) - the winning feature vectors are
-    assembled with one sum all-reduce (each row has exactly one contributor), and EVERY rank commits the same bank,
-    de-dup and pruning; rank 0 alone writes ``unique_prototypes.json``.  Returns (best image per prototype [P] as GLOBAL
-    image indices, the local shard's per-image flat indices, dropped duplicates).
-
-    ``batch_size`` (an integer; None keeps the path above exactly) runs the single-pass push (``push_single_pass``): runs of
-    equally sized images are encoded ``batch_size`` at a time, every image exactly once, the winners and their feature
-    vectors are kept in a ``PushTable`` on the device, and one device-to-host copy brings them for the commit.  The second
-    entry of the result is then the winners' flat latent indices, int64 [P], instead of the per-image index list; under a
-    sharded push every rank makes the one pass over its shard and the same two collectives follow."""
+    to the result.  With ``root_dir_for_saving_prototypes``, the prefix and ``epoch_number`` all set they are also saved under
+    the reference's names (``save_box_tables``).  Not under a sharded push: with more than one rank this raises ``SpxError``."""
     from . import dp
 
-    net = prototype_network_parallel
-    if hasattr(net, "module"):
-        net = net.module
+    net = unwrap(prototype_network_parallel)
     net.eval()
     log("\tpush")
     start = time.time()
-    num_classes = net.num_classes
     device = device or str(net.prototype_vectors.device)
     rank, world = _dp_world(group)
     want_boxes = bool(boxes) or proto_bound_boxes_filename_prefix is not None
     if want_boxes and world > 1:
         raise SpxError(f"push bounding boxes are not available under a sharded push ({world} ranks): run the push with boxes in "
                        "one process, or drop boxes=True / proto_bound_boxes_filename_prefix")
+    rng = scan_range(dataset, rank, world)
+    # this rank's candidates (best image as a GLOBAL index, value, flat index), each [P]; an empty shard never wins
     if batch_size is not None:
-        rng = dp.shard_range(len(dataset), rank, world) if world > 1 else range(len(dataset))
         if world == 1 and len(rng) == 0:
             raise SpxError("the push needs at least one image")
         table = push_single_pass(dataset, net, batch_size=batch_size, void_class=0, image_range=rng, device=device)
-        if world == 1:
-            best, flat = table.best_image, table.best_flat
-            best_host, flat_host, patch_host = table.to_host()        # the push's one device-to-host copy
-            tables = push_box_tables(best_host, None, dataset, net, device=device, flat=flat_host) if want_boxes else None
-            patches = patch_host.numpy().reshape(tuple(net.prototype_shape))
-        else:                                                         # an empty shard keeps +inf and never wins
-            best, _, flat = dp.reduce_push_candidates(table.best_image, table.best_value, table.best_flat, 0, group=group)
-            owner = (best >= rng.start) & (best < rng.stop)
-            full = dp.gather_push_patches(table.best_patch, owner, group=group)        # [P, Cs], identical on every rank
-            tables = None
-            patches = full.cpu().numpy().reshape(tuple(net.prototype_shape))
-        dup = commit_push(net, patches, root_dir_for_saving_prototypes if rank == 0 else None, log=log)
-        if tables is not None and None not in (root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number):
-            save_box_tables(tables[0], tables[1], root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number)
-        log("\tpush time: \t{0}".format(time.time() - start))
-        return (best, flat, dup) if tables is None else (best, flat, dup, tables[0], tables[1])
-    if world == 1:
-        best, tot_idx = min_across_dataset(dataset, net, num_classes, void_class=0, device=device)
-        tables = push_box_tables(best, tot_idx, dataset, net, device=device) if want_boxes else None
-        patches = global_min(best, tot_idx, dataset, net, device=device)
-        dup = commit_push(net, patches, root_dir_for_saving_prototypes, log=log)
-        if tables is not None and None not in (root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number):
-            save_box_tables(tables[0], tables[1], root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number)
-        log("\tpush time: \t{0}".format(time.time() - start))
-        return (best, tot_idx, dup) if tables is None else (best, tot_idx, dup, tables[0], tables[1])
-
-    P = net.num_prototypes
-    rng = dp.shard_range(len(dataset), rank, world)
-    dev = torch.device(device)
-    ar = torch.arange(P, device=dev)
-    if len(rng) > 0:
-        best_local, tot_idx, tot_val = min_across_dataset(dataset, net, num_classes, void_class=0, device=device, image_range=rng,
-                                                          return_values=True)                    # tot_val: [n_local, P]
-        local_val = tot_val[best_local, ar]
-        local_flat = torch.cat(list(tot_idx), dim=0)[best_local, ar]
-    else:                                                              # more ranks than images: this rank never wins
-        best_local = torch.zeros(P, dtype=torch.int64, device=dev)
-        tot_idx = []
-        local_val = torch.full((P,), float("inf"), dtype=torch.float32, device=dev)
-        local_flat = torch.zeros(P, dtype=torch.int64, device=dev)
-    gimg, _, gflat = dp.reduce_push_candidates(best_local, local_val, local_flat, rng.start, group=group)
-    owner = (gimg >= rng.start) & (gimg < rng.stop)
-    with torch.no_grad():
-        local = _winning_patches((gimg - rng.start).tolist(), tot_idx, dataset, net, device, image_offset=rng.start,
-                                 only=owner.tolist())
-    full = dp.gather_push_patches(local, owner, group=group)           # [P, Cs], identical on every rank
-    patches = full.cpu().numpy().reshape(tuple(net.prototype_shape))
-    dup = commit_push(net, patches, root_dir_for_saving_prototypes if rank == 0 else None, log=log)
+        local = (table.best_image, table.best_value, table.best_flat)
+    else:
+        local, tot_idx = _two_pass_candidates(dataset, net, rng, device, world)
+    best, _, flat = dp.reduce_push_candidates(*local, 0, group=group)                 # global, identical on every rank
+    owner = (best >= rng.start) & (best < rng.stop)
+    if batch_size is not None:
+        patch = table.best_patch
+    else:
+        winners = torch.stack([best - rng.start, flat, owner.to(torch.int64)]).tolist()    # one copy for the second pass
+        patch = _winning_patches(winners[0], winners[1], dataset, net, device, image_offset=rng.start, only=winners[2])
+    full = dp.gather_push_patches(patch, owner, group=group)                                # [P, Cs], identical on every rank
+    best_host, flat_host, patch_host = _winners_to_host(best, flat, full)                  # the single pass's one device-to-host copy
+    tables = push_box_tables(best_host, None, dataset, net, device=device, flat=flat_host) if want_boxes else None
+    dup = commit_push(net, patch_host.numpy().reshape(tuple(net.prototype_shape)), root_dir_for_saving_prototypes if rank == 0 else None,
+                      log=log)
+    if tables is not None and None not in (root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number):
+        save_box_tables(tables[0], tables[1], root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number)
     log("\tpush time: \t{0}".format(time.time() - start))
-    return gimg, tot_idx, dup
+    return (best, flat if batch_size is not None else tot_idx, dup) + (tuple(tables) if tables is not None else ())

@@ -3,7 +3,7 @@ labels, P = 228, S = 4, K = 19, C = 256 fp32 features) against the push's pair a
 same process on the same inputs; each time is the median of --reps event-timed calls after two warm-up calls, divided
 by B (ms per image).
 
-    python tools/probes/prune_time.py [--batches 1,8] [--reps 20]
+    python tools/probes/prune_time.py [--batches 1,8] [--reps 20] [--search N]
 
 Variants per B:
   fused               prune_nearest_from_features (spx_dist_prune_min: the map is never written)
@@ -11,11 +11,16 @@ Variants per B:
   map + push argmin   distance map + push_masked_argmin (the push's class-masked pair, the yardstick)
   footprint + merge   prune_footprint on the 1024 x 2048 labels + NearestTable.merge (k = 6)
   fused step          fused + footprint + merge: what find_k_nearest_patches_to_prototypes runs per batch
-Prints one JSON line per (B, variant)."""
+Prints one JSON line per (B, variant).
+
+--search N times the whole search instead, uploads included: find_k_nearest_patches_to_prototypes (k = 6) over N synthetic host
+images at that shape with the stand-in backbone of push_single_pass_time.py, per batch size: a host clock around the call,
+ending in a device synchronise, one warm-up, then the median (min .. max) of three, and a checksum of the result."""
 import argparse
 import json
 import os
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch  # noqa: E402
@@ -81,11 +86,35 @@ def run(B, reps):
                           "median_ms": round(ms, 4), "ms_per_image": round(ms / B, 4), "reps": reps}), flush=True)
 
 
+def search(n_images, batches):
+    from push_single_pass_time import _Images, _net
+
+    dev = torch.device("cuda:0")
+    net = _net(P, K, S, C // S, dev)
+    data = _Images(n_images, H * 8, W * 8, K)
+    for B in batches:
+        ts = []
+        for r in range(4):                                                   # call 0 is the warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = spx.find_k_nearest_patches_to_prototypes(data, net, 6, batch_size=B, log=lambda *_: None)
+            torch.cuda.synchronize()
+            if r:
+                ts.append(time.perf_counter() - t0)
+        ts.sort()
+        print(json.dumps({"variant": "search", "images": n_images, "B": B, "median_s": round(ts[1], 4), "min_s": round(ts[0], 4),
+                          "max_s": round(ts[2], 4), "checksum": [int(res.image.sum()), int(res.latent.sum()), int(res.label.sum())]}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="1,8")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--search", type=int, default=0, metavar="N")
     args = ap.parse_args()
+    if args.search:
+        return search(args.search, [int(b) for b in args.batches.split(",")])
     for B in (int(b) for b in args.batches.split(",")):
         run(B, args.reps)
 

@@ -134,7 +134,7 @@ def whole_push(n_images, dev, reps=3):
 def stage_times(n_images, dev):
     """Where a single pass spends its wall time: the loop of push_single_pass restated with a device synchronise and a host
     clock after every stage (so the stages cannot overlap, and the sum exceeds the push's own time), summed over all runs."""
-    from scaleprotoseg_amd.prune import _batches
+    from scaleprotoseg_amd.scan import batches
     from scaleprotoseg_amd.utils import resize_label
 
     P, K, S, Cs = 228, 19, 4, 64
@@ -153,7 +153,7 @@ def stage_times(n_images, dev):
                 return time.perf_counter()
 
             with torch.no_grad():
-                for run in _batches(data, range(len(data)), bs):
+                for run in batches(data, range(len(data)), bs):
                     t = time.perf_counter()
                     if host_stack:                                           # the variant the driver does NOT use
                         x = torch.stack([img for _, img, _ in run])
