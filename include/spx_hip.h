@@ -603,6 +603,37 @@ int spx_push_merge(const int64_t* indices, const float* values, const void* x, i
                    int32_t HW, int32_t Cs, const int32_t* proto_scale, int64_t image0, float* best_value, int64_t* best_image,
                    int64_t* best_flat, float* best_patch, void* stream);
 
+/* Explanation maps (additive to ABI 17; segmentation/analysis/sample_activations_prototype.py:71-133,
+ * sample_activations_group.py:72-131): the normalised heat map of an activation plane over one class of an image, and the map of
+ * the slot that dominates each pixel of the class, as one byte per pixel.
+ *   planes, host_strides, u, labels   as spx_overlap_accumulate takes them (labels [N, H, W]: 0 = void, k + 1 = class k)
+ *   heat rows   int32 [R, 3] on the device = (n, c, class k): plane (n, c) over class k.  host_rows: the same table in host
+ *               memory, required: every row is checked on the host (0 <= n < N, 0 <= c < C, k >= 0) and a bad one refuses
+ *               the call before any launch.
+ *   m           labels[n] == k + 1 ? u[n, c] : 0;   lo = min m, hi = max m over the H*W pixels;   d = hi - lo (fp32)
+ *   heat        (uint8) trunc(255 * ((m - lo) / d)), every operation in fp32 and rounded on its own, the division correctly
+ *               rounded: NumPy's np.uint8(255 * ((m - amin) / amax(m - amin))) on float32.  Where d == 0 (a constant plane, a
+ *               class absent from the image) the row is all zeros; NumPy divides 0 by 0 there and its bytes are undefined.
+ * spx_explain_range writes the order-preserving uint32 keys of lo and hi into workspace (8 R bytes, no initialisation needed,
+ * one call at a time per workspace): integer min / max atomics, run-to-run identical.  spx_explain_heat, given the same
+ * arguments and that workspace, writes heat uint8 [R, H, W] and ranges fp32 [R, 2] = (lo, hi).
+ *   dominant rows  int32 [R, 2] on the device = (n, class k), host_rows as above (0 <= n < N, 0 <= k < K)
+ *   dom            labels[n] == k + 1 ? argmax over j of weights[k, j] * u[n, slot_table[k, j]] : 255, the product in fp32, over
+ *                  the slots with a channel in [0, C); the first maximum on ties and a NaN counts as a maximum (np.argmax);
+ *                  the value is the column j of slot_table int32 [K, J]; a class without a slot gives 255 everywhere.
+ *                  weights fp32 [K, J] on the device, or NULL = 1.
+ * spx_explain_dominant writes dom uint8 [R, H, W].  heat and dom may have any alignment; every byte is written exactly once.
+ * Each call enqueues on `stream` only.  Limits: those of spx_overlap_accumulate, R <= 65535. */
+int spx_explain_range(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                      const int32_t* host_rows, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
+                      void* workspace, void* stream);
+int spx_explain_heat(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                     const int32_t* host_rows, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
+                     const void* workspace, uint8_t* heat, float* ranges, void* stream);
+int spx_explain_dominant(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                         const int32_t* host_rows, const int32_t* slot_table, const float* weights, int32_t R, int32_t N, int32_t C,
+                         int32_t K, int32_t J, int32_t h, int32_t w, int32_t H, int32_t W, uint8_t* dom, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,10 @@ Public surface mirrors the reference's module/function names for this path:
     PushTable, push_single_pass                     (the same push in ONE pass over the data set, images encoded in batches:
                                                      running winners and their feature vectors kept on the GPU;
                                                      push_prototypes_multiscale(batch_size=...))
+    ExplanationMaps, activation_heat_maps, dominant_slot_maps
+                                                    (segmentation/analysis/sample_activations_prototype.py:71-133,
+                                                     sample_activations_group.py:72-131: per-slot uint8 heat maps over a
+                                                     class and the map of the dominant slot, one byte per pixel)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -79,6 +83,7 @@ from .push import (  # noqa: F401
     push_prototypes_multiscale,
 )
 from .pushbox import push_bounding_boxes  # noqa: F401
+from .explain import ExplanationMaps, activation_heat_maps, dominant_slot_maps  # noqa: F401
 from .prune import NearestPatches, find_k_nearest_patches_to_prototypes, prune_prototypes  # noqa: F401
 from .utils import projection_simplex_sort, resize_label  # noqa: F401
 

@@ -869,6 +869,66 @@ int spx_push_boxes(const float* planes, const int64_t* host_strides, const void*
                                             H, W, add_margin, rf_boxes, crops, (hipStream_t)stream), who);
 }
 
+#define SPX_EXP_MAX_ROWS 65535
+
+// what the three explanation-map entry points check alike
+static int explain_check(const char* who, const float* planes, const int64_t* st, const void* labels, int32_t label_bytes,
+                         const int32_t* rows, const int32_t* host_rows, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
+                         int32_t W) {
+    if (!labels || !rows || !host_rows) return fail("%s: NULL labels / rows / host rows", who);
+    if (label_bytes != 1 && label_bytes != 4 && label_bytes != 8)
+        return fail("%s: label byte code %d (1 = uint8, 4 = int32, 8 = int64)", who, label_bytes);
+    if (R < 1 || R > SPX_EXP_MAX_ROWS) return fail("%s: %d rows (1..%d)", who, R, SPX_EXP_MAX_ROWS);
+    return overlap_check(who, planes, st, N, C, h, w, H, W, rows);
+}
+static int explain_heat_rows(const char* who, const int32_t* host_rows, int32_t R, int32_t N, int32_t C) {
+    for (int r = 0; r < R; ++r) {
+        const int32_t* q = host_rows + 3 * (size_t)r;
+        if (q[0] < 0 || q[0] >= N || q[1] < 0 || q[1] >= C || q[2] < 0)
+            return fail("%s: row %d = (n %d, c %d, class %d) out of range (N=%d C=%d, class >= 0)", who, r, q[0], q[1], q[2], N, C);
+    }
+    return 0;
+}
+
+int spx_explain_range(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                      const int32_t* host_rows, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
+                      void* workspace, void* stream) {
+    static const char* who = "spx_explain_range";
+    if (!workspace) return fail("%s: NULL workspace", who);
+    if (int e = explain_check(who, planes, host_strides, labels, label_bytes, rows, host_rows, R, N, C, h, w, H, W)) return e;
+    if (int e = explain_heat_rows(who, host_rows, R, N, C)) return e;
+    return hip_status(spx_launch_explain_range(planes, (const long long*)host_strides, labels, label_bytes, rows, R, N, C, h, w, H, W,
+                                               workspace, (hipStream_t)stream), who);
+}
+
+int spx_explain_heat(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                     const int32_t* host_rows, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
+                     const void* workspace, uint8_t* heat, float* ranges, void* stream) {
+    static const char* who = "spx_explain_heat";
+    if (!workspace || !heat || !ranges) return fail("%s: NULL workspace / heat / ranges", who);
+    if (int e = explain_check(who, planes, host_strides, labels, label_bytes, rows, host_rows, R, N, C, h, w, H, W)) return e;
+    if (int e = explain_heat_rows(who, host_rows, R, N, C)) return e;
+    return hip_status(spx_launch_explain_heat(planes, (const long long*)host_strides, labels, label_bytes, rows, R, N, C, h, w, H, W,
+                                              workspace, heat, ranges, (hipStream_t)stream), who);
+}
+
+int spx_explain_dominant(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                         const int32_t* host_rows, const int32_t* slot_table, const float* weights, int32_t R, int32_t N, int32_t C,
+                         int32_t K, int32_t J, int32_t h, int32_t w, int32_t H, int32_t W, uint8_t* dom, void* stream) {
+    static const char* who = "spx_explain_dominant";
+    if (!slot_table || !dom) return fail("%s: NULL slot table / output", who);
+    if (K < 1 || K > SPX_EVAL_MAX_CLASSES || J < 1 || J > SPX_OVL_MAX_SLOTS)
+        return fail("%s: bad sizes (K=%d J=%d; K <= %d, J <= %d)", who, K, J, SPX_EVAL_MAX_CLASSES, SPX_OVL_MAX_SLOTS);
+    if (int e = explain_check(who, planes, host_strides, labels, label_bytes, rows, host_rows, R, N, C, h, w, H, W)) return e;
+    for (int r = 0; r < R; ++r) {
+        const int32_t* q = host_rows + 2 * (size_t)r;
+        if (q[0] < 0 || q[0] >= N || q[1] < 0 || q[1] >= K)
+            return fail("%s: row %d = (n %d, class %d) out of range (N=%d K=%d)", who, r, q[0], q[1], N, K);
+    }
+    return hip_status(spx_launch_explain_dominant(planes, (const long long*)host_strides, labels, label_bytes, rows, slot_table, weights,
+                                                  R, N, C, K, J, h, w, H, W, dom, (hipStream_t)stream), who);
+}
+
 static int kld_check(const char* who, const float* vals, const int32_t* labels, int32_t B, int32_t J, int32_t HW, int32_t K,
                      const void* out, int pairs) {
     if (!vals || !labels || !out) return fail("%s: NULL buffer", who);

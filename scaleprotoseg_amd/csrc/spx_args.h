@@ -222,6 +222,15 @@ hipError_t spx_launch_overlap_accumulate(const float* planes, const long long* s
 hipError_t spx_launch_push_boxes(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
                                  const float* thresholds, int R, int N, int C, int h, int w, int H, int W, int add_margin,
                                  int32_t* rf_boxes, int32_t* crops, hipStream_t s);
+// explanation maps (spx_explain.hip)
+hipError_t spx_launch_explain_range(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
+                                    int R, int N, int C, int h, int w, int H, int W, void* workspace, hipStream_t s);
+hipError_t spx_launch_explain_heat(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
+                                   int R, int N, int C, int h, int w, int H, int W, const void* workspace, uint8_t* heat, float* ranges,
+                                   hipStream_t s);
+hipError_t spx_launch_explain_dominant(const float* planes, const long long* st, const void* labels, int label_bytes,
+                                       const int32_t* rows, const int32_t* table, const float* weights, int R, int N, int C, int K, int J,
+                                       int h, int w, int H, int W, uint8_t* dom, hipStream_t s);
 size_t spx_actloss_ws_bytes(int B, int K, int J);
 hipError_t spx_launch_actloss_max(const spx_actloss* p, void* workspace, hipStream_t s);
 hipError_t spx_launch_actloss_sums(const spx_actloss* p, void* workspace, hipStream_t s);

@@ -13,8 +13,6 @@
 #include "spx_overlap_sample.h"
 
 #define OVL_THREADS 256
-#define OVL_STAGE 8192            // floats of latent rows staged per band (32 KiB)
-#define OVL_BAND 256              // most output rows of one band (the y-tap table's size)
 #define OVL_BINS 2048             // bins of a histogram round (the last round uses 1024)
 #define OVL_MAX_J 32
 #define OVL_MAX_PAIRS (OVL_MAX_J * (OVL_MAX_J + 1) / 2)
@@ -161,30 +159,6 @@ __global__ __launch_bounds__(OVL_THREADS) void spx_overlap_scan_kernel(int round
         thresholds[plane] = gamma >= 0.5f ? hi - d * (1.0f - gamma) : lo + d * gamma;
     }
 }
-
-// rows of a band so that its latent footprint (rows i_first - 1 .. i_last + 2) fits the stage
-static int ovl_band_rows(int h, int w, int H) {
-    const int cap = OVL_STAGE / w;                               // >= 5: the entry point bounds w
-    if (cap >= h) return H < OVL_BAND ? H : OVL_BAND;
-    // (r - 1) * h / H <= cap - 5, so first and last row of a band are at most cap - 4 latent rows apart (the floors of two
-    // coordinates x apart differ by at most ceil(x)) and with the taps -1 .. +2 at most cap rows are staged
-    const long long r = 1 + (long long)(cap - 5) * H / h;
-    return (int)(r < OVL_BAND ? r : OVL_BAND);
-}
-// the most latent rows any band of `band` output rows stages, by the kernel's own coordinate rule (host copy of ovl_coord's
-// integer part): the launch refuses a band that would not fit instead of trusting the bound above
-static int ovl_max_staged_rows(int h, int H, int band) {
-    int most = 0;
-    for (int Y0 = 0; Y0 < H; Y0 += band) {
-        const int Y1 = Y0 + band < H ? Y0 + band : H;
-        const long long n0 = (2LL * Y0 + 1) * h - H, n1 = (2LL * (Y1 - 1) + 1) * h - H, den = 2LL * H;
-        const int i0 = n0 < 0 ? -1 : (int)(n0 / den), i1 = n1 < 0 ? -1 : (int)(n1 / den);
-        const int lo = i0 - 1 < 0 ? 0 : (i0 - 1 > h - 1 ? h - 1 : i0 - 1), hi = i1 + 2 > h - 1 ? h - 1 : (i1 + 2 < 0 ? 0 : i1 + 2);
-        if (hi - lo + 1 > most) most = hi - lo + 1;
-    }
-    return most;
-}
-
 
 size_t spx_overlap_ws_bytes(int N, int C, int K) {
     const long long planes = (long long)N * C;

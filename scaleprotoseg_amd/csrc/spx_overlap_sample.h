@@ -1,6 +1,7 @@
-// What the activation-overlap metrics (spx_overlap.hip) and the push bounding boxes (spx_pushbox.hip) share: the upsampled
-// value of a pixel recomputed from the latent plane, the strided view of the planes and the label read.  ONE function,
-// compiled with -ffp-contract=off, gives a pixel the same bits in every pass of either file.
+// What the activation-overlap metrics (spx_overlap.hip), the push bounding boxes (spx_pushbox.hip) and the explanation maps
+// (spx_explain.hip) share: the upsampled value of a pixel recomputed from the latent plane, the strided view of the planes, the
+// label read and the bands of output rows that stage their latent rows in LDS.  ONE function, compiled with -ffp-contract=off,
+// gives a pixel the same bits in every pass of every file.
 #ifndef SPX_OVERLAP_SAMPLE_H
 #define SPX_OVERLAP_SAMPLE_H
 #include "spx_common.h"
@@ -73,6 +74,33 @@ __device__ __forceinline__ long long ovl_label(const void* labels, int label_byt
     if (label_bytes == 1) return (long long)((const uint8_t*)labels)[o];
     if (label_bytes == 4) return (long long)((const int32_t*)labels)[o];
     return ((const long long*)labels)[o];
+}
+
+// ---- bands of output rows whose latent footprint is staged in LDS --------------------------------------------------------
+#define OVL_STAGE 8192            // floats of latent rows staged per band (32 KiB)
+#define OVL_BAND 256              // most output rows of one band (the y-tap table's size)
+
+// rows of a band so that its latent footprint (rows i_first - 1 .. i_last + 2) fits the stage
+static inline int ovl_band_rows(int h, int w, int H) {
+    const int cap = OVL_STAGE / w;                               // >= 5: the entry point bounds w
+    if (cap >= h) return H < OVL_BAND ? H : OVL_BAND;
+    // (r - 1) * h / H <= cap - 5, so first and last row of a band are at most cap - 4 latent rows apart (the floors of two
+    // coordinates x apart differ by at most ceil(x)) and with the taps -1 .. +2 at most cap rows are staged
+    const long long r = 1 + (long long)(cap - 5) * H / h;
+    return (int)(r < OVL_BAND ? r : OVL_BAND);
+}
+// the most latent rows any band of `band` output rows stages, by the kernel's own coordinate rule (host copy of ovl_coord's
+// integer part): the launch refuses a band that would not fit instead of trusting the bound above
+static inline int ovl_max_staged_rows(int h, int H, int band) {
+    int most = 0;
+    for (int Y0 = 0; Y0 < H; Y0 += band) {
+        const int Y1 = Y0 + band < H ? Y0 + band : H;
+        const long long n0 = (2LL * Y0 + 1) * h - H, n1 = (2LL * (Y1 - 1) + 1) * h - H, den = 2LL * H;
+        const int i0 = n0 < 0 ? -1 : (int)(n0 / den), i1 = n1 < 0 ? -1 : (int)(n1 / den);
+        const int lo = i0 - 1 < 0 ? 0 : (i0 - 1 > h - 1 ? h - 1 : i0 - 1), hi = i1 + 2 > h - 1 ? h - 1 : (i1 + 2 < 0 ? 0 : i1 + 2);
+        if (hi - lo + 1 > most) most = hi - lo + 1;
+    }
+    return most;
 }
 
 #endif  // SPX_OVERLAP_SAMPLE_H

@@ -53,6 +53,39 @@ def _planes(t: torch.Tensor, grid: Optional[Tuple[int, int]], name: str) -> torc
     raise SpxError(f"{name} must be [N, C, h, w], or [M, C] with grid=(h, w)")
 
 
+def _input_planes(activations, distances, grid, similarity, group_sizes, owner: str) -> torch.Tensor:
+    """The [N, C, h, w] planes of what ``update`` (and the explanation maps) accept: activations as ``_planes`` takes them,
+    ``distances=`` through the model's ``similarity`` (``for_prototypes``), or the list ``compute_group`` returns, concatenated
+    (``for_groups``, ``group_sizes`` = its widths)."""
+    if (activations is None) == (distances is None):
+        raise SpxError("pass either activations or distances=")
+    if distances is not None:
+        if similarity is None:
+            raise SpxError(f"distances= needs {owner}.for_prototypes(ppnet)")
+        _dev_ptr(distances, "distances")
+        activations = similarity(_planes(distances, grid, "distances"))
+    elif isinstance(activations, (list, tuple)):
+        if group_sizes is None or [int(t.shape[-1]) for t in activations] != group_sizes:
+            raise SpxError(f"a list of activations must be what compute_group returns for {owner}.for_groups(ppnet)")
+        for t in activations:
+            _dev_ptr(t, "activations")
+        activations = torch.cat([t.detach() for t in activations], dim=1)
+    return _planes(activations, grid, "activations")
+
+
+def _group_slot_table(ppnet) -> Tuple[torch.Tensor, list]:
+    """([K, J] channel of (class, group) in the concatenation of ``compute_group``'s list, -1 = no such group; its widths)."""
+    sizes = [int(gp.weight.shape[0]) for gp in ppnet.group_projection]
+    if len(sizes) != ppnet.num_classes:
+        raise SpxError(f"{len(sizes)} group projections for {ppnet.num_classes} classes")
+    table = torch.full((len(sizes), max(1, max(sizes))), -1, dtype=torch.long)
+    c0 = 0
+    for k, g in enumerate(sizes):
+        table[k, :g] = torch.arange(c0, c0 + g)
+        c0 += g
+    return table, sizes
+
+
 def _rank(q: float, count: int) -> Tuple[int, float]:
     """(k, gamma) of numpy's linear quantile for ``count`` values: float64 on the host, gamma then rounded to fp32."""
     q = float(q)
@@ -177,16 +210,9 @@ class ActivationOverlap:
         that list.  ``update`` takes the list or its concatenation ([M, U] with ``grid``, or [N, U, h, w])."""
         if device is None:
             device = ppnet.prototype_vectors.device
-        sizes = [int(gp.weight.shape[0]) for gp in ppnet.group_projection]
-        if len(sizes) != ppnet.num_classes:
-            raise SpxError(f"{len(sizes)} group projections for {ppnet.num_classes} classes")
-        table = torch.full((len(sizes), max(1, max(sizes))), -1, dtype=torch.long)
-        c0 = 0
-        for k, g in enumerate(sizes):
-            table[k, :g] = torch.arange(c0, c0 + g)
-            c0 += g
+        table, sizes = _group_slot_table(ppnet)
         m = cls(ppnet.num_classes, table, device, quantile)
-        m.num_channels = c0
+        m.num_channels = sum(sizes)
         m._group_sizes = sizes
         return m
 
@@ -202,20 +228,7 @@ class ActivationOverlap:
         lib = _lib.load()
         if labels is None:
             raise SpxError("labels are required")
-        if (activations is None) == (distances is None):
-            raise SpxError("pass either activations or distances=")
-        if distances is not None:
-            if self._similarity is None:
-                raise SpxError("distances= needs ActivationOverlap.for_prototypes(ppnet)")
-            _dev_ptr(distances, "distances")
-            activations = self._similarity(_planes(distances, grid, "distances"))
-        elif isinstance(activations, (list, tuple)):
-            if self._group_sizes is None or [int(t.shape[-1]) for t in activations] != self._group_sizes:
-                raise SpxError("a list of activations must be what compute_group returns for ActivationOverlap.for_groups(ppnet)")
-            for t in activations:
-                _dev_ptr(t, "activations")
-            activations = torch.cat([t.detach() for t in activations], dim=1)
-        planes = _planes(activations, grid, "activations")
+        planes = _input_planes(activations, distances, grid, self._similarity, self._group_sizes, "ActivationOverlap")
         if labels.dim() != 3 or labels.dtype not in _LABEL_BYTES:
             raise SpxError(f"labels must be uint8, int32 or int64 [N, H, W] (got {labels.dtype} {tuple(labels.shape)})")
         for t, name in ((planes, "activations"), (labels, "labels")):
