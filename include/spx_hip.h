@@ -273,6 +273,17 @@ int spx_group_dense(const float* const* block_ptrs, const int32_t* block_cols, i
                     void* stream);
 int spx_group_dense_bwd(const float* d_out, const int32_t* flat_row, const int32_t* flat_col, int64_t n, int32_t P, float* d_flat,
                         void* stream);
+/* In-place Euclidean projection of every ROW of the group projections onto the simplex {w >= 0, sum w = z} in one launch
+ * (segmentation/utils.py:113-124 projection_simplex_sort, once per class after every optimizer step of the group phase,
+ * segmentation/model/module_multiscale_group_train.py:337-338).  block_ptrs / block_rows / block_cols: HOST arrays of nblocks
+ * DEVICE pointers to contiguous fp32 matrices [G_j, n_j], their row counts G_j and column counts n_j.  Per row: u = the row in
+ * descending order; css_k = fp32(sum_{i<=k} u_i) - z, the sum kept in float64, added in order, rounded per element; rho = the
+ * largest k with u_k - css_k / k > 0 (fp32); theta = css_rho / rho; w = v - theta where that is not below 0, else 0.  Bit-identical
+ * to the stock formula on a CPU copy of the row; no atomics, run-to-run identical.  A row holding a NaN comes back all NaN, the
+ * other rows are untouched by it.  Enqueues on `stream` only.  Limits: 1 <= nblocks <= 192, G_j >= 1, 1 <= n_j <= 1024, at
+ * most 2^31 - 1 rows; a violation or a NULL pointer returns non-zero and launches nothing. */
+int spx_simplex_project(float* const* block_ptrs, const int32_t* block_rows, const int32_t* block_cols, int32_t nblocks, float z,
+                        void* stream);
 size_t spx_packed_tail_bytes(const spx_plan* plan);
 int spx_pack_group_tail(const spx_plan* plan, const float* Wg, int32_t K2, void* packed_tail, void* packed_tailT,
                         void* stream);

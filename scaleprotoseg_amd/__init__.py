@@ -7,6 +7,10 @@ Public surface mirrors the reference's module/function names for this path:
     compute_distances, min_across_dataset, global_min, push_prototypes_multiscale
                                                     (segmentation/push_multiscale_optimization.py)
     projection_simplex_sort, resize_label           (segmentation/utils.py, segmentation/data/dataset.py)
+    projection_simplex_sort_                        (the same projection of all group projections IN PLACE, one launch,
+                                                     bit-identical to the formula on the CPU; capturable)
+    threshold_group_projections_, non_zero_proto    (segmentation/analysis/threshold_save.py:27-28, segmentation/utils.py:140-154:
+                                                     zero the small group weights; the prototypes any group still uses)
     KLDLoss, KLDLossGroup                           (segmentation/model/loss.py; KLDLoss also takes the class-gathered
                                                      ClassDistances of forward_from_conv_features(target_labels=...))
     SegmentationMetrics                             (segmentation/eval_valid_multiscale.py:229-275: mIoU, per-class IoU,
@@ -85,6 +89,12 @@ from .push import (  # noqa: F401
 from .pushbox import push_bounding_boxes  # noqa: F401
 from .explain import ExplanationMaps, activation_heat_maps, dominant_slot_maps  # noqa: F401
 from .prune import NearestPatches, find_k_nearest_patches_to_prototypes, prune_prototypes  # noqa: F401
-from .utils import projection_simplex_sort, resize_label  # noqa: F401
+from .utils import (  # noqa: F401
+    non_zero_proto,
+    projection_simplex_sort,
+    projection_simplex_sort_,
+    resize_label,
+    threshold_group_projections_,
+)
 
 __version__ = "0.1.0"

@@ -594,6 +594,30 @@ int spx_group_dense_bwd(const float* d_out, const int32_t* flat_row, const int32
     return hip_status(spx_launch_group_dense_bwd(d_out, flat_row, flat_col, n, P, d_flat, (hipStream_t)stream), "spx_group_dense_bwd");
 }
 
+int spx_simplex_project(float* const* block_ptrs, const int32_t* block_rows, const int32_t* block_cols, int32_t nblocks, float z,
+                        void* stream) {
+    static const char* who = "spx_simplex_project";
+    if (!block_ptrs || !block_rows || !block_cols) return fail("%s: NULL table", who);
+    if (nblocks < 1 || nblocks > SPX_GROUP_BLOCKS_MAX) return fail("%s: %d blocks (1..%d)", who, nblocks, SPX_GROUP_BLOCKS_MAX);
+    SpxSimplexArgs a{};
+    long long rows = 0;
+    for (int j = 0; j < nblocks; ++j) {
+        if (!block_ptrs[j]) return fail("%s: block %d is NULL", who, j);
+        if (block_rows[j] < 1) return fail("%s: block %d has %d rows (>= 1)", who, j, block_rows[j]);
+        if (block_cols[j] < 1 || block_cols[j] > SPX_SIMPLEX_MAX_COLS)
+            return fail("%s: block %d has %d columns (1..%d)", who, j, block_cols[j], SPX_SIMPLEX_MAX_COLS);
+        a.ptrs[j] = block_ptrs[j];
+        a.cols[j] = block_cols[j];
+        a.row0[j] = (int)rows;
+        rows += block_rows[j];
+        if (rows > 0x7fffffffLL) return fail("%s: more than 2^31 - 1 rows", who);
+    }
+    a.row0[nblocks] = (int)rows;
+    a.nblocks = nblocks;
+    a.z = z;
+    return hip_status(spx_launch_simplex(a, (hipStream_t)stream), who);
+}
+
 int spx_ce_fwd(const float* logits, const int32_t* labels, int64_t M, int32_t K, float* lse, int32_t* pred, float* partials,
                void* stream) {
     if (!logits || !labels || !lse || !partials) return fail("spx_ce_fwd: NULL buffer");

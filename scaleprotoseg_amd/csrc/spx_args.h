@@ -161,6 +161,16 @@ struct SpxGroupDenseArgs {
 hipError_t spx_launch_group_dense(const SpxGroupDenseArgs& a, hipStream_t s);
 hipError_t spx_launch_group_dense_bwd(const float* d_out, const int32_t* rows, const int32_t* cols, long long n, int P, float* d_flat,
                                       hipStream_t s);
+// in-place simplex projection of the group projections' rows (spx_simplex_project): one workgroup per row
+#define SPX_SIMPLEX_MAX_COLS 1024
+struct SpxSimplexArgs {
+    float* ptrs[SPX_GROUP_BLOCKS_MAX];           // device pointer of every block's weight [G_j, n_j]
+    int cols[SPX_GROUP_BLOCKS_MAX];              // n_j
+    int row0[SPX_GROUP_BLOCKS_MAX + 1];          // first row of block j in the launch's row order; row0[nblocks] = all rows
+    int nblocks;
+    float z;
+};
+hipError_t spx_launch_simplex(const SpxSimplexArgs& a, hipStream_t s);
 hipError_t spx_launch_push_argmin(const float* dist, const int32_t* labels, const float* ident, int B, int P, int K,
                                   int HW, int void_class, float max_dist, int64_t* idx, float* val,
                                   uint64_t* scratch, hipStream_t s);

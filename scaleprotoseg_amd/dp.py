@@ -189,17 +189,20 @@ class DataParallelStep:
     (equal to the single-process loss over the union batch when each rank's loss is a mean over equally many terms)."""
 
     def __init__(self, net: torch.nn.Module, optimizer: torch.optim.Optimizer, iter_size: int = 1, group=None,
-                 grad_hook=None, scheduler=None):
+                 grad_hook=None, scheduler=None, fused_projection: bool = False):
         """``grad_hook`` (optional, no arguments) runs on every rank AFTER the all-reduce and BEFORE ``optimizer.step()`` - the
         place of the reference's gradient edits, e.g. ``last_layer_group.weight.grad *= group_class_identity.T`` when
         ``incorrect_strength == 0`` (module_multiscale_group_train.py:327-328); ``scheduler.step()`` (optional) follows the
-        optimizer step and precedes the simplex re-projection, as upstream (:333-338)."""
+        optimizer step and precedes the simplex re-projection, as upstream (:333-338).  ``fused_projection=True`` re-projects
+        all group projections in place with one launch (``utils.projection_simplex_sort_``: storages kept, bit-identical to the
+        formula on the CPU); the default is the per-class formula on the device, each result bound as a new storage."""
         self.net = net
         self.optimizer = optimizer
         self.iter_size = int(iter_size)
         self.group = group
         self.grad_hook = grad_hook
         self.scheduler = scheduler
+        self.fused_projection = bool(fused_projection)
         self.iter_steps = 0
         self.bucket = FlatGradBucket(self._trainable(), attach=True)
 
@@ -231,9 +234,12 @@ class DataParallelStep:
             self.scheduler.step()
         projections = getattr(self.net, "group_projection", None)
         if projections is not None:
-            from .utils import projection_simplex_sort
+            from .utils import projection_simplex_sort, projection_simplex_sort_
 
-            for gp in projections:
-                gp.weight.data = projection_simplex_sort(gp.weight.data)
+            if self.fused_projection:
+                projection_simplex_sort_([gp.weight for gp in projections])
+            else:
+                for gp in projections:
+                    gp.weight.data = projection_simplex_sort(gp.weight.data)
         self.bucket.zero()                   # (not zero_grad(set_to_none=True): the .grad views stay attached)
         return True

@@ -23,7 +23,7 @@ from .functional import (MAX_FUSED_HEAD_ROWS, MAX_FUSED_TAIL_CLASSES, GroupTable
                          group_dense, group_exp, invalidate_pack_cache, proto_head_forward, shifted_labels_i32, wide_group_tail,
                          wide_linear)
 from .model_multiscale import _PrototypeBankMixin, _build_add_on, _first_add_on_channels
-from .utils import projection_simplex_sort
+from .utils import projection_simplex_sort, projection_simplex_sort_
 
 
 class GroupRegTables:
@@ -305,6 +305,12 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
     def set_last_layer_incorrect_connection(self):
         pos = torch.t(self.group_class_identity).to(self.last_layer_group.weight.device)  # :480-491
         self.last_layer_group.weight.data.copy_(1 * pos + self.incorrect_strength * (1 - pos))
+        invalidate_pack_cache()
+
+    def project_group_simplex_(self, z: float = 1.0):
+        """Re-project every ``group_projection`` weight onto the simplex in place (the step after ``optimizer.step()`` in the
+        group phase, module_multiscale_group_train.py:337-338): one launch, storages kept (``utils.projection_simplex_sort_``)."""
+        projection_simplex_sort_([gp.weight for gp in self.group_projection], z)
         invalidate_pack_cache()
 
     def _initialize_weights(self, equiv_path=None, equiv_scale_weight: float = 0.25):
