@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import loss_oracle as LO
 from oracle import ppnet_oracle as O
+from kld_cases import MIN_LOSS, correlated_planes
 
 
 def _dev():
@@ -846,7 +847,8 @@ def test_kld_kernels_match_reference_golden(golden, tag):
 
 
 def test_kld_kernels_large_random():
-    """2048 x 1024 pixels, random (non-uniform) and patchy labels: kernels vs the torch formulation of the same loss."""
+    """2048 x 1024 pixels, random (non-uniform) and patchy labels: kernels vs the torch formulation of the same loss.  Twice: on
+    independent slot planes (loss about 1e-8: the value assertion cannot fail there) and on tests/kld_cases.py's correlated ones."""
     import scaleprotoseg_amd as spx
 
     dev = _dev()
@@ -854,26 +856,29 @@ def test_kld_kernels_large_random():
     ident = O.default_class_identity(P, K, S)
     lay = _layout(P, K, S, 16, O.default_scale_ranges(P, S))
     keys, J, table = spx.class_gather_table(lay, ident, dev)
-    gen = torch.Generator(device=dev).manual_seed(5)
-    for patchy in (False, True):
-        if patchy:
-            t = torch.randint(0, K + 1, (1, H // 32, W // 32), device=dev, generator=gen).repeat_interleave(32, 1).repeat_interleave(32, 2)
-        else:
-            t = torch.randint(0, K + 1, (1, H, W), device=dev, generator=gen)
-        base = torch.rand(1, J, H * W, device=dev, generator=gen) * 40
-        loss_fn = spx.KLDLoss(ident, S, {0: (0, P)})
-        v1 = base.clone().requires_grad_(True)
-        l1 = loss_fn(spx.ClassDistances(v1, (t.reshape(1, -1) - 1).int(), table, (H, W)), t)
-        l1.backward()
-        v2 = base.double().clone().requires_grad_(True)                      # fp64 -> the oracle's torch restatement
-        with pytest.raises(spx.SpxError):
-            loss_fn(spx.ClassDistances(v2, (t.reshape(1, -1) - 1).int(), table, (H, W)), t)      # the product has no other backend
-        l2 = LO.kld_loss(loss_fn, spx.ClassDistances(v2, (t.reshape(1, -1) - 1).int(), table, (H, W)), t)
-        l2.backward()
-        torch.cuda.synchronize()
-        assert abs(l1.item() - l2.item()) <= 1e-5 * max(1.0, abs(l2.item())), (l1.item(), l2.item())
-        s = v2.grad.abs().max().item()
-        assert (v1.grad.double() - v2.grad).abs().max().item() <= 1e-4 * s + 1e-12
+    for planes in ("independent", "correlated"):
+        gen = torch.Generator(device=dev).manual_seed(5)
+        for patchy in (False, True):
+            if patchy:
+                t = torch.randint(0, K + 1, (1, H // 32, W // 32), device=dev, generator=gen).repeat_interleave(32, 1).repeat_interleave(32, 2)
+            else:
+                t = torch.randint(0, K + 1, (1, H, W), device=dev, generator=gen)
+            base = torch.rand(1, J, H * W, device=dev, generator=gen) * 40 if planes == "independent" else correlated_planes(1, J, H * W, gen, span=40.0)
+            loss_fn = spx.KLDLoss(ident, S, {0: (0, P)})
+            v1 = base.clone().requires_grad_(True)
+            l1 = loss_fn(spx.ClassDistances(v1, (t.reshape(1, -1) - 1).int(), table, (H, W)), t)
+            l1.backward()
+            v2 = base.double().clone().requires_grad_(True)                      # fp64 -> the oracle's torch restatement
+            with pytest.raises(spx.SpxError):
+                loss_fn(spx.ClassDistances(v2, (t.reshape(1, -1) - 1).int(), table, (H, W)), t)      # the product has no other backend
+            l2 = LO.kld_loss(loss_fn, spx.ClassDistances(v2, (t.reshape(1, -1) - 1).int(), table, (H, W)), t)
+            l2.backward()
+            torch.cuda.synchronize()
+            if planes == "correlated":
+                assert l2.item() >= MIN_LOSS, l2.item()                          # the value assertion below is live
+            assert abs(l1.item() - l2.item()) <= 1e-5 * max(1.0, abs(l2.item())), (l1.item(), l2.item())
+            s = v2.grad.abs().max().item()
+            assert (v1.grad.double() - v2.grad).abs().max().item() <= 1e-4 * s + 1e-12
 
 
 @pytest.mark.parametrize("K,per", [(150, 12), (182, 12)])
@@ -894,19 +899,23 @@ def test_kld_kernels_with_the_ade_and_coco_class_counts(K, per):
     coarse = torch.randn(B, K + 1, 3, 5, device=dev, generator=gen)
     t = torch.nn.functional.interpolate(coarse, size=(H, W), mode="bilinear", align_corners=False).argmax(dim=1)     # irregular regions
     t[0, :4] = torch.randint(0, K + 1, (4, W), device=dev, generator=gen)                                            # and some salt
-    base = torch.rand(B, J, H * W, device=dev, generator=gen) * 20
     loss_fn = spx.KLDLoss(ident, S, ranges)
     lab0 = (t.reshape(B, -1) - 1).int()
-    v1 = base.clone().requires_grad_(True)
-    l1 = loss_fn(spx.ClassDistances(v1, lab0, table, (H, W)), t)
-    l1.backward()
-    v2 = base.double().clone().requires_grad_(True)
-    l2 = LO.kld_loss(loss_fn, spx.ClassDistances(v2, lab0, table, (H, W)), t)
-    l2.backward()
-    torch.cuda.synchronize()
-    assert abs(l1.item() - l2.item()) <= 1e-5 * max(1.0, abs(l2.item())), (l1.item(), l2.item())
-    sc = v2.grad.abs().max().item()
-    assert sc > 0 and (v1.grad.double() - v2.grad).abs().max().item() <= 1e-4 * sc + 1e-12
+    # independent slot planes (loss 2e-2 and less) and tests/kld_cases.py's correlated ones
+    for planes in ("independent", "correlated"):
+        base = torch.rand(B, J, H * W, device=dev, generator=gen) * 20 if planes == "independent" else correlated_planes(B, J, H * W, gen, span=20.0)
+        v1 = base.clone().requires_grad_(True)
+        l1 = loss_fn(spx.ClassDistances(v1, lab0, table, (H, W)), t)
+        l1.backward()
+        v2 = base.double().clone().requires_grad_(True)
+        l2 = LO.kld_loss(loss_fn, spx.ClassDistances(v2, lab0, table, (H, W)), t)
+        l2.backward()
+        torch.cuda.synchronize()
+        if planes == "correlated":
+            assert l2.item() >= MIN_LOSS, l2.item()                              # the value assertion below is live
+        assert abs(l1.item() - l2.item()) <= 1e-5 * max(1.0, abs(l2.item())), (l1.item(), l2.item())
+        sc = v2.grad.abs().max().item()
+        assert sc > 0 and (v1.grad.double() - v2.grad).abs().max().item() <= 1e-4 * sc + 1e-12
 
 
 def test_kld_group_kernels_match_reference_golden(golden):
@@ -950,24 +959,28 @@ def test_kld_kernels_ragged_grids(H, W):
     keys, J, table = spx.class_gather_table(lay, ident, dev)
     gen = torch.Generator(device=dev).manual_seed(H * 1000 + W)
     t = torch.randint(0, K + 1, (2, (H + 7) // 8, (W + 15) // 16), device=dev, generator=gen).repeat_interleave(8, 1).repeat_interleave(16, 2)[:, :H, :W].contiguous()
-    base = torch.rand(2, J, H * W, device=dev, generator=gen) * 30
     loss_fn = spx.KLDLoss(ident, S, {0: (0, P)})
     lab = (t.reshape(2, -1) - 1).int()
-    v2 = base.double().clone().requires_grad_(True)
-    l2 = LO.kld_loss(loss_fn, spx.ClassDistances(v2, lab, table, (H, W)), t)
-    l2.backward()
-    for grid in ((H, W), (1, H * W)):               # column strips / one row (= the linear order)
-        v1 = base.clone().requires_grad_(True)
-        l1 = loss_fn(spx.ClassDistances(v1, lab, table, grid), t)
-        l1.backward()
-        torch.cuda.synchronize()
-        assert abs(l1.item() - l2.item()) <= 1e-5 * max(1.0, abs(l2.item())), (grid, l1.item(), l2.item())
-        s = v2.grad.abs().max().item()
-        assert (v1.grad.double() - v2.grad).abs().max().item() <= 1e-4 * s + 1e-12
-    # W = 0 through the C ABI gives the same sums as the column walk up to fp32 rounding of partial sums
-    A_w = L.segment_pair_sums(base, lab, K, W)
-    A_0 = L.segment_pair_sums(base, lab, K, 0)
-    assert (A_w - A_0).abs().max().item() <= 1e-5 * (1.0 + A_0.abs().max().item())
+    # independent slot planes (loss 2e-5 and less) and tests/kld_cases.py's correlated ones
+    for planes in ("independent", "correlated"):
+        base = torch.rand(2, J, H * W, device=dev, generator=gen) * 30 if planes == "independent" else correlated_planes(2, J, H * W, gen)
+        v2 = base.double().clone().requires_grad_(True)
+        l2 = LO.kld_loss(loss_fn, spx.ClassDistances(v2, lab, table, (H, W)), t)
+        l2.backward()
+        if planes == "correlated":
+            assert l2.item() >= MIN_LOSS, l2.item()                              # the value assertions below are live
+        for grid in ((H, W), (1, H * W)):               # column strips / one row (= the linear order)
+            v1 = base.clone().requires_grad_(True)
+            l1 = loss_fn(spx.ClassDistances(v1, lab, table, grid), t)
+            l1.backward()
+            torch.cuda.synchronize()
+            assert abs(l1.item() - l2.item()) <= 1e-5 * max(1.0, abs(l2.item())), (grid, l1.item(), l2.item())
+            s = v2.grad.abs().max().item()
+            assert (v1.grad.double() - v2.grad).abs().max().item() <= 1e-4 * s + 1e-12
+        # W = 0 through the C ABI gives the same sums as the column walk up to fp32 rounding of partial sums
+        A_w = L.segment_pair_sums(base, lab, K, W)
+        A_0 = L.segment_pair_sums(base, lab, K, 0)
+        assert (A_w - A_0).abs().max().item() <= 1e-5 * (1.0 + A_0.abs().max().item())
 
 
 @pytest.mark.parametrize("B,P,K,H,W,void", [(1, 3, 2, 1, 4, 0), (2, 8, 4, 2, 6, None), (3, 21, 7, 10, 36, 3), (1, 190, 19, 64, 260, 0), (2, 9, 3, 130, 64, None)])

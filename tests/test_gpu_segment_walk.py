@@ -1,7 +1,8 @@
 """GPU checks of the shared segment walk (csrc/spx_kld_walk.h) under both families that use it: the KLD loss against LO.kld_loss in
 float64 and the activation losses against the float64 restatement of tests/test_activation_losses_cpu.py, with the tolerances of
-the existing tests of those kernels.  The planes are random [B, J, HW] tensors (no distance kernel); the label map is built so that
-every branch of the walk runs whatever tile height the launcher picks (tiles start at multiples of 16 rows):
+the existing tests of those kernels.  The planes are random [B, J, HW] tensors (no distance kernel; for the KLD loss both
+independent slots, loss about 0, and tests/kld_cases.py's correlated ones, loss about 0.4); the label map (kld_cases.band_labels)
+is built so that every branch of the walk runs whatever tile height the launcher picks (tiles start at multiples of 16 rows):
   rows  0 -  7  one class                         a uniform run
   rows  8 - 15  another class                     a class change inside one wave's walk: a publish mid-walk
   rows 16 - 19  void                              a step that is skipped
@@ -16,12 +17,13 @@ import torch
 
 from oracle import loss_oracle as LO
 from oracle import ppnet_oracle as O
+from kld_cases import BAND_B, BAND_H, BAND_W, MIN_LOSS, band_classes, band_labels as _labels, correlated_planes
 from test_activation_losses_cpu import log_activation
 from test_gpu_activation_losses import W3, _check_against_reference64, _identity, _reference64
 
 pytestmark = pytest.mark.gpu
 
-B, H, W = 2, 37, 83
+B, H, W = BAND_B, BAND_H, BAND_W                           # 2 x 37 x 83
 WIDTHS = (3, 7, 11, 16)                                   # one J per JT = 4, 8, 12, 16
 WALKS = ("grid", "linear")
 
@@ -32,46 +34,26 @@ def _dev():
     return torch.device("cuda:0")
 
 
-@functools.lru_cache(maxsize=None)
-def _labels(K, bands):
-    """labels0 [B, H, W] (class 0..K-1, else none) as in the module docstring; ``bands[b]``: the three band classes of image b."""
-    gen = torch.Generator().manual_seed(37 * 83 + K)
-    lab = torch.full((B, H, W), -1, dtype=torch.long)
-    for b in range(B):
-        c0, c1, c2 = bands[b]
-        lab[b, 0:8], lab[b, 8:16], lab[b, 28:] = c0, c1, c2
-        lab[b, 20:28] = torch.randint(-1, K, (8, W), generator=gen)
-        lab[b, 21, 5], lab[b, 26, 70] = K + 1, -3
-    for b in range(B):
-        assert len(set(bands[b])) == 3
-        assert (lab[b, 0:8] == bands[b][0]).all() and (lab[b, 8:16] == bands[b][1]).all()        # two classes, two 8-row bands
-        assert (lab[b, 16:20] == -1).all() and (lab[b, 28:] == bands[b][2]).all()
-        blocks = [lab[b, r:r + 4, c:c + 16] for r in (20, 24) for c in range(0, W, 16)]
-        assert any(len(set(x[(x >= 0) & (x < K)].tolist())) >= 2 for x in blocks)                 # a mixed 16 x 4 step
-        assert (lab[b] >= K).any() and (lab[b] < -1).any()
-    return lab
-
-
 def _grid(walk):
     return (H, W) if walk == "grid" else (1, H * W)
 
 
 @functools.lru_cache(maxsize=None)
-def _kld_case(K, J):
-    """(identity, target, labels0 int32, planes, loss module, float64 loss, float64 gradient), on the device."""
+def _kld_case(K, J, planes):
+    """(target, labels0 int32, table, planes, loss module, float64 loss, float64 gradient), on the device; ``planes``: "independent"
+    (rand * 30 per slot) or "correlated" (kld_cases.correlated_planes)."""
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.loss import ClassDistances, class_slot_table
 
     dev = _dev()
     P = K * J
     ident = O.default_class_identity(P, K, 1)
-    bands = ((0, K - 1, 2), (K - 2, 1, K - 1)) if K > 5 else ((0, 1, 2), (3, 4, 1))
-    lab = _labels(K, bands).to(dev)
+    lab = _labels(K, band_classes(K)).to(dev)
     t = lab + 1
     table = class_slot_table(ident).to(dev)
     assert tuple(table.shape) == (K, J)
     gen = torch.Generator(device=dev).manual_seed(1000 * K + J)
-    base = torch.rand(B, J, H * W, device=dev, generator=gen) * 30
+    base = torch.rand(B, J, H * W, device=dev, generator=gen) * 30 if planes == "independent" else correlated_planes(B, J, H * W, gen)
     loss_fn = spx.KLDLoss(ident, 1, {0: (0, P)})
     lab32 = lab.reshape(B, -1).int()
     v2 = base.double().clone().requires_grad_(True)
@@ -83,17 +65,20 @@ def _kld_case(K, J):
 def _check_kld(K, J, walk):
     from scaleprotoseg_amd.loss import ClassDistances
 
-    t, lab32, table, base, loss_fn, ref, ref_grad = _kld_case(K, J)
-    v1 = base.clone().requires_grad_(True)
-    l1 = loss_fn(ClassDistances(v1, lab32, table, _grid(walk)), t)
-    l1.backward()
-    torch.cuda.synchronize()
-    gmax = ref_grad.abs().max().item()
-    gerr = (v1.grad.double() - ref_grad).abs().max().item()
-    print(f"KLD K={K} J={J} {walk}: loss {l1.item():.9g} ref {ref:.9g}; gradient err {gerr:.3g} of max {gmax:.3g}")
-    assert ref > 0 and gmax > 0
-    assert abs(l1.item() - ref) <= 1e-5 * max(1.0, abs(ref))
-    assert gerr <= 1e-4 * gmax
+    for planes in ("independent", "correlated"):
+        t, lab32, table, base, loss_fn, ref, ref_grad = _kld_case(K, J, planes)
+        v1 = base.clone().requires_grad_(True)
+        l1 = loss_fn(ClassDistances(v1, lab32, table, _grid(walk)), t)
+        l1.backward()
+        torch.cuda.synchronize()
+        gmax = ref_grad.abs().max().item()
+        gerr = (v1.grad.double() - ref_grad).abs().max().item()
+        print(f"KLD K={K} J={J} {walk} {planes}: loss {l1.item():.9g} ref {ref:.9g}; gradient err {gerr:.3g} of max {gmax:.3g}")
+        assert ref > 0 and gmax > 0
+        if planes == "correlated":
+            assert ref >= MIN_LOSS                                # the value assertion below is live
+        assert abs(l1.item() - ref) <= 1e-5 * max(1.0, abs(ref))
+        assert gerr <= 1e-4 * gmax
 
 
 @pytest.mark.parametrize("walk", WALKS)
