@@ -336,6 +336,12 @@ def shifted_labels_i32(labels: torch.Tensor, device) -> torch.Tensor:
             _lib.check(lib.spx_shift_labels(_lib.ptr(labels), int(labels.dtype == torch.int64), labels.numel(), _lib.ptr(out),
                                             _lib.stream_ptr()))
         return out
+    if labels.dtype in (torch.int64, torch.int32):
+        # the kernel's rule, not a 32-bit wrap: a value whose v - 1 leaves +-(2^31 - 1) is no class (-1) - the low word of
+        # 2^32 + 3 is class 2, and INT32_MIN - 1 wraps to INT32_MAX
+        w = labels.to(torch.int64) - 1
+        w = torch.where((w < -2147483647) | (w > 2147483647), torch.full_like(w, -1), w).to(torch.int32)
+        return w.to(device=device).contiguous()
     return (labels.to(device=device, dtype=torch.int32) - 1).contiguous()
 
 

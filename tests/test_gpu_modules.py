@@ -735,11 +735,16 @@ def test_cross_entropy_kernels_match_reference_golden(golden):
 
 
 @pytest.mark.parametrize("shape,x_dtype,gather", [
-    ((2, 4, 64, 228, 19, 17, 19), torch.float32, False),
-    ((1, 1, 256, 190, 19, 16, 64), torch.bfloat16, False),
-    ((2, 4, 16, 40, 5, 9, 11), torch.float32, True),
-    ((1, 1, 64, 210, 64, 8, 16), torch.float32, False),       # 64 classes: two class blocks
-    ((1, 4, 64, 600, 150, 5, 8), torch.float32, False),       # 150 classes: five class blocks (strided logits path)
+    # which cross entropy each case reaches: with S >= 2 and at most 1024 tiles of 128 pixels the forward runs scale-parallel
+    # (spx_fwd_split_workspace_bytes != 0) and the loss is the STAND-ALONE kernel's on the summed logits; only S = 1 (or more
+    # tiles) enters the fused epilogue.  The backward forms d_logits in the pixel kernel's prologue in all five.
+    # tests/test_gpu_ce_float64.py holds each implementation to float64 per pixel.
+    ((2, 4, 64, 228, 19, 17, 19), torch.float32, False),      # S = 4, 6 tiles: stand-alone spx_ce_fwd
+    ((1, 1, 256, 190, 19, 16, 64), torch.bfloat16, False),    # S = 1: fused epilogue, one class block
+    ((2, 4, 16, 40, 5, 9, 11), torch.float32, True),          # S = 4, 2 tiles: stand-alone spx_ce_fwd (behind the class-gathered forward)
+    ((1, 1, 64, 210, 64, 8, 16), torch.float32, False),       # S = 1: fused epilogue; 64 classes: two class blocks
+    ((1, 4, 64, 600, 150, 5, 8), torch.float32, False),       # S = 4, 1 tile: stand-alone spx_ce_fwd; 150 classes: five class blocks
+                                                              # (strided logits path) in the forward's stores and the prologue only
 ])
 def test_fused_cross_entropy_through_the_module(shape, x_dtype, gather):
     import scaleprotoseg_amd as spx
