@@ -744,8 +744,31 @@ int spx_upsample_argext(const float* src, int32_t N, int32_t C, int32_t h, int32
                                                  (hipStream_t)stream), "spx_upsample_argext");
 }
 
+// ---- full-resolution map operators: evaluation metrics, activation overlap, push bounding boxes, explanation maps ----------
 #define SPX_EVAL_MAX_CLASSES 1024
 #define SPX_EVAL_MAX_PROTOTYPES 4096
+#define SPX_OVL_MAX_SLOTS 32
+#define SPX_OVL_MAX_OUT 32768
+#define SPX_OVL_MAX_ROWS 16384
+#define SPX_OVL_MAX_COLS 1638
+#define SPX_PBX_MAX_ROWS (1 << 24)
+#define SPX_EXP_MAX_ROWS 65535
+
+static int check_label_bytes(const char* who, int32_t code) {
+    if (code != 1 && code != 4 && code != 8) return fail("%s: label byte code %d (1 = uint8, 4 = int32, 8 = int64)", who, code);
+    return 0;
+}
+
+// strides st = (n, channel, y, x) of a [N, C, h, w] tensor of `noun` ("" = the planes): none negative, and one image within
+// 2^31 elements, since the kernels address inside one image with 32-bit offsets
+static int check_image_strides(const char* who, const char* noun, const int64_t* st, int32_t C, int32_t h, int32_t w) {
+    const char* sep = *noun ? " " : "";
+    for (int i = 0; i < 4; ++i)
+        if (st[i] < 0) return fail("%s: negative %s%sstride", who, noun, sep);
+    if ((long long)(C - 1) * st[1] + (long long)(h - 1) * st[2] + (long long)(w - 1) * st[3] >= (1LL << 31))
+        return fail("%s: one %s%simage spans more than 2^31 elements", who, noun, sep);
+    return 0;
+}
 
 int spx_eval_check_classes(const int32_t* host_classes, int32_t P, int32_t K) {
     if (!host_classes) return fail("spx_eval_check_classes: NULL table");
@@ -763,18 +786,11 @@ static int eval_check(const char* who, const float* logits, const int64_t* lst, 
     if (N < 1 || K < 1 || h < 1 || w < 1 || H < 1 || W < 1) return fail("%s: empty input (N=%d K=%d h=%d w=%d H=%d W=%d)", who, N, K, h, w, H, W);
     if (K > SPX_EVAL_MAX_CLASSES) return fail("%s: %d classes (at most %d)", who, K, SPX_EVAL_MAX_CLASSES);
     if ((long long)N * H * W >= (1LL << 31) || (long long)h * w >= (1LL << 31)) return fail("%s: maps too large", who);
-    for (int i = 0; i < 4; ++i)
-        if (lst[i] < 0) return fail("%s: negative logit stride", who);
-    // the kernels address inside one image with 32-bit offsets
-    if ((long long)(K - 1) * lst[1] + (long long)(h - 1) * lst[2] + (long long)(w - 1) * lst[3] >= (1LL << 31))
-        return fail("%s: one image of logits spans more than 2^31 elements", who);
+    if (int e = check_image_strides(who, "logit", lst, K, h, w)) return e;
     if (dist) {
         if (!dst) return fail("%s: NULL distance strides", who);
         if (P < 1 || P > SPX_EVAL_MAX_PROTOTYPES) return fail("%s: %d prototypes (1..%d)", who, P, SPX_EVAL_MAX_PROTOTYPES);
-        for (int i = 0; i < 4; ++i)
-            if (dst[i] < 0) return fail("%s: negative distance stride", who);
-        if ((long long)(P - 1) * dst[1] + (long long)(h - 1) * dst[2] + (long long)(w - 1) * dst[3] >= (1LL << 31))
-            return fail("%s: one image of distances spans more than 2^31 elements", who);
+        if (int e = check_image_strides(who, "distance", dst, P, h, w)) return e;
     }
     return 0;
 }
@@ -786,8 +802,7 @@ int spx_eval_accumulate(const float* logits, const int64_t* host_logit_strides, 
     static const char* who = "spx_eval_accumulate";
     if (!labels || !conf) return fail("%s: NULL labels / confusion counters", who);
     if (distances && (!proto_class || !hits)) return fail("%s: distances without prototype classes / hit counters", who);
-    if (label_bytes != 1 && label_bytes != 4 && label_bytes != 8)
-        return fail("%s: label byte code %d (1 = uint8, 4 = int32, 8 = int64)", who, label_bytes);
+    if (int e = check_label_bytes(who, label_bytes)) return e;
     if (int e = eval_check(who, logits, host_logit_strides, distances, host_dist_strides, N, K, P, h, w, H, W)) return e;
     return hip_status(spx_launch_eval_accumulate(logits, (const long long*)host_logit_strides, distances,
                                                  (const long long*)host_dist_strides, proto_class, labels, label_bytes, N, K, P,
@@ -810,11 +825,6 @@ int spx_eval_topk(const float* logits, const int64_t* host_logit_strides, const 
                                            (unsigned long long*)seen, (hipStream_t)stream), who);
 }
 
-#define SPX_OVL_MAX_SLOTS 32
-#define SPX_OVL_MAX_OUT 32768
-#define SPX_OVL_MAX_ROWS 16384
-#define SPX_OVL_MAX_COLS 1638
-
 static int overlap_check(const char* who, const float* planes, const int64_t* st, int32_t N, int32_t C, int32_t h, int32_t w,
                          int32_t H, int32_t W, const void* workspace) {
     if (!planes || !st || !workspace) return fail("%s: NULL planes / strides / workspace", who);
@@ -824,11 +834,7 @@ static int overlap_check(const char* who, const float* planes, const int64_t* st
         return fail("%s: output %d x %d too large (H*W < 2^31, H and W <= %d)", who, H, W, SPX_OVL_MAX_OUT);
     if (h > SPX_OVL_MAX_ROWS || w > SPX_OVL_MAX_COLS)
         return fail("%s: latent grid %d x %d too large (h <= %d, w <= %d)", who, h, w, SPX_OVL_MAX_ROWS, SPX_OVL_MAX_COLS);
-    for (int i = 0; i < 4; ++i)
-        if (st[i] < 0) return fail("%s: negative stride", who);
-    if ((long long)(C - 1) * st[1] + (long long)(h - 1) * st[2] + (long long)(w - 1) * st[3] >= (1LL << 31))
-        return fail("%s: one image of planes spans more than 2^31 elements", who);
-    return 0;
+    return check_image_strides(who, "", st, C, h, w);
 }
 
 size_t spx_overlap_workspace_bytes(int32_t N, int32_t C, int32_t K) {
@@ -860,8 +866,7 @@ int spx_overlap_accumulate(const float* planes, const int64_t* host_strides, con
     static const char* who = "spx_overlap_accumulate";
     if (!thresholds || !labels || !slot_table || !inter || !area || !images)
         return fail("%s: NULL thresholds / labels / slot table / counters", who);
-    if (label_bytes != 1 && label_bytes != 4 && label_bytes != 8)
-        return fail("%s: label byte code %d (1 = uint8, 4 = int32, 8 = int64)", who, label_bytes);
+    if (int e = check_label_bytes(who, label_bytes)) return e;
     if (K < 1 || K > SPX_EVAL_MAX_CLASSES || J < 1 || J > SPX_OVL_MAX_SLOTS)
         return fail("%s: bad sizes (K=%d J=%d; K <= %d, J <= %d)", who, K, J, SPX_EVAL_MAX_CLASSES, SPX_OVL_MAX_SLOTS);
     if (int e = overlap_check(who, planes, host_strides, N, C, h, w, H, W, workspace)) return e;
@@ -870,15 +875,12 @@ int spx_overlap_accumulate(const float* planes, const int64_t* host_strides, con
                                                     (unsigned long long*)images, workspace, (hipStream_t)stream), who);
 }
 
-#define SPX_PBX_MAX_ROWS (1 << 24)
-
 int spx_push_boxes(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
                    const int32_t* host_rows, const float* thresholds, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
                    int32_t W, int32_t add_margin, int32_t* rf_boxes, int32_t* crops, void* stream) {
     static const char* who = "spx_push_boxes";
     if (!labels || !rows || !thresholds || !rf_boxes || !crops) return fail("%s: NULL labels / rows / thresholds / boxes", who);
-    if (label_bytes != 1 && label_bytes != 4 && label_bytes != 8)
-        return fail("%s: label byte code %d (1 = uint8, 4 = int32, 8 = int64)", who, label_bytes);
+    if (int e = check_label_bytes(who, label_bytes)) return e;
     if (R < 1 || R > SPX_PBX_MAX_ROWS) return fail("%s: %d rows (1..%d)", who, R, SPX_PBX_MAX_ROWS);
     if (add_margin < 0 || add_margin > SPX_OVL_MAX_OUT) return fail("%s: add_margin %d outside 0..%d", who, add_margin, SPX_OVL_MAX_OUT);
     if (int e = overlap_check(who, planes, host_strides, N, C, h, w, H, W, rows)) return e;
@@ -893,15 +895,12 @@ int spx_push_boxes(const float* planes, const int64_t* host_strides, const void*
                                             H, W, add_margin, rf_boxes, crops, (hipStream_t)stream), who);
 }
 
-#define SPX_EXP_MAX_ROWS 65535
-
 // what the three explanation-map entry points check alike
 static int explain_check(const char* who, const float* planes, const int64_t* st, const void* labels, int32_t label_bytes,
                          const int32_t* rows, const int32_t* host_rows, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
                          int32_t W) {
     if (!labels || !rows || !host_rows) return fail("%s: NULL labels / rows / host rows", who);
-    if (label_bytes != 1 && label_bytes != 4 && label_bytes != 8)
-        return fail("%s: label byte code %d (1 = uint8, 4 = int32, 8 = int64)", who, label_bytes);
+    if (int e = check_label_bytes(who, label_bytes)) return e;
     if (R < 1 || R > SPX_EXP_MAX_ROWS) return fail("%s: %d rows (1..%d)", who, R, SPX_EXP_MAX_ROWS);
     return overlap_check(who, planes, st, N, C, h, w, H, W, rows);
 }

@@ -3,7 +3,7 @@
 // upsampled [C, H, W] tensor (1.6-1.9 GB per Cityscapes image) and copies it to the host first
 // (segmentation/eval_valid_multiscale.py:229-234, :375-383).  The source map (<= tens of MB) stays cache-resident:
 // every output pixel reads its 4 neighbours of each channel; neighbouring outputs share them.
-#include "spx_common.h"
+#include "spx_planes.h"
 
 // torch's area_pixel_compute_source_index for align_corners = False (no explicit scale factor): scale = in / out,
 // src = scale * (dst + 0.5) - 0.5 clamped at 0; i0 = floor, i1 = min(i0 + 1, in - 1), lambda1 = src - i0.
@@ -78,11 +78,6 @@ hipError_t spx_launch_upsample_argext(const float* src, int N, int C, int h, int
 #define SPX_EVAL_THREADS 256
 #define SPX_EVAL_FULL_CONF_WORDS 8192
 
-struct EvalMap {                 // element strides of a 4-D fp32 tensor, in (n, channel, y, x) order
-    const float* p;
-    long long sn, sc, sy, sx;
-};
-
 __device__ __forceinline__ float bilerp(const float* __restrict__ q, unsigned o00, unsigned o01, unsigned o10, unsigned o11,
                                         float lx0, float lx1, float ly0, float ly1) {
     const float t0 = __builtin_fmaf(q[o00], lx0, q[o01] * lx1), t1 = __builtin_fmaf(q[o10], lx0, q[o11] * lx1);
@@ -127,12 +122,6 @@ __device__ __forceinline__ void argext_run(const float* __restrict__ q, int sc, 
     }
 }
 
-__device__ __forceinline__ long long read_label(const void* labels, int label_bytes, size_t o) {
-    if (label_bytes == 1) return (long long)((const uint8_t*)labels)[o];
-    if (label_bytes == 4) return (long long)((const int32_t*)labels)[o];
-    return ((const long long*)labels)[o];
-}
-
 // Logits arrive pixel-major ([N, h, w, K]): read straight from memory, the 64 lanes of a wave touch ~9 source pixels
 // K * 4 bytes apart, i.e. ~9 cache lines per load instead of the one line of a channel-major map.  So each tile first
 // copies its source footprint (rows ya..yb, columns xa..xb, all K channels; ~2 x 9 pixels at x8) to LDS channel-major
@@ -150,7 +139,7 @@ __device__ __forceinline__ long long read_label(const void* labels, int label_by
 #define SPX_EVAL_DCHUNK (SPX_EVAL_STAGE / 64)
 
 __global__ __launch_bounds__(SPX_EVAL_ACC_THREADS) void spx_eval_accumulate_kernel(
-    EvalMap lg, EvalMap ds, const int32_t* __restrict__ pcls, const void* __restrict__ labels, int label_bytes, int N, int K,
+    SpxPlanes lg, SpxPlanes ds, const int32_t* __restrict__ pcls, const void* __restrict__ labels, int label_bytes, int N, int K,
     int P, int h, int w, int H, int W, float sh, float sw, int tiles_x, int tiles_y, int full_conf,
     unsigned long long* __restrict__ conf, unsigned long long* __restrict__ hits) {
     extern __shared__ unsigned int s_eval[];
@@ -202,7 +191,7 @@ __global__ __launch_bounds__(SPX_EVAL_ACC_THREADS) void spx_eval_accumulate_kern
             pred = argext_at<true>(lq, lg.sc, K, r0 + c0, r0 + c1, r1 + c0, r1 + c1, lx0, lx1, ly0, ly1);
         }
         if (active) {
-            const long long ann = read_label(labels, label_bytes, ((size_t)n * H + oy) * W + ox);
+            const long long ann = spx_label(labels, label_bytes, ((size_t)n * H + oy) * W + ox);
             if (ann != 0) {
                 const int row = (ann >= 1 && ann <= K) ? (int)(ann - 1) : K;
                 if (full_conf) atomicAdd(&s_conf[row * K + pred], 1u);
@@ -252,7 +241,7 @@ __global__ __launch_bounds__(SPX_EVAL_ACC_THREADS) void spx_eval_accumulate_kern
 // ascending order), hit_rank = (cls(p) == pred), then an inclusive prefix sum of the hits added to the workgroup's
 // topk copy.  Samples outside [0, H) x [0, W) are skipped and not counted as seen.
 __global__ __launch_bounds__(SPX_EVAL_THREADS) void spx_eval_topk_kernel(
-    EvalMap lg, EvalMap ds, const int32_t* __restrict__ pcls, const void* __restrict__ samples, int sample_bytes, int N, int S,
+    SpxPlanes lg, SpxPlanes ds, const int32_t* __restrict__ pcls, const void* __restrict__ samples, int sample_bytes, int N, int S,
     int K, int P, int h, int w, int H, int W, float sh, float sw, unsigned long long* __restrict__ topk,
     unsigned long long* __restrict__ seen) {
     extern __shared__ unsigned int s_eval[];
@@ -355,16 +344,6 @@ __global__ __launch_bounds__(SPX_EVAL_THREADS) void spx_eval_topk_kernel(
     if (tid == 0 && seen && taken) atomicAdd(seen, (unsigned long long)taken);
 }
 
-static inline EvalMap eval_map(const float* p, const long long* st) {
-    EvalMap m;
-    m.p = p;
-    m.sn = p ? st[0] : 0;
-    m.sc = p ? st[1] : 0;
-    m.sy = p ? st[2] : 0;
-    m.sx = p ? st[3] : 0;
-    return m;
-}
-
 // the whole matrix in LDS when it fits beside the hit counters, the class table and the staging area in 64 KiB
 static int spx_eval_full_conf(int K, int P) {
     return (long long)(K + 1) * K <= SPX_EVAL_FULL_CONF_WORDS && (long long)(K + 1) * K + 2 * P + SPX_EVAL_STAGE <= 16384 ? 1 : 0;
@@ -390,8 +369,8 @@ hipError_t spx_launch_eval_accumulate(const float* logits, const long long* lst,
         per_cu = 2;
     const long long cap = (long long)per_cu * cus;
     const unsigned grid = (unsigned)(ntiles < cap ? ntiles : cap);
-    hipLaunchKernelGGL(spx_eval_accumulate_kernel, dim3(grid), dim3(SPX_EVAL_ACC_THREADS), lds, s, eval_map(logits, lst),
-                       eval_map(dist, dst), pcls, labels, label_bytes, N, K, dist ? P : 0, h, w, H, W, sh, sw, tiles_x, tiles_y,
+    hipLaunchKernelGGL(spx_eval_accumulate_kernel, dim3(grid), dim3(SPX_EVAL_ACC_THREADS), lds, s, spx_planes(logits, lst),
+                       spx_planes(dist, dst), pcls, labels, label_bytes, N, K, dist ? P : 0, h, w, H, W, sh, sw, tiles_x, tiles_y,
                        full, conf, hits);
     return hipGetLastError();
 }
@@ -403,7 +382,7 @@ hipError_t spx_launch_eval_topk(const float* logits, const long long* lst, const
     const long long total = (long long)N * S;
     const unsigned grid = (unsigned)(total < 256 ? total : 256);
     const size_t lds = sizeof(unsigned int) * (3 * (size_t)P + (size_t)K);
-    hipLaunchKernelGGL(spx_eval_topk_kernel, dim3(grid), dim3(SPX_EVAL_THREADS), lds, s, eval_map(logits, lst), eval_map(dist, dst), pcls,
+    hipLaunchKernelGGL(spx_eval_topk_kernel, dim3(grid), dim3(SPX_EVAL_THREADS), lds, s, spx_planes(logits, lst), spx_planes(dist, dst), pcls,
                        samples, sample_bytes, N, S, K, P, h, w, H, W, sh, sw, topk, seen);
     return hipGetLastError();
 }

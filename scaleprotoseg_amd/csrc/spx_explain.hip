@@ -32,7 +32,7 @@ struct ExpLabels {
 // ---- range -------------------------------------------------------------------------------------------------------------
 // Band blockIdx.x of heat row blockIdx.y.  keys uint32 [2][R]: running minimum (initialised to all ones) and maximum (zero) of
 // float_key(m).  Wave v takes the band's rows v, v + 4, ..., lane l the columns l, l + 64, ... (the labels are read along X).
-__global__ __launch_bounds__(EXP_THREADS) void spx_explain_range_kernel(OvlPlanes a, ExpLabels labels, const int32_t* __restrict__ rows,
+__global__ __launch_bounds__(EXP_THREADS) void spx_explain_range_kernel(SpxPlanes a, ExpLabels labels, const int32_t* __restrict__ rows,
                                                                         int R, int N, int C, int h, int w, int H, int W, int band_rows,
                                                                         uint32_t* __restrict__ keys) {
     __shared__ float s_stage[OVL_STAGE];
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(EXP_THREADS) void spx_explain_range_kernel(OvlPlane
         ovl_axis(X, w, W, 0, 1, ox, wx);
         for (int i = wave; i < nrows; i += EXP_THREADS / 64) {
             float m = 0.0f;
-            if (ovl_label(labels.p, labels.bytes, label0 + (size_t)(Y0 + i) * W + X) == want)
+            if (spx_label(labels.p, labels.bytes, label0 + (size_t)(Y0 + i) * W + X) == want)
                 m = ovl_value(s_stage, &s_oy[4 * i], &s_wy[4 * i], ox, wx);
             const uint32_t key = float_key(m);
             klo = min(klo, key);
@@ -105,7 +105,7 @@ hipError_t spx_launch_explain_range(const float* planes, const long long* st, co
     if (e != hipSuccess) return e;
     const ExpLabels lab = {labels, label_bytes};
     hipLaunchKernelGGL(spx_explain_range_kernel, dim3((unsigned)((H + band - 1) / band), (unsigned)R), dim3(EXP_THREADS), 0, s,
-                       ovl_planes(planes, st), lab, rows, R, N, C, h, w, H, W, band, keys);
+                       spx_planes(planes, st), lab, rows, R, N, C, h, w, H, W, band, keys);
     return hipGetLastError();
 }
 
@@ -148,7 +148,7 @@ static inline long long exp_image_dwords(int H, int W) { return ((long long)H * 
 struct ExpTaps {
     int Y, oy[4], ox[4];
     float wy[4], wx[4];
-    __device__ __forceinline__ void at(const OvlPlanes& a, int h, int w, int H, int W, int Yn, int Xn) {
+    __device__ __forceinline__ void at(const SpxPlanes& a, int h, int w, int H, int W, int Yn, int Xn) {
         if (Yn != Y) {
             ovl_axis(Yn, h, H, 0, (int)a.sy, oy, wy);
             Y = Yn;
@@ -165,7 +165,7 @@ __device__ __forceinline__ uint32_t exp_heat_byte(float m, float lo, float d) {
 }
 
 struct ExpHeatPixel {
-    OvlPlanes a;
+    SpxPlanes a;
     ExpLabels labels;
     const float* plane;
     size_t label0;
@@ -176,13 +176,13 @@ struct ExpHeatPixel {
     ExpTaps taps;
     __device__ __forceinline__ uint32_t operator()(int Y, int X) {
         if (d == 0.0f) return 0u;
-        if (ovl_label(labels.p, labels.bytes, label0 + (size_t)Y * W + X) != want) return outside;
+        if (spx_label(labels.p, labels.bytes, label0 + (size_t)Y * W + X) != want) return outside;
         taps.at(a, h, w, H, W, Y, X);
         return exp_heat_byte(ovl_value(plane, taps.oy, taps.wy, taps.ox, taps.wx), lo, d);
     }
 };
 
-__global__ __launch_bounds__(EXP_THREADS) void spx_explain_heat_kernel(OvlPlanes a, ExpLabels labels, const int32_t* __restrict__ rows,
+__global__ __launch_bounds__(EXP_THREADS) void spx_explain_heat_kernel(SpxPlanes a, ExpLabels labels, const int32_t* __restrict__ rows,
                                                                        int R, int N, int C, int h, int w, int H, int W,
                                                                        const uint32_t* __restrict__ keys, uint8_t* __restrict__ heat,
                                                                        float* __restrict__ ranges) {
@@ -217,12 +217,12 @@ hipError_t spx_launch_explain_heat(const float* planes, const long long* st, con
     const long long per = (long long)EXP_THREADS * EXP_DWORDS;
     const ExpLabels lab = {labels, label_bytes};
     hipLaunchKernelGGL(spx_explain_heat_kernel, dim3((unsigned)((exp_image_dwords(H, W) + per - 1) / per), (unsigned)R), dim3(EXP_THREADS),
-                       0, s, ovl_planes(planes, st), lab, rows, R, N, C, h, w, H, W, (const uint32_t*)workspace, heat, ranges);
+                       0, s, spx_planes(planes, st), lab, rows, R, N, C, h, w, H, W, (const uint32_t*)workspace, heat, ranges);
     return hipGetLastError();
 }
 
 struct ExpDominantPixel {
-    OvlPlanes a;
+    SpxPlanes a;
     ExpLabels labels;
     const float* image;           // a.p + n * sn
     const int32_t* slots;         // the class's row of the slot table
@@ -232,7 +232,7 @@ struct ExpDominantPixel {
     int C, J, h, w, H, W;
     ExpTaps taps;
     __device__ __forceinline__ uint32_t operator()(int Y, int X) {
-        if (ovl_label(labels.p, labels.bytes, label0 + (size_t)Y * W + X) != want) return EXP_OFF;
+        if (spx_label(labels.p, labels.bytes, label0 + (size_t)Y * W + X) != want) return EXP_OFF;
         taps.at(a, h, w, H, W, Y, X);
         uint32_t best = EXP_OFF;
         float top = 0.0f;
@@ -250,7 +250,7 @@ struct ExpDominantPixel {
     }
 };
 
-__global__ __launch_bounds__(EXP_THREADS) void spx_explain_dominant_kernel(OvlPlanes a, ExpLabels labels, const int32_t* __restrict__ rows,
+__global__ __launch_bounds__(EXP_THREADS) void spx_explain_dominant_kernel(SpxPlanes a, ExpLabels labels, const int32_t* __restrict__ rows,
                                                                            const int32_t* __restrict__ table,
                                                                            const float* __restrict__ weights, int N, int C, int K, int J,
                                                                            int h, int w, int H, int W, uint8_t* __restrict__ dom) {
@@ -281,6 +281,6 @@ hipError_t spx_launch_explain_dominant(const float* planes, const long long* st,
     const long long per = (long long)EXP_THREADS * EXP_DWORDS;
     const ExpLabels lab = {labels, label_bytes};
     hipLaunchKernelGGL(spx_explain_dominant_kernel, dim3((unsigned)((exp_image_dwords(H, W) + per - 1) / per), (unsigned)R),
-                       dim3(EXP_THREADS), 0, s, ovl_planes(planes, st), lab, rows, table, weights, N, C, K, J, h, w, H, W, dom);
+                       dim3(EXP_THREADS), 0, s, spx_planes(planes, st), lab, rows, table, weights, N, C, K, J, h, w, H, W, dom);
     return hipGetLastError();
 }

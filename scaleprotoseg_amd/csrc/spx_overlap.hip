@@ -60,7 +60,7 @@ __device__ __forceinline__ void ovl_count(uint32_t* hist, int& cur, uint32_t& ru
 // Histogram round `round` (0, 1, 2) of the band of output rows blockIdx.x of plane (blockIdx.z, blockIdx.y).  The band's
 // latent rows plus the halo of the cubic taps are staged in LDS; wave v takes the band's rows v, v + 4, ..., lane l the
 // columns l, l + 64, ...
-__global__ __launch_bounds__(OVL_THREADS) void spx_overlap_hist_kernel(OvlPlanes a, int C, int h, int w, int H, int W, int band_rows,
+__global__ __launch_bounds__(OVL_THREADS) void spx_overlap_hist_kernel(SpxPlanes a, int C, int h, int w, int H, int W, int band_rows,
                                                                        int round, const uint32_t* __restrict__ state,
                                                                        uint32_t* __restrict__ hist) {
     __shared__ float s_stage[OVL_STAGE];
@@ -175,7 +175,7 @@ hipError_t spx_launch_overlap_thresholds(const float* planes, const long long* s
     if (band < 1 || (long long)ovl_max_staged_rows(h, H, band) * w > OVL_STAGE) return hipErrorInvalidValue;
     hipLaunchKernelGGL(spx_overlap_init_kernel, dim3((unsigned)np), dim3(OVL_THREADS), 0, s, state, hist, (uint32_t)k, (uint32_t)k1);
     const dim3 grid((unsigned)((H + band - 1) / band), (unsigned)C, (unsigned)N);
-    const OvlPlanes a = ovl_planes(planes, st);
+    const SpxPlanes a = spx_planes(planes, st);
     for (int round = 0; round < 3; ++round) {
         hipLaunchKernelGGL(spx_overlap_hist_kernel, grid, dim3(OVL_THREADS), 0, s, a, C, h, w, H, W, band, round, state, hist);
         hipLaunchKernelGGL(spx_overlap_scan_kernel, dim3((unsigned)np), dim3(OVL_THREADS), 0, s, round, state, hist, gamma, thresholds);
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(OVL_THREADS) void spx_overlap_presence_kernel(const
     for (int i = tid; i < K; i += OVL_THREADS) s_seen[i] = 0;
     __syncthreads();
     for (long long i = (long long)blockIdx.x * OVL_THREADS + tid; i < HW; i += (long long)gridDim.x * OVL_THREADS) {
-        const long long ann = ovl_label(labels, label_bytes, (size_t)n * HW + i);
+        const long long ann = spx_label(labels, label_bytes, (size_t)n * HW + i);
         if (ann >= 1 && ann <= K) s_seen[ann - 1] = 1;
     }
     __syncthreads();
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(OVL_THREADS) void spx_overlap_presence_kernel(const
 // row-major order; j == j' is the area) to its registers.  Rows without any pixel above a threshold (most of them at
 // q = 0.95) skip the pairs.
 __global__ __launch_bounds__(OVL_THREADS) void spx_overlap_count_kernel(
-    OvlPlanes a, const float* __restrict__ thresholds, const int32_t* __restrict__ table, const int32_t* __restrict__ presence, int C,
+    SpxPlanes a, const float* __restrict__ thresholds, const int32_t* __restrict__ table, const int32_t* __restrict__ presence, int C,
     int K, int J, int h, int w, int H, int W, int tiles_x, unsigned long long* __restrict__ inter, unsigned long long* __restrict__ area,
     unsigned long long* __restrict__ images) {
     __shared__ unsigned long long s_b[4][OVL_MAX_J];
@@ -294,6 +294,6 @@ hipError_t spx_launch_overlap_accumulate(const float* planes, const long long* s
                        labels, label_bytes, K, HW, presence);
     const int tiles_x = (W + 63) / 64, tiles_y = (H + OVL_CNT_ROWS - 1) / OVL_CNT_ROWS;
     hipLaunchKernelGGL(spx_overlap_count_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)K, (unsigned)N), dim3(OVL_THREADS), 0, s,
-                       ovl_planes(planes, st), thresholds, table, presence, C, K, J, h, w, H, W, tiles_x, inter, area, images);
+                       spx_planes(planes, st), thresholds, table, presence, C, K, J, h, w, H, W, tiles_x, inter, area, images);
     return hipGetLastError();
 }

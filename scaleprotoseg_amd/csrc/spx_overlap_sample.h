@@ -1,25 +1,10 @@
 // What the activation-overlap metrics (spx_overlap.hip), the push bounding boxes (spx_pushbox.hip) and the explanation maps
-// (spx_explain.hip) share: the upsampled value of a pixel recomputed from the latent plane, the strided view of the planes, the
-// label read and the bands of output rows that stage their latent rows in LDS.  ONE function, compiled with -ffp-contract=off,
-// gives a pixel the same bits in every pass of every file.
+// (spx_explain.hip) share: the upsampled value of a pixel recomputed from the latent plane and the bands of output rows that
+// stage their latent rows in LDS (the strided view of the planes and the label read come from spx_planes.h).  ONE function,
+// compiled with -ffp-contract=off, gives a pixel the same bits in every pass of every file.
 #ifndef SPX_OVERLAP_SAMPLE_H
 #define SPX_OVERLAP_SAMPLE_H
-#include "spx_common.h"
-
-struct OvlPlanes {                // element strides of a 4-D fp32 tensor, in (n, channel, y, x) order
-    const float* p;
-    long long sn, sc, sy, sx;
-};
-
-static inline OvlPlanes ovl_planes(const float* p, const long long* st) {
-    OvlPlanes m;
-    m.p = p;
-    m.sn = st[0];
-    m.sc = st[1];
-    m.sy = st[2];
-    m.sx = st[3];
-    return m;
-}
+#include "spx_planes.h"
 
 // ---- the upsampled value ---------------------------------------------------------------------------------------------
 // Source coordinate of output index d for `in` source and `out` output samples: s = (d + 0.5) * in / out - 0.5, taken
@@ -68,12 +53,6 @@ __device__ __forceinline__ float ovl_value(const float* p, const int* oy, const 
         v = a == 0 ? row * wy[0] : v + row * wy[a];
     }
     return v;
-}
-
-__device__ __forceinline__ long long ovl_label(const void* labels, int label_bytes, size_t o) {
-    if (label_bytes == 1) return (long long)((const uint8_t*)labels)[o];
-    if (label_bytes == 4) return (long long)((const int32_t*)labels)[o];
-    return ((const long long*)labels)[o];
 }
 
 // ---- bands of output rows whose latent footprint is staged in LDS --------------------------------------------------------

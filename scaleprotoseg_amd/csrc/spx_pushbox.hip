@@ -34,7 +34,7 @@ struct PbxRow {                   // what the "any" queries of one row share
 };
 
 __device__ __forceinline__ bool pbx_hit(const PbxRow& r, int Y, int X) {
-    if (ovl_label(r.labels, r.label_bytes, r.label0 + (size_t)Y * r.W + X) != r.want) return r.outside_hits;
+    if (spx_label(r.labels, r.label_bytes, r.label0 + (size_t)Y * r.W + X) != r.want) return r.outside_hits;
     int ox[4], oy[4];
     float wx[4], wy[4];
     ovl_axis(Y, r.h, r.H, 0, r.sy, oy, wy);
@@ -57,7 +57,7 @@ __device__ __forceinline__ bool pbx_any(const PbxRow& r, int Y0, int X0, int dY,
     return s_any[slot] != 0;
 }
 
-__global__ __launch_bounds__(PBX_THREADS) void spx_push_boxes_kernel(OvlPlanes a, const void* __restrict__ labels, int label_bytes,
+__global__ __launch_bounds__(PBX_THREADS) void spx_push_boxes_kernel(SpxPlanes a, const void* __restrict__ labels, int label_bytes,
                                                                      const int32_t* __restrict__ rows, const float* __restrict__ thresholds,
                                                                      int N, int C, int h, int w, int H, int W, int add_margin,
                                                                      int32_t* __restrict__ rf_boxes, int32_t* __restrict__ crops) {
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(PBX_THREADS) void spx_push_boxes_kernel(OvlPlanes a
 hipError_t spx_launch_push_boxes(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
                                  const float* thresholds, int R, int N, int C, int h, int w, int H, int W, int add_margin,
                                  int32_t* rf_boxes, int32_t* crops, hipStream_t s) {
-    hipLaunchKernelGGL(spx_push_boxes_kernel, dim3((unsigned)R), dim3(PBX_THREADS), 0, s, ovl_planes(planes, st), labels, label_bytes,
+    hipLaunchKernelGGL(spx_push_boxes_kernel, dim3((unsigned)R), dim3(PBX_THREADS), 0, s, spx_planes(planes, st), labels, label_bytes,
                        rows, thresholds, N, C, h, w, H, W, add_margin, rf_boxes, crops);
     return hipGetLastError();
 }

@@ -31,22 +31,12 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _lib
+from . import _lib, _maps
 from ._lib import SpxError
-from .metrics import _LABEL_BYTES, _strides
-from .overlap import MAX_SLOTS, _group_slot_table, _input_planes, _planes
+from ._maps import LABEL_BYTES, bad_row, host_rows, strides
 
 OFF_CLASS = 255                  # the dominant map outside the class
 MAX_ROWS = 65535                 # rows of one launch; longer row tables are cut into launches
-
-
-def _host_table(slot_table) -> torch.Tensor:
-    table = torch.as_tensor(slot_table).detach().cpu()
-    if table.dim() != 2 or table.shape[0] < 1 or table.shape[1] < 1 or table.is_floating_point():
-        raise SpxError(f"slot_table must be integer [K, J] with K, J >= 1 (got {table.dtype} {tuple(table.shape)})")
-    if table.shape[1] > MAX_SLOTS:
-        raise SpxError(f"{table.shape[1]} slots per class (at most {MAX_SLOTS})")
-    return table.to(torch.int32).contiguous()
 
 
 def _check_channels(table: torch.Tensor, C: int) -> None:
@@ -54,43 +44,11 @@ def _check_channels(table: torch.Tensor, C: int) -> None:
         raise SpxError(f"activations have {C} channels, the slot table names channel {int(table.max())}")
 
 
-def _host_rows(rows, width: int, what: str) -> torch.Tensor:
-    if not isinstance(rows, torch.Tensor):
-        rows = torch.as_tensor(rows)
-    if rows.is_cuda:
-        raise SpxError("rows must be a host tensor: every row is checked on the host before any launch (rows_for returns such)")
-    if rows.dim() != 2 or rows.shape[1] != width or rows.shape[0] < 1 or rows.is_floating_point():
-        raise SpxError(f"rows must be integer [R, {width}] = {what} with R >= 1 (got {rows.dtype} {tuple(rows.shape)})")
-    return rows.detach().to(torch.int64)
-
-
-def _bad_row(rows: torch.Tensor, bad: torch.Tensor, why: str) -> None:
-    if bool(bad.any()):
-        r = int(bad.nonzero()[0])
-        raise SpxError(f"row {r} = {tuple(rows[r].tolist())}: {why}")
-
-
 def _checked(activations, labels, grid):
     """(planes, N, C, h, w, H, W) of inputs whose shapes and types fit; nothing here needs the device."""
-    planes = _planes(activations, grid, "activations")
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype not in _LABEL_BYTES:
-        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, torch.Tensor) else type(labels).__name__
-        raise SpxError(f"labels must be uint8, int32 or int64 [N, H, W] (got {got})")
+    planes = _maps.planes(activations, grid, "activations")
     N, C, h, w = (int(v) for v in planes.shape)
-    if labels.shape[0] != N:
-        raise SpxError(f"labels hold {labels.shape[0]} images, activations {N}")
-    return planes, N, C, h, w, int(labels.shape[1]), int(labels.shape[2])
-
-
-def _on_device(planes: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    _lib.require_gpu(planes, "activations")
-    _lib.require_gpu(labels, "labels")
-    if labels.device != planes.device:
-        raise SpxError(f"labels are on {labels.device}, activations on {planes.device}")
-    if torch.cuda.current_device() != planes.device.index:
-        raise SpxError(f"current device cuda:{torch.cuda.current_device()} is not the activations' {planes.device}: the kernels "
-                       "run on the current device's stream")
-    return labels.detach().contiguous()
+    return (planes, N, C, h, w, *_maps.label_map(labels, N, "activations"))
 
 
 def _upload(host: torch.Tensor, device) -> torch.Tensor:
@@ -116,15 +74,15 @@ def activation_heat_maps(activations: torch.Tensor, labels: torch.Tensor, rows, 
     uint8 [R, H, W] tensor to write into (any alignment; every byte is written exactly once).  Enqueues work on the current
     stream only; never synchronises."""
     planes, N, C, h, w, H, W = _checked(activations, labels, grid)
-    table = _host_table(slot_table)
+    table = _maps.slot_table(slot_table)
     _check_channels(table, C)
     K, J = (int(v) for v in table.shape)
-    rows = _host_rows(rows, 3, "(n, k, j)")
+    rows = host_rows(rows, 3, "(n, k, j)")
     n, k, j = rows[:, 0], rows[:, 1], rows[:, 2]
-    _bad_row(rows, (n < 0) | (n >= N) | (k < 0) | (k >= K) | (j < 0) | (j >= J), f"outside N={N}, K={K}, J={J}")
+    bad_row(rows, (n < 0) | (n >= N) | (k < 0) | (k >= K) | (j < 0) | (j >= J), f"outside N={N}, K={K}, J={J}")
     c = table.to(torch.int64)[k, j]
-    _bad_row(rows, c < 0, "the class has no such slot")
-    lab = _on_device(planes, labels)
+    bad_row(rows, c < 0, "the class has no such slot")
+    lab = _maps.device_labels(planes, labels)
     lib = _lib.load()
     R = int(rows.shape[0])
     heat = _output(out, (R, H, W), planes.device)
@@ -132,10 +90,10 @@ def activation_heat_maps(activations: torch.Tensor, labels: torch.Tensor, rows, 
     host = torch.stack([n, c, k], dim=1).to(torch.int32).contiguous()
     dev = _upload(host, planes.device)
     keys = torch.empty(2 * min(R, MAX_ROWS), dtype=torch.int32, device=planes.device)
-    st, stream = _strides(planes, (0, 1, 2, 3)), _lib.stream_ptr()
+    st, stream = strides(planes), _lib.stream_ptr()
     for r0 in range(0, R, MAX_ROWS):
         r1 = min(R, r0 + MAX_ROWS)
-        common = (planes.data_ptr(), st, lab.data_ptr(), _LABEL_BYTES[lab.dtype], dev[r0:r1].data_ptr(), host[r0:r1].data_ptr(),
+        common = (planes.data_ptr(), st, lab.data_ptr(), LABEL_BYTES[lab.dtype], dev[r0:r1].data_ptr(), host[r0:r1].data_ptr(),
                   r1 - r0, N, C, h, w, H, W, keys.data_ptr())
         _lib.check(lib.spx_explain_range(*common, stream))
         _lib.check(lib.spx_explain_heat(*common, heat[r0:r1].data_ptr(), ranges[r0:r1].data_ptr(), stream))
@@ -149,18 +107,18 @@ def dominant_slot_maps(activations: torch.Tensor, labels: torch.Tensor, rows, sl
     on the host (pass a host tensor: a device tensor is copied back first).  ``weights``: fp32 [K, J] on the device (read
     there, never by the host), or None = 1.  The other arguments as ``activation_heat_maps`` takes them.  Enqueues work on the
     current stream only; never synchronises."""
-    return _dominant(activations, labels, rows, _host_table(slot_table), None, weights, grid, out)
+    return _dominant(activations, labels, rows, _maps.slot_table(slot_table), None, weights, grid, out)
 
 
 def _dominant(activations, labels, rows, table: torch.Tensor, dev_table: Optional[torch.Tensor], weights, grid, out) -> torch.Tensor:
     planes, N, C, h, w, H, W = _checked(activations, labels, grid)
     _check_channels(table, C)
     K, J = (int(v) for v in table.shape)
-    rows = _host_rows(rows, 2, "(n, k)")
-    _bad_row(rows, (rows[:, 0] < 0) | (rows[:, 0] >= N) | (rows[:, 1] < 0) | (rows[:, 1] >= K), f"outside N={N}, K={K}")
+    rows = host_rows(rows, 2, "(n, k)")
+    bad_row(rows, (rows[:, 0] < 0) | (rows[:, 0] >= N) | (rows[:, 1] < 0) | (rows[:, 1] >= K), f"outside N={N}, K={K}")
     if weights is not None and (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != (K, J)):
         raise SpxError(f"weights must be fp32 [{K}, {J}]")
-    lab = _on_device(planes, labels)
+    lab = _maps.device_labels(planes, labels)
     if weights is not None:
         _lib.require_gpu(weights, "weights")
         if weights.device != planes.device:
@@ -173,10 +131,10 @@ def _dominant(activations, labels, rows, table: torch.Tensor, dev_table: Optiona
     dev = _upload(host, planes.device)
     if dev_table is None:
         dev_table = _upload(table, planes.device)
-    st, stream = _strides(planes, (0, 1, 2, 3)), _lib.stream_ptr()
+    st, stream = strides(planes), _lib.stream_ptr()
     for r0 in range(0, R, MAX_ROWS):
         r1 = min(R, r0 + MAX_ROWS)
-        _lib.check(lib.spx_explain_dominant(planes.data_ptr(), st, lab.data_ptr(), _LABEL_BYTES[lab.dtype], dev[r0:r1].data_ptr(),
+        _lib.check(lib.spx_explain_dominant(planes.data_ptr(), st, lab.data_ptr(), LABEL_BYTES[lab.dtype], dev[r0:r1].data_ptr(),
                                             host[r0:r1].data_ptr(), dev_table.data_ptr(), _lib.ptr(weights), r1 - r0, N, C, K, J, h, w,
                                             H, W, dom[r0:r1].data_ptr(), stream))
     return dom
@@ -195,7 +153,7 @@ class ExplanationMaps:
 
     def __init__(self, num_classes: int, slot_table, weight_source=None):
         self.num_classes = K = int(num_classes)
-        self.slot_table = _host_table(slot_table)
+        self.slot_table = _maps.slot_table(slot_table)
         if K < 1 or self.slot_table.shape[0] != K:
             raise SpxError(f"slot_table must be [{K}, J] with J >= 1")
         self.num_slots = int(self.slot_table.shape[1])
@@ -220,7 +178,7 @@ class ExplanationMaps:
         """Slots = the groups of each class, as ``ActivationOverlap.for_groups`` numbers them; the weight of (k, j) is
         ``last_layer_group.weight[k, channel of (k, j)]`` (sample_activations_group.py:92-95), gathered on the device at every
         call: an optimizer step or a loaded checkpoint is seen without any cache to invalidate."""
-        table, sizes = _group_slot_table(ppnet)
+        table, sizes = _maps.group_slot_table(ppnet)
         index = (torch.arange(table.shape[0]).unsqueeze(1).expand_as(table).contiguous(), table.clamp_min(0), table >= 0)
         head = ppnet.last_layer_group
         on: Dict[torch.device, tuple] = {}
@@ -239,7 +197,7 @@ class ExplanationMaps:
         return ex
 
     def _inputs(self, activations, distances, grid):
-        return _input_planes(activations, distances, grid, self._similarity, self._group_sizes, "ExplanationMaps")
+        return _maps.input_planes(activations, distances, grid, self._similarity, self._group_sizes, "ExplanationMaps")
 
     def _table_on(self, device: torch.device) -> torch.Tensor:
         """The device copy of the slot table, made at the first call on ``device`` (a blocking copy, once)."""
@@ -251,8 +209,7 @@ class ExplanationMaps:
         """(rows int64 [R, 3] = (n, k, j), rows2 int64 [R2, 2] = (n, k)), host tensors: every slot, and every class with a
         slot, of the classes present in each image, in ascending (n, k, j) order: what the reference's loop over
         ``np.unique(gt_ann)`` plots.  Presence is counted where the labels live and copied once: ONE host synchronisation."""
-        if labels.dim() != 3 or labels.dtype not in _LABEL_BYTES:
-            raise SpxError(f"labels must be uint8, int32 or int64 [N, H, W] (got {labels.dtype} {tuple(labels.shape)})")
+        _maps.label_map(labels)
         N, K = int(labels.shape[0]), self.num_classes
         lab = labels.detach().reshape(N, -1).to(torch.int64)
         lab = torch.where((lab >= 1) & (lab <= K), lab, torch.zeros_like(lab))

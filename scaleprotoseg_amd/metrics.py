@@ -18,18 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import SpxError
-
-_LABEL_BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
-
-
-def _dev_ptr(t: torch.Tensor, name: str) -> int:
-    _lib.require_gpu(t, name)
-    return t.data_ptr()
-
-
-def _strides(t: torch.Tensor, order) -> C.Array:
-    st = t.stride()
-    return (C.c_int64 * 4)(*[int(st[i]) for i in order])
+from ._maps import LABEL_BYTES, dev_ptr, label_map, on_device, strides
 
 
 def prototype_classes(prototype_class_identity: torch.Tensor) -> torch.Tensor:
@@ -41,20 +30,17 @@ def prototype_classes(prototype_class_identity: torch.Tensor) -> torch.Tensor:
 
 
 def _check_maps(logits: torch.Tensor, labels: torch.Tensor, distances: Optional[torch.Tensor]):
+    """(H, W) of inputs whose shapes and types fit; nothing here needs the device."""
     if logits.dim() != 4 or logits.dtype != torch.float32:
         raise SpxError("logits must be fp32 [N, h, w, K]")
-    if labels.dim() != 3:
-        raise SpxError("labels must be [N, H, W]")
-    if labels.dtype not in _LABEL_BYTES:
-        raise SpxError(f"labels must be uint8, int32 or int64 (got {labels.dtype})")
     N, h, w, _ = logits.shape
-    if labels.shape[0] != N:
-        raise SpxError(f"labels hold {labels.shape[0]} images, logits {N}")
+    H, W = label_map(labels, N, "logits")
     if distances is not None:
         if distances.dim() != 4 or distances.dtype != torch.float32:
             raise SpxError("distances must be fp32 [N, P, h, w]")
         if distances.shape[0] != N or tuple(distances.shape[2:]) != (h, w):
             raise SpxError(f"distances {tuple(distances.shape)} do not match logits {tuple(logits.shape)}")
+    return H, W
 
 
 def eval_accumulate(logits: torch.Tensor, labels: torch.Tensor, conf: torch.Tensor, distances: Optional[torch.Tensor] = None,
@@ -63,9 +49,8 @@ def eval_accumulate(logits: torch.Tensor, labels: torch.Tensor, conf: torch.Tens
     [N, h, w, K] and ``distances`` fp32 [N, P, h, w] are read through their strides; ``labels`` [N, H, W] set the output
     size.  ``proto_class`` is the device int32 table of :func:`prototype_classes`."""
     lib = _lib.load()
-    _check_maps(logits, labels, distances)
+    H, W = _check_maps(logits, labels, distances)
     N, h, w, K = logits.shape
-    H, W = int(labels.shape[1]), int(labels.shape[2])
     if conf.dtype != torch.int64 or conf.numel() != (K + 1) * K:
         raise SpxError(f"conf must be int64 with {(K + 1) * K} elements")
     lab = labels.detach().contiguous()
@@ -78,9 +63,9 @@ def eval_accumulate(logits: torch.Tensor, labels: torch.Tensor, conf: torch.Tens
             raise SpxError("distances need proto_class and hits")
         if proto_class.dtype != torch.int32 or proto_class.numel() != P or hits.dtype != torch.int64 or hits.numel() != P:
             raise SpxError(f"proto_class must be int32 and hits int64, both with {P} elements")
-        dptr, dst, cptr, hptr = _dev_ptr(d, "distances"), _strides(d, (0, 1, 2, 3)), _lib.ptr(proto_class), _lib.ptr(hits)
-    _lib.check(lib.spx_eval_accumulate(_dev_ptr(lg, "logits"), _strides(lg, (0, 3, 1, 2)), dptr, dst, cptr,
-                                       _dev_ptr(lab, "labels"), _LABEL_BYTES[lab.dtype], N, K, P, h, w, H, W,
+        dptr, dst, cptr, hptr = dev_ptr(d, "distances"), strides(d), _lib.ptr(proto_class), _lib.ptr(hits)
+    _lib.check(lib.spx_eval_accumulate(dev_ptr(lg, "logits"), strides(lg, (0, 3, 1, 2)), dptr, dst, cptr,
+                                       dev_ptr(lab, "labels"), LABEL_BYTES[lab.dtype], N, K, P, h, w, H, W,
                                        _lib.ptr(conf), hptr, _lib.stream_ptr()))
 
 
@@ -102,11 +87,11 @@ def eval_topk(logits: torch.Tensor, distances: torch.Tensor, proto_class: torch.
     if seen is not None and (seen.dtype != torch.int64 or seen.numel() != 1):
         raise SpxError("seen must be one int64")
     S = int(samples.shape[1])
-    _dev_ptr(samples, "samples")
+    dev_ptr(samples, "samples")
     smp = samples.detach().contiguous()
     lg, d = logits.detach(), distances.detach()
-    _lib.check(lib.spx_eval_topk(_dev_ptr(lg, "logits"), _strides(lg, (0, 3, 1, 2)), _dev_ptr(d, "distances"),
-                                 _strides(d, (0, 1, 2, 3)), _lib.ptr(proto_class), _lib.ptr(smp), smp.element_size(), N, S, K, P, h, w,
+    _lib.check(lib.spx_eval_topk(dev_ptr(lg, "logits"), strides(lg, (0, 3, 1, 2)), dev_ptr(d, "distances"),
+                                 strides(d), _lib.ptr(proto_class), _lib.ptr(smp), smp.element_size(), N, S, K, P, h, w,
                                  int(size[0]), int(size[1]), _lib.ptr(topk), _lib.ptr(seen), _lib.stream_ptr()))
 
 
@@ -220,14 +205,7 @@ class SegmentationMetrics:
             raise SpxError(f"distances must be [N, {self.num_prototypes}, h, w] (and the metrics built with a class identity)")
         if samples is not None and distances is None:
             raise SpxError("samples need distances")
-        for t, name in ((logits, "logits"), (labels, "labels"), (distances, "distances"), (samples, "samples")):
-            if t is not None:
-                _dev_ptr(t, name)
-                if t.device != self.device:
-                    raise SpxError(f"{name} is on {t.device}, the metrics' counters on {self.device}")
-        if torch.cuda.current_device() != self.device.index:
-            raise SpxError(f"current device cuda:{torch.cuda.current_device()} is not the metrics' {self.device}: the "
-                           "kernels run on the current device's stream")
+        on_device(((logits, "logits"), (labels, "labels"), (distances, "distances"), (samples, "samples")), self.device, "metrics")
         eval_accumulate(logits, labels, self.conf, distances, self.proto_class, None if distances is None else self.hits)
         if samples is not None:
             eval_topk(logits, distances, self.proto_class, samples, labels.shape[1:], self.topk, self.samples_seen)

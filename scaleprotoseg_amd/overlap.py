@@ -31,59 +31,9 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _lib
+from . import _lib, _maps
 from ._lib import SpxError
-from .metrics import _LABEL_BYTES, _dev_ptr, _strides
-
-MAX_SLOTS = 32
-
-
-def _planes(t: torch.Tensor, grid: Optional[Tuple[int, int]], name: str) -> torch.Tensor:
-    """[N, C, h, w] view (any strides) of ``t``: 4-D as it is, or the pixel-major [M, C] output of
-    ``forward_from_conv_features(return_activations=True)`` with ``grid`` = (h, w)."""
-    if t.dtype != torch.float32:
-        raise SpxError(f"{name} must be fp32 (got {t.dtype})")
-    if t.dim() == 4:
-        return t.detach()
-    if t.dim() == 2 and grid is not None:
-        h, w = int(grid[0]), int(grid[1])
-        if h < 1 or w < 1 or t.shape[0] % (h * w) != 0:
-            raise SpxError(f"{name} has {t.shape[0]} rows, not a multiple of the grid {h} x {w}")
-        return t.detach().view(t.shape[0] // (h * w), h, w, t.shape[1]).permute(0, 3, 1, 2)
-    raise SpxError(f"{name} must be [N, C, h, w], or [M, C] with grid=(h, w)")
-
-
-def _input_planes(activations, distances, grid, similarity, group_sizes, owner: str) -> torch.Tensor:
-    """The [N, C, h, w] planes of what ``update`` (and the explanation maps) accept: activations as ``_planes`` takes them,
-    ``distances=`` through the model's ``similarity`` (``for_prototypes``), or the list ``compute_group`` returns, concatenated
-    (``for_groups``, ``group_sizes`` = its widths)."""
-    if (activations is None) == (distances is None):
-        raise SpxError("pass either activations or distances=")
-    if distances is not None:
-        if similarity is None:
-            raise SpxError(f"distances= needs {owner}.for_prototypes(ppnet)")
-        _dev_ptr(distances, "distances")
-        activations = similarity(_planes(distances, grid, "distances"))
-    elif isinstance(activations, (list, tuple)):
-        if group_sizes is None or [int(t.shape[-1]) for t in activations] != group_sizes:
-            raise SpxError(f"a list of activations must be what compute_group returns for {owner}.for_groups(ppnet)")
-        for t in activations:
-            _dev_ptr(t, "activations")
-        activations = torch.cat([t.detach() for t in activations], dim=1)
-    return _planes(activations, grid, "activations")
-
-
-def _group_slot_table(ppnet) -> Tuple[torch.Tensor, list]:
-    """([K, J] channel of (class, group) in the concatenation of ``compute_group``'s list, -1 = no such group; its widths)."""
-    sizes = [int(gp.weight.shape[0]) for gp in ppnet.group_projection]
-    if len(sizes) != ppnet.num_classes:
-        raise SpxError(f"{len(sizes)} group projections for {ppnet.num_classes} classes")
-    table = torch.full((len(sizes), max(1, max(sizes))), -1, dtype=torch.long)
-    c0 = 0
-    for k, g in enumerate(sizes):
-        table[k, :g] = torch.arange(c0, c0 + g)
-        c0 += g
-    return table, sizes
+from ._maps import LABEL_BYTES, dev_ptr, strides
 
 
 def _rank(q: float, count: int) -> Tuple[int, float]:
@@ -113,7 +63,7 @@ def _thresholds(lib, planes: torch.Tensor, size, q: float, workspace: torch.Tens
         raise SpxError(f"size must be positive (got {H} x {W})")
     k, gamma = _rank(q, H * W)
     out = torch.empty(N, Cn, dtype=torch.float32, device=planes.device)
-    _lib.check(lib.spx_overlap_thresholds(_dev_ptr(planes, "activations"), _strides(planes, (0, 1, 2, 3)), N, Cn, h, w, H, W, k, gamma,
+    _lib.check(lib.spx_overlap_thresholds(dev_ptr(planes, "activations"), strides(planes), N, Cn, h, w, H, W, k, gamma,
                                           _lib.ptr(workspace), _lib.ptr(out), _lib.stream_ptr()))
     return out
 
@@ -124,8 +74,8 @@ def high_activation_threshold(activations: torch.Tensor, size, q: float = 0.95, 
     ``activations`` is [N, C, h, w] with any strides, or pixel-major [M, C] with ``grid`` = (h, w)."""
     lib = _lib.load()
     _rank(q, 2)
-    planes = _planes(activations, grid, "activations")
-    _dev_ptr(planes, "activations")
+    planes = _maps.planes(activations, grid, "activations")
+    dev_ptr(planes, "activations")
     N, Cn = int(planes.shape[0]), int(planes.shape[1])
     return _thresholds(lib, planes, size, q, _workspace(lib, N, Cn, 1, planes.device))
 
@@ -173,14 +123,12 @@ class ActivationOverlap:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.num_classes = K = int(num_classes)
-        table = slot_table.detach().cpu()
-        if K < 1 or table.dim() != 2 or table.shape[0] != K or table.shape[1] < 1:
+        table = _maps.slot_table(slot_table)
+        if K < 1 or table.shape[0] != K:
             raise SpxError(f"slot_table must be [{K}, J] with J >= 1")
-        if table.shape[1] > MAX_SLOTS:
-            raise SpxError(f"{table.shape[1]} slots per class (at most {MAX_SLOTS})")
         _rank(quantile, 2)
         self.quantile = float(quantile)
-        self.slot_table_host = table.to(torch.int32).contiguous()
+        self.slot_table_host = table
         self.num_slots = J = int(table.shape[1])
         self.num_channels = int(table.max().item()) + 1
         self.slot_table = self.slot_table_host.to(self.device)
@@ -210,7 +158,7 @@ class ActivationOverlap:
         that list.  ``update`` takes the list or its concatenation ([M, U] with ``grid``, or [N, U, h, w])."""
         if device is None:
             device = ppnet.prototype_vectors.device
-        table, sizes = _group_slot_table(ppnet)
+        table, sizes = _maps.group_slot_table(ppnet)
         m = cls(ppnet.num_classes, table, device, quantile)
         m.num_channels = sum(sizes)
         m._group_sizes = sizes
@@ -228,27 +176,16 @@ class ActivationOverlap:
         lib = _lib.load()
         if labels is None:
             raise SpxError("labels are required")
-        planes = _input_planes(activations, distances, grid, self._similarity, self._group_sizes, "ActivationOverlap")
-        if labels.dim() != 3 or labels.dtype not in _LABEL_BYTES:
-            raise SpxError(f"labels must be uint8, int32 or int64 [N, H, W] (got {labels.dtype} {tuple(labels.shape)})")
-        for t, name in ((planes, "activations"), (labels, "labels")):
-            _dev_ptr(t, name)
-            if t.device != self.device:
-                raise SpxError(f"{name} is on {t.device}, the overlap counters on {self.device}")
-        if torch.cuda.current_device() != self.device.index:
-            raise SpxError(f"current device cuda:{torch.cuda.current_device()} is not the counters' {self.device}: the "
-                           "kernels run on the current device's stream")
+        planes = _maps.input_planes(activations, distances, grid, self._similarity, self._group_sizes, "ActivationOverlap")
         N, Cn, h, w = (int(v) for v in planes.shape)
-        if labels.shape[0] != N:
-            raise SpxError(f"labels hold {labels.shape[0]} images, activations {N}")
+        H, W = _maps.label_map(labels, N, "activations")
         if Cn < self.num_channels:
             raise SpxError(f"activations have {Cn} channels, the slot table names channel {self.num_channels - 1}")
-        H, W = int(labels.shape[1]), int(labels.shape[2])
-        lab = labels.detach().contiguous()
+        lab = _maps.device_labels(planes, labels, "activations", self.device, "counters")
         ws = _workspace(lib, N, Cn, self.num_classes, self.device)
         thr = _thresholds(lib, planes, (H, W), self.quantile, ws)
-        _lib.check(lib.spx_overlap_accumulate(planes.data_ptr(), _strides(planes, (0, 1, 2, 3)), _lib.ptr(thr), lab.data_ptr(),
-                                              _LABEL_BYTES[lab.dtype], _lib.ptr(self.slot_table), N, Cn, self.num_classes,
+        _lib.check(lib.spx_overlap_accumulate(planes.data_ptr(), strides(planes), _lib.ptr(thr), lab.data_ptr(),
+                                              LABEL_BYTES[lab.dtype], _lib.ptr(self.slot_table), N, Cn, self.num_classes,
                                               self.num_slots, h, w, H, W, _lib.ptr(self.inter), _lib.ptr(self.area),
                                               _lib.ptr(self.images), _lib.ptr(ws), _lib.stream_ptr()))
 

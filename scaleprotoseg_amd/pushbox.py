@@ -32,10 +32,10 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, _maps
 from ._lib import SpxError
-from .metrics import _LABEL_BYTES, _dev_ptr, _strides
-from .overlap import _planes, _rank, _thresholds, _workspace
+from ._maps import LABEL_BYTES, strides
+from .overlap import _rank, _thresholds, _workspace
 
 _MAX_SELECT_PLANES = 4096       # channels of one spx_overlap_thresholds call
 
@@ -65,27 +65,24 @@ def push_bounding_boxes(activations: torch.Tensor, labels: torch.Tensor, rows: t
     synchronises."""
     lib = _lib.load()
     _rank(q, 2)
-    planes = _planes(activations, grid, "activations")
-    _dev_ptr(planes, "activations")
-    _dev_ptr(labels, "labels")
-    if labels.dim() != 3 or labels.dtype not in _LABEL_BYTES:
-        raise SpxError(f"labels must be uint8, int32 or int64 [N, H, W] (got {labels.dtype} {tuple(labels.shape)})")
+    planes = _maps.planes(activations, grid, "activations")
     N, Cn, h, w = (int(v) for v in planes.shape)
-    if labels.shape[0] != N:
-        raise SpxError(f"labels hold {labels.shape[0]} images, activations {N}")
-    if labels.device != planes.device:
-        raise SpxError(f"labels are on {labels.device}, activations on {planes.device}")
-    H, W = int(labels.shape[1]), int(labels.shape[2])
-    if not isinstance(rows, torch.Tensor):
-        rows = torch.as_tensor(rows)
-    if rows.dim() != 2 or rows.shape[1] != 4 or rows.shape[0] < 1 or rows.is_floating_point():
-        raise SpxError(f"rows must be integer [R, 4] with R >= 1 (got {rows.dtype} {tuple(rows.shape)})")
-    R = int(rows.shape[0])
+    H, W = _maps.label_map(labels, N, "activations")
     host_rows = None
-    if not rows.is_cuda:
-        host_rows = rows.detach().to(torch.int32).contiguous()
-        if not torch.equal(host_rows.to(torch.int64), rows.detach().to(torch.int64)):
+    if isinstance(rows, torch.Tensor) and rows.is_cuda:
+        if rows.dim() != 2 or rows.shape[1] != 4 or rows.shape[0] < 1 or rows.is_floating_point():
+            raise SpxError(f"rows must be integer [R, 4] with R >= 1 (got {rows.dtype} {tuple(rows.shape)})")
+    else:
+        rows = _maps.host_rows(rows, 4, "(n, c, class, flat latent index)")
+        host_rows = rows.to(torch.int32).contiguous()
+        if not torch.equal(host_rows.to(torch.int64), rows):
             raise SpxError("rows do not fit int32")
+        if thresholds is None:                     # the select below reads the planes the rows name
+            n, c = rows[:, 0], rows[:, 1]
+            _maps.bad_row(rows, (n < 0) | (n >= N) | (c < 0) | (c >= Cn), f"no plane of N={N}, C={Cn}")
+    R = int(rows.shape[0])
+    lab = _maps.device_labels(planes, labels)
+    if host_rows is not None:
         dev_rows = host_rows.to(planes.device)
     else:
         if rows.device != planes.device:
@@ -93,25 +90,20 @@ def push_bounding_boxes(activations: torch.Tensor, labels: torch.Tensor, rows: t
         dev_rows = rows.detach().to(torch.int32).contiguous()
     if thresholds is None:
         if host_rows is not None:
-            bad = (host_rows[:, 0] < 0) | (host_rows[:, 0] >= N) | (host_rows[:, 1] < 0) | (host_rows[:, 1] >= Cn)
-            if bool(bad.any()):
-                r = int(bad.nonzero()[0])
-                raise SpxError(f"row {r} names plane ({int(host_rows[r, 0])}, {int(host_rows[r, 1])}) outside [{N}, {Cn}]")
-            pairs = torch.unique(host_rows[:, :2].to(torch.int64), dim=0).to(planes.device)
+            pairs = torch.unique(rows[:, :2], dim=0).to(planes.device)
         else:                                      # no host read: one select per row, rows out of range fold onto plane (0, 0)
             pairs = dev_rows[:, :2].to(torch.int64)
             ok = (pairs[:, 0] >= 0) & (pairs[:, 0] < N) & (pairs[:, 1] >= 0) & (pairs[:, 1] < Cn)
             pairs = pairs * ok.unsqueeze(1)
         thresholds = _select_for(lib, planes, pairs, (H, W), q)
     else:
-        _dev_ptr(thresholds, "thresholds")
+        _lib.require_gpu(thresholds, "thresholds")
         if thresholds.dtype != torch.float32 or tuple(thresholds.shape) != (N, Cn) or thresholds.device != planes.device:
             raise SpxError(f"thresholds must be fp32 [{N}, {Cn}] on {planes.device}")
         thresholds = thresholds.detach().contiguous()
-    lab = labels.detach().contiguous()
     rf = torch.empty(R, 4, dtype=torch.int32, device=planes.device)
     box = torch.empty(R, 4, dtype=torch.int32, device=planes.device)
-    _lib.check(lib.spx_push_boxes(planes.data_ptr(), _strides(planes, (0, 1, 2, 3)), lab.data_ptr(), _LABEL_BYTES[lab.dtype],
+    _lib.check(lib.spx_push_boxes(planes.data_ptr(), strides(planes), lab.data_ptr(), LABEL_BYTES[lab.dtype],
                                   _lib.ptr(dev_rows), None if host_rows is None else host_rows.data_ptr(), _lib.ptr(thresholds), R, N,
                                   Cn, h, w, H, W, int(add_margin), _lib.ptr(rf), _lib.ptr(box), _lib.stream_ptr()))
     return rf.to(torch.int64), box.to(torch.int64)

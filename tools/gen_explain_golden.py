@@ -1,16 +1,15 @@
 """Write tests/golden/explanation_maps.npz by driving the reference's own ``plot_activation_proto`` and ``plot_activation_group``
 (segmentation/analysis/sample_activations_prototype.py:30-133, sample_activations_group.py:29-131; CPU only).
 
-    SPX_REFERENCE=/path/to/ScaleProtoSeg python tools/gen_explain_golden.py
+    SPX_REFERENCE=/path/to/ScaleProtoSeg python tools/gen_explain_golden.py [output.npz]
 
-The two functions are loaded from the reference checkout and called once per image with stand-ins for everything around them:
+The two functions are loaded from the reference checkout and called once per image with stand-ins for everything around them
+(those of tools/reference_stubs.py, and):
 
 * a fake ``ppnet`` that returns prepared tensors (``conv_features``, ``forward_from_conv_features``, ``compute_group``,
   ``prototype_class_identity``, ``epsilon``, ``num_groups``, ``last_layer_group``); ``.cuda()`` is a no-op;
 * ``to_normalized_tensor`` and ``transforms.ToTensor`` stubs that only carry the image size; ``plt`` does nothing, the files the
   functions would write are never written (their class folders are made in a temporary directory);
-* ``cv2.resize(..., INTER_CUBIC)`` replaced by the float64 restatement of tests/overlap_restatement.py rounded to float32
-  (``cv2`` is not needed and was never run against the restatement);
 * ``cv2.applyColorMap`` records its uint8 argument: the heat map;  the ``ListedColormap`` object records the array it is called
   with: the argmax map;  ``np.amin`` inside the two functions also records the minimum and maximum of its argument, the masked
   map: ``ranges``;
@@ -25,26 +24,19 @@ tests/explain_restatement.py.  The tool asserts ambiguous <= 4 + H*W / 50 for ev
 dominant rows of the deliberately tied class."""
 from __future__ import annotations
 
-import importlib.util
 import os
-import sys
 import tempfile
 import types
 import warnings
 
-sys.dont_write_bytecode = True
-
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "..", "tests"))
-import explain_restatement as E  # noqa: E402
-import overlap_restatement as R  # noqa: E402
+import reference_stubs as S
+import explain_restatement as E
 
-REF = os.environ.get("SPX_REFERENCE")
-OUT = os.path.join(HERE, "..", "tests", "golden", "explanation_maps.npz")
 EPS = 1e-4
+BLOCKS = (5, 6)
 REC = []                                                          # ("range", lo, hi) / ("heat", bytes) / ("argmax", array)
 
 
@@ -58,13 +50,6 @@ class _RecordingNumpy:
     def amin(a):
         REC.append(("range", np.float32(np.amin(a)), np.float32(np.amax(a))))
         return np.amin(a)
-
-
-def _resize(src, dsize, interpolation):
-    assert interpolation == "INTER_CUBIC" and src.dtype == np.float32
-    if src.ndim == 3 and src.shape[2] == 1:                   # a one-channel image comes back 2-D from cv2.resize
-        src = src[:, :, 0]
-    return R.upsample(src, (dsize[1], dsize[0])).astype(np.float32)
 
 
 def _apply_color_map(src, colormap):
@@ -83,65 +68,14 @@ class _Colormap:
         return np.zeros(index.shape + (4,))
 
 
-class _Sized:
-    """Stands for the PIL image and for every tensor made from it: carries (H, W) only."""
-
-    def __init__(self, H, W):
-        self.size_hw = (H, W)
-
-    def unsqueeze(self, _):
-        return self
-
-    def cuda(self):
-        return self
-
-    def detach(self):
-        return self
-
-    def cpu(self):
-        return self
-
-    def numpy(self):
-        return np.zeros((3,) + self.size_hw, np.float32)
-
-
 def _stub_modules():
-    def mod(name, **attrs):
-        m = types.ModuleType(name)
-        m.__dict__.update(attrs)
-        sys.modules[name] = m
-        return m
-
+    """The shared stand-ins, with a ``cv2`` that also has ``applyColorMap`` and a ``matplotlib`` with the recording colormap."""
     nothing = lambda *a, **kw: None
-    mod("argh", dispatch_command=nothing)
-    mod("cv2", resize=_resize, INTER_CUBIC="INTER_CUBIC", applyColorMap=_apply_color_map, COLORMAP_JET="COLORMAP_JET")
+    S.stub_modules()
+    S.mod("cv2", resize=S.resize, INTER_CUBIC="INTER_CUBIC", applyColorMap=_apply_color_map, COLORMAP_JET="COLORMAP_JET")
     cm = types.SimpleNamespace(viridis=lambda x: np.zeros(np.shape(x) + (4,)))
-    plt = mod("matplotlib.pyplot", cm=cm, imsave=nothing, close=nothing)
-    mpl = mod("matplotlib", pyplot=plt, colors=mod("matplotlib.colors", ListedColormap=_Colormap))
-    mpl.__path__ = []
-    mod("PIL", Image=mod("PIL.Image", Image=_Sized))
-    mod("torchvision", transforms=mod("torchvision.transforms", ToTensor=lambda: (lambda img: img)))
-    mod("tqdm", tqdm=lambda it, **kw: it)
-    mod("find_nearest", to_normalized_tensor=lambda img: img)
-    mod("settings", log=print)
-    seg = mod("segmentation")
-    seg.__path__ = []
-    names = ("CITYSCAPES_19_EVAL_CATEGORIES", "CITYSCAPES_CATEGORIES", "PASCAL_CATEGORIES", "PASCAL_ID_MAPPING", "ADE20k_ID_2_LABEL")
-    mod("segmentation.constants", **{n: {} for n in names})
-    mod("segmentation.data").__path__ = []
-    mod("segmentation.data.dataset", PatchClassificationDataset=object)
-    mod("segmentation.model").__path__ = []
-    mod("segmentation.model.model", PPNet=object)
-    mod("segmentation.model.model_multiscale", PPNetMultiScale=object)
-    mod("segmentation.model.model_multiscale_group", PPNetMultiScale=object)
-
-
-def _load(rel):
-    spec = importlib.util.spec_from_file_location("ref_" + os.path.basename(rel)[:-3], os.path.join(REF, rel))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    m.np = _RecordingNumpy()
-    return m
+    plt = S.mod("matplotlib.pyplot", cm=cm, imsave=nothing, close=nothing)
+    S.mod("matplotlib", pyplot=plt, colors=S.mod("matplotlib.colors", ListedColormap=_Colormap)).__path__ = []
 
 
 class _ProtoNet:
@@ -172,30 +106,6 @@ class _GroupNet:
         return self.groups
 
 
-def _bf16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
-
-
-def _labels(g, N, H, W, K, present):
-    """Blocky labels: image n holds the classes present[n] plus void, and one pixel with the label K + 2."""
-    lab = np.zeros((N, H, W), np.uint8)
-    for n in range(N):
-        vals = np.array([0] + [k + 1 for k in present[n]])
-        by, bx = max(1, H // 5), max(1, W // 6)
-        grid = vals[torch.randint(0, len(vals), (H // by + 1, W // bx + 1), generator=g).numpy()]
-        lab[n] = np.kron(grid, np.ones((by, bx), np.int64))[:H, :W]
-        for i, v in enumerate(vals):                 # every listed value occurs
-            lab[n, i, 0] = v
-        lab[n, H - 1, W - 1] = K + 2
-    return lab
-
-
-def _for_reference(lab, K):
-    out = lab.copy()
-    out[out > K] = 0
-    return out
-
-
 def _drive(fn, net, lab, K, H, W, h, w, g):
     """Call the reference once per image; the recorded events in its order."""
     names = {k: f"class{k}" for k in range(K)}
@@ -206,7 +116,7 @@ def _drive(fn, net, lab, K, H, W, h, w, g):
             net.select(n)
             net.logits = torch.randn(1, h, w, K, generator=g)
             del REC[:]
-            fn(_Sized(H, W), n, _for_reference(lab[n], K), net, names, tmp)
+            fn(S.Sized(H, W, channels=3, dtype=np.float32), n, S.for_reference(lab[n], K), net, names, tmp)
             events.append(list(REC))
     return events
 
@@ -259,10 +169,10 @@ def _proto_case(name, PA, seed, h, w, H, W, tie):
     ident[torch.arange(P), torch.tensor(cls)] = 1
     present = [[0, 1, 2], [0, 2]]                                 # class 1 is absent from image 1
     base = torch.rand(N, K, h, w, generator=g) * 1.5 + 0.05
-    d = _bf16(base[:, cls] * (0.5 + torch.rand(N, P, h, w, generator=g)))
+    d = S.bf16(base[:, cls] * (0.5 + torch.rand(N, P, h, w, generator=g)))
     if tie:
         d[:, 7] = d[:, 5]
-    lab = _labels(g, N, H, W, K, present)
+    lab = S.labels(g, N, H, W, K, present, BLOCKS)
     net = _ProtoNet(ident)
     net.select = lambda n: setattr(net, "distances", d[n:n + 1])
     events = _drive(PA.plot_activation_proto, net, lab, K, H, W, h, w, g)
@@ -287,10 +197,10 @@ def _group_case(name, GA, seed, h, w, H, W):
     # a constant plane: hi == lo.  Zero is the only constant that stays one in every arithmetic (the taps' weights sum to 1
     # only nearly, so another constant comes back with its last bits varying and hi - lo a few ulps)
     a[:, 1, 2] = 0.0
-    a = _bf16(a).reshape(N, K * G, h, w)
-    head = _bf16(torch.rand(K, K * G, generator=g) * 1.5 + 0.25)
+    a = S.bf16(a).reshape(N, K * G, h, w)
+    head = S.bf16(torch.rand(K, K * G, generator=g) * 1.5 + 0.25)
     head[0, 0] = -0.75
-    lab = _labels(g, N, H, W, K, present)
+    lab = S.labels(g, N, H, W, K, present, BLOCKS)
     net = _GroupNet(K, G, head)
     net.grid = (h, w)
 
@@ -311,18 +221,17 @@ def _group_case(name, GA, seed, h, w, H, W):
 
 
 def main():
-    if not REF:
-        sys.exit("set SPX_REFERENCE to the reference checkout")
     _stub_modules()
-    PA = _load(os.path.join("segmentation", "analysis", "sample_activations_prototype.py"))
-    GA = _load(os.path.join("segmentation", "analysis", "sample_activations_group.py"))
+    PA = S.load(os.path.join("segmentation", "analysis", "sample_activations_prototype.py"), numpy_proxy=_RecordingNumpy())
+    GA = S.load(os.path.join("segmentation", "analysis", "sample_activations_group.py"), numpy_proxy=_RecordingNumpy())
     cases = {}
     cases.update(_proto_case("proto_5x7_33x41", PA, 20240702, 5, 7, 33, 41, tie=False))
     cases.update(_proto_case("proto_3x3_17x19_tied", PA, 20240703, 3, 3, 17, 19, tie=True))
     cases.update(_group_case("group_5x7_33x41", GA, 20240704, 5, 7, 33, 41))
     cases.update(_group_case("group_3x3_17x19", GA, 20240705, 3, 3, 17, 19))
-    np.savez_compressed(OUT, **cases)
-    print(OUT, os.path.getsize(OUT), "bytes")
+    out = S.out_path("explanation_maps.npz")
+    np.savez_compressed(out, **cases)
+    print(out, os.path.getsize(out), "bytes")
 
 
 if __name__ == "__main__":

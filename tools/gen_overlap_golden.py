@@ -1,15 +1,14 @@
 """Write tests/golden/activation_overlap.npz by driving the reference's own ``prototype_overlap`` and ``group_overlap``
 (segmentation/analysis/prototype_overlap.py:28-92, group_overlap.py:28-87; CPU only).
 
-    SPX_REFERENCE=/path/to/ScaleProtoSeg python tools/gen_overlap_golden.py
+    SPX_REFERENCE=/path/to/ScaleProtoSeg python tools/gen_overlap_golden.py [output.npz]
 
-The two functions are loaded from the reference checkout and called once per image with stand-ins for everything around them:
+The two functions are loaded from the reference checkout and called once per image with stand-ins for everything around them
+(those of tools/reference_stubs.py, and):
 
 * a fake ``ppnet`` that returns prepared tensors (``conv_features``, ``forward_from_conv_features``, ``compute_group``,
   ``prototype_class_identity``, ``epsilon``, ``num_groups``); ``.cuda()`` is a no-op;
 * ``to_normalized_tensor`` and ``transforms.ToTensor`` stubs that only carry the image size;
-* ``cv2.resize(..., INTER_CUBIC)`` replaced by the float64 restatement of tests/overlap_restatement.py rounded to float32
-  (``cv2`` is not needed and was never run against the restatement);
 * ``np.quantile(x, 0.95)`` inside the two functions answered at the case's ``q`` (the reference hard-codes 0.95; the fixture
   also records 0.8), by the real ``np.quantile`` on the same float32 array;
 * the reference cannot take a label outside 0..K (it indexes the class identity with it), so the one out-of-range pixel of the
@@ -22,24 +21,17 @@ m = 64 * 2^-23 * max|a|.  The tool asserts ambiguous <= 4 + |mask| / 1000 for ev
 exact case, whose quantised planes tie with their thresholds on purpose."""
 from __future__ import annotations
 
-import importlib.util
 import os
-import sys
-import types
 from collections import defaultdict
-
-sys.dont_write_bytecode = True
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "..", "tests"))
-import overlap_restatement as R  # noqa: E402
+import reference_stubs as S
+import overlap_restatement as R
 
-REF = os.environ.get("SPX_REFERENCE")
-OUT = os.path.join(HERE, "..", "tests", "golden", "activation_overlap.npz")
 EPS = 1e-4
+BLOCKS = (6, 7)
 Q = {"value": 0.95}
 
 
@@ -53,68 +45,6 @@ class _NumpyAtQ:
     def quantile(a, q):
         assert q == 0.95
         return np.quantile(a, Q["value"])
-
-
-def _resize(src, dsize, interpolation):
-    assert interpolation == "INTER_CUBIC" and src.dtype == np.float32
-    if src.ndim == 3 and src.shape[2] == 1:                   # a one-channel image comes back 2-D from cv2.resize
-        src = src[:, :, 0]
-    return R.upsample(src, (dsize[1], dsize[0])).astype(np.float32)
-
-
-class _Sized:
-    """Stands for the PIL image and for every tensor made from it: carries (H, W) only."""
-
-    def __init__(self, H, W):
-        self.size_hw = (H, W)
-
-    def unsqueeze(self, _):
-        return self
-
-    def cuda(self):
-        return self
-
-    def detach(self):
-        return self
-
-    def cpu(self):
-        return self
-
-    def numpy(self):
-        return np.zeros((1,) + self.size_hw, np.uint8)
-
-
-def _stub_modules():
-    def mod(name, **attrs):
-        m = types.ModuleType(name)
-        m.__dict__.update(attrs)
-        sys.modules[name] = m
-        return m
-
-    mod("argh", dispatch_command=lambda f: None)
-    mod("cv2", resize=_resize, INTER_CUBIC="INTER_CUBIC")
-    mod("PIL", Image=mod("PIL.Image", Image=_Sized))
-    mod("torchvision", transforms=mod("torchvision.transforms", ToTensor=lambda: (lambda img: img)))
-    mod("tqdm", tqdm=lambda it, **kw: it)
-    mod("find_nearest", to_normalized_tensor=lambda img: img)
-    mod("settings", log=print)
-    seg = mod("segmentation")
-    seg.__path__ = []
-    names = ("CITYSCAPES_19_EVAL_CATEGORIES", "CITYSCAPES_CATEGORIES", "PASCAL_CATEGORIES", "PASCAL_ID_MAPPING", "ADE20k_ID_2_LABEL")
-    mod("segmentation.constants", **{n: {} for n in names})
-    mod("segmentation.data").__path__ = []
-    mod("segmentation.data.dataset", PatchClassificationDataset=object)
-    mod("segmentation.model").__path__ = []
-    mod("segmentation.model.model_multiscale", PPNetMultiScale=object)
-    mod("segmentation.model.model_multiscale_group", PPNetMultiScale=object)
-
-
-def _load(rel):
-    spec = importlib.util.spec_from_file_location("ref_" + os.path.basename(rel)[:-3], os.path.join(REF, rel))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    m.np = _NumpyAtQ()
-    return m
 
 
 class _ProtoNet:
@@ -143,30 +73,6 @@ class _GroupNet:
 
     def compute_group(self, activations):
         return self.groups
-
-
-def _bf16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
-
-
-def _labels(g, N, H, W, K, present):
-    """Blocky labels: image n holds the classes present[n] plus void, and one pixel with the label K + 2."""
-    lab = np.zeros((N, H, W), np.uint8)
-    for n in range(N):
-        vals = np.array([0] + [k + 1 for k in present[n]])
-        by, bx = max(1, H // 6), max(1, W // 7)
-        grid = vals[torch.randint(0, len(vals), (H // by + 1, W // bx + 1), generator=g).numpy()]
-        lab[n] = np.kron(grid, np.ones((by, bx), np.int64))[:H, :W]
-        for i, v in enumerate(vals):                 # every listed value occurs
-            lab[n, i, 0] = v
-        lab[n, H - 1, W - 1] = K + 2
-    return lab
-
-
-def _for_reference(lab, K):
-    out = lab.copy()
-    out[out > K] = 0
-    return out
 
 
 def _collect(class_val, tot_val, slots_of, N_present):
@@ -222,16 +128,16 @@ def _proto_case(name, PO, seed, h, w, H, W, q):
     ident[torch.arange(P), torch.tensor(cls)] = 1
     present = [[0, 1, 2, 3], [0, 2]]
     base = torch.rand(N, K, h, w, generator=g) * 1.5 + 0.05
-    d = _bf16(base[:, cls] + 0.3 * torch.rand(N, P, h, w, generator=g))
+    d = S.bf16(base[:, cls] + 0.3 * torch.rand(N, P, h, w, generator=g))
     d[:, 2] = d[:, 0]
-    lab = _labels(g, N, H, W, K, present)
+    lab = S.labels(g, N, H, W, K, present, BLOCKS)
     Q["value"] = q
     net = _ProtoNet(ident)
     class_val = {k: defaultdict(list) for k in range(K)}
     tot_val = defaultdict(list)
     for n in range(N):
         net.distances = d[n:n + 1]
-        PO.prototype_overlap(_Sized(H, W), _for_reference(lab[n], K), net, class_val, tot_val)
+        PO.prototype_overlap(S.Sized(H, W), S.for_reference(lab[n], K), net, class_val, tot_val)
     slots_of = [[p for p in range(P) if cls[p] == k] for k in range(K)]
     table = np.full((K, 3), -1, np.int64)
     for k in range(K):
@@ -254,8 +160,8 @@ def _group_case(name, GO, seed, h, w, H, W, q, exact=False):
         a = torch.round(a * 4.0) / 4.0                        # multiples of 0.25: many ties across the threshold
         a[:, 1, 2] = 0.75                                     # a constant plane: empty mask
         a[:, 2, 1] = a[:, 2, 0]                               # a duplicated plane: intersection = union = area
-    a = _bf16(a).reshape(N, K * G, h, w)
-    lab = _labels(g, N, H, W, K, present)
+    a = S.bf16(a).reshape(N, K * G, h, w)
+    lab = S.labels(g, N, H, W, K, present, BLOCKS)
     Q["value"] = q
     net = _GroupNet(K, G)
     net.grid = (h, w)
@@ -264,7 +170,7 @@ def _group_case(name, GO, seed, h, w, H, W, q, exact=False):
     for n in range(N):
         pix = a[n].permute(1, 2, 0).reshape(h * w, K * G)     # the [M, U] layout compute_group's list is split from
         net.groups = list(torch.split(pix, G, dim=1))
-        GO.group_overlap(_Sized(H, W), _for_reference(lab[n], K), net, class_val, tot_val)
+        GO.group_overlap(S.Sized(H, W), S.for_reference(lab[n], K), net, class_val, tot_val)
     table = np.arange(K * G, dtype=np.int64).reshape(K, G)
     out = dict(kind=np.array("group"), activations=a.numpy(), labels=lab, q=np.float64(q), table=table)
     out.update(_collect(class_val, tot_val, [list(r) for r in table], [sum(k in p for p in present) for k in range(K)]))
@@ -273,11 +179,9 @@ def _group_case(name, GO, seed, h, w, H, W, q, exact=False):
 
 
 def main():
-    if not REF:
-        sys.exit("set SPX_REFERENCE to the reference checkout")
-    _stub_modules()
-    PO = _load(os.path.join("segmentation", "analysis", "prototype_overlap.py"))
-    GO = _load(os.path.join("segmentation", "analysis", "group_overlap.py"))
+    S.stub_modules()
+    PO = S.load(os.path.join("segmentation", "analysis", "prototype_overlap.py"), numpy_proxy=_NumpyAtQ())
+    GO = S.load(os.path.join("segmentation", "analysis", "group_overlap.py"), numpy_proxy=_NumpyAtQ())
     cases = {}
     shapes = (("s5x7", 5, 7, 33, 50), ("s9x11", 9, 11, 70, 85), ("s17x17", 17, 17, 129, 129), ("s33x65", 33, 65, 257, 513))
     seed = 20240611
@@ -290,8 +194,9 @@ def main():
             seed += 1
             cases.update(_group_case(f"group_{tag}_q{int(q * 100)}", GO, seed, h, w, H, W, q))
     cases.update(_group_case("exact_70x85_q95", GO, seed + 1, 70, 85, 70, 85, 0.95, exact=True))
-    np.savez_compressed(OUT, **cases)
-    print(OUT, os.path.getsize(OUT), "bytes")
+    out = S.out_path("activation_overlap.npz")
+    np.savez_compressed(out, **cases)
+    print(out, os.path.getsize(out), "bytes")
 
 
 if __name__ == "__main__":

@@ -1,17 +1,16 @@
 """Write tests/golden/push_boxes.npz by driving the reference's own ``update_prototypes_on_image``
 (segmentation/push_multiscale_optimization.py:341-497) and ``helpers.find_continuous_high_activation_crop`` (CPU only).
 
-    SPX_REFERENCE=/path/to/ScaleProtoSeg python tools/gen_push_boxes_golden.py
+    SPX_REFERENCE=/path/to/ScaleProtoSeg python tools/gen_push_boxes_golden.py [output.npz]
 
-The two functions are loaded from the reference checkout and called with stand-ins for everything around them:
+The two functions are loaded from the reference checkout and called with stand-ins for everything around them (those of
+tools/reference_stubs.py, and):
 
 * a fake ``ppnet`` that returns prepared distances (``conv_features``, ``forward_from_conv_features``,
   ``prototype_class_identity``, ``prototype_shape``, ``num_scales``, ``epsilon``, ``prototype_activation_function``) and a fake
   dataset (``img_ids``, ``get_img_path``, ``annotations_dir``, ``image_margin_size = 0``, ``convert_targets = None``);
 * PIL, ``to_normalized_tensor``, ``transforms.ToTensor`` and matplotlib stand-ins that only carry the image size (the "image
   file" of an id is a text file with its size and index); ``dir_for_saving_prototypes=None``, so nothing is plotted;
-* ``cv2.resize(..., INTER_CUBIC)`` replaced by the float64 restatement of tests/overlap_restatement.py rounded to float32
-  (``cv2`` is not needed and was never run against the restatement);
 * the labels as ``.npy`` files in a temporary directory, as the reference loads them.
 
 Data only is recorded, keys ``<case>__<field>``: the latent distances (bf16-representable; ``"log"`` cases, and the identity
@@ -26,97 +25,18 @@ the reference in every row, and per case that at most 1 row in 8 is non-robust (
 satisfy it."""
 from __future__ import annotations
 
-import importlib.util
 import os
-import sys
 import tempfile
-import types
-
-sys.dont_write_bytecode = True
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "..", "tests"))
-import overlap_restatement as R  # noqa: E402
-import push_boxes_restatement as PB  # noqa: E402
+import reference_stubs as S
+import overlap_restatement as R
+import push_boxes_restatement as PB
 
-REF = os.environ.get("SPX_REFERENCE")
-OUT = os.path.join(HERE, "..", "tests", "golden", "push_boxes.npz")
 EPS = 1e-4
 K = 4                                       # class 3 owns a prototype and occurs in no image
-
-
-def _resize(src, dsize, interpolation):
-    assert interpolation == "INTER_CUBIC" and src.dtype == np.float32 and src.ndim == 2
-    return R.upsample(src, (dsize[1], dsize[0])).astype(np.float32)
-
-
-class _Sized:
-    """Stands for the PIL image and for every tensor made from it: carries (H, W) and the image's index only."""
-
-    def __init__(self, H, W, n):
-        self.height, self.width, self.n = H, W, n
-
-    def convert(self, mode):
-        return self
-
-    def crop(self, box):
-        assert box == (0, 0, self.width, self.height)
-        return self
-
-    def unsqueeze(self, _):
-        return self
-
-    def to(self, _):
-        return self
-
-    def detach(self):
-        return self
-
-    def cpu(self):
-        return self
-
-    def numpy(self):
-        return np.zeros((1, self.height, self.width), np.uint8)
-
-
-def _open(f):
-    H, W, n = (int(v) for v in f.read().split())
-    return _Sized(H, W, n)
-
-
-def _stub_modules():
-    def mod(name, **attrs):
-        m = types.ModuleType(name)
-        m.__dict__.update(attrs)
-        sys.modules[name] = m
-        return m
-
-    mod("cv2", resize=_resize, INTER_CUBIC="INTER_CUBIC")
-    mod("matplotlib", pyplot=mod("matplotlib.pyplot"))
-    mod("PIL", Image=mod("PIL.Image", open=_open))
-    mod("torchvision", transforms=mod("torchvision.transforms", ToTensor=lambda: (lambda img: img)))
-    mod("tqdm", tqdm=lambda it, **kw: it)
-    mod("find_nearest", to_normalized_tensor=lambda img: img)
-    seg = mod("segmentation")
-    seg.__path__ = []
-    names = ("CITYSCAPES_19_EVAL_CATEGORIES", "CITYSCAPES_CATEGORIES", "COCO_ID_2_LABEL", "EM_ID_2_LABEL", "PASCAL_CATEGORIES",
-             "PASCAL_ID_MAPPING", "ADE20k_ID_2_LABEL")
-    mod("segmentation.constants", **{n: {} for n in names})
-    mod("segmentation.data").__path__ = []
-    mod("segmentation.data.dataset", PatchClassificationDataset=object, resize_label=None)
-    mod("segmentation.model").__path__ = []
-    mod("segmentation.model.model_multiscale", PPNetMultiScale=object)
-
-
-def _load(rel, name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(REF, rel))
-    m = importlib.util.module_from_spec(spec)
-    sys.modules[name] = m
-    spec.loader.exec_module(m)
-    return m
 
 
 class _Net:
@@ -156,10 +76,6 @@ class _Data:
 
     def get_img_path(self, i):
         return os.path.join(self.annotations_dir, i + ".img")
-
-
-def _bf16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
 
 
 def _labels(H, W):
@@ -261,7 +177,7 @@ def _reference_case(name, PUSH, seed, h, w, H, W, identity=False):
         d = torch.round((3.5 * (1.0 - b.clamp(0, 1)) + 0.25) * 4.0) / 4.0          # multiples of 0.25 in [0.25, 3.75]
     else:
         d = 1.5 * (1.0 - b).clamp_min(0) + 0.05
-    d = _bf16(_place(d, img))
+    d = S.bf16(_place(d, img))
     labels = _labels(H, W)
     net = _Net(ident, d, "linear" if identity else "log", (h, w))
     ref_rf = np.full((P, 6), -1)
@@ -296,7 +212,7 @@ def _negative_case(name, HELP, seed, h, w, H, W):
     ident = torch.zeros(P, K)
     ident[torch.arange(P), torch.tensor(cls)] = 1
     b, flat = _bumps(g, h, w)
-    a = _bf16(_place(b - 2.0, img)).numpy()
+    a = S.bf16(_place(b - 2.0, img)).numpy()
     labels = _labels(H, W)
     ref_rf = np.full((P, 6), -1, np.int64)
     ref_box = np.full((P, 6), -1, np.int64)
@@ -317,11 +233,9 @@ def _negative_case(name, HELP, seed, h, w, H, W):
 
 
 def main():
-    if not REF:
-        sys.exit("set SPX_REFERENCE to the reference checkout")
-    _stub_modules()
-    HELP = _load("helpers.py", "helpers")
-    PUSH = _load(os.path.join("segmentation", "push_multiscale_optimization.py"), "ref_push_multiscale_optimization")
+    S.stub_modules()
+    HELP = S.load("helpers.py", "helpers")
+    PUSH = S.load(os.path.join("segmentation", "push_multiscale_optimization.py"), "ref_push_multiscale_optimization")
     cases, feats = {}, set()
     shapes = (("s5x7", 5, 7, 33, 50), ("s9x11", 9, 11, 70, 85), ("s17x17", 17, 17, 129, 129), ("s33x65", 33, 65, 257, 513))
     seed = 20241018
@@ -335,8 +249,9 @@ def main():
     cases.update(_negative_case("negative_9x11", HELP, seed + 2, 9, 11, 70, 85))
     want = {"top", "bottom", "left", "right", "rf_past_image", "no_growth", "growth"}
     assert want <= feats, want - feats
-    np.savez_compressed(OUT, **cases)
-    print(OUT, os.path.getsize(OUT), "bytes")
+    out = S.out_path("push_boxes.npz")
+    np.savez_compressed(out, **cases)
+    print(out, os.path.getsize(out), "bytes")
 
 
 if __name__ == "__main__":
