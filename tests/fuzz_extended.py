@@ -1,5 +1,5 @@
 """Extended randomised parity run (not collected by pytest): the bodies of test_random_configurations and
-test_random_gather_and_tail over many more seeds than the suite carries.  Usage (GPU box):
+test_random_gather_and_tail (tests/parity_cases.py) over many more seeds than the suite carries.  Usage (GPU box):
     python tests/fuzz_extended.py FIRST LAST [LOGFILE]
     python tests/fuzz_extended.py kld|push|pushfused FIRST LAST [LOGFILE]
 Prints one line per failing seed and a summary; progress goes to LOGFILE every 10 seeds."""
@@ -10,7 +10,8 @@ import traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import test_gpu_parity as T  # noqa: E402
+import parity_cases as T  # noqa: E402
+from oracle import ppnet_oracle as O  # noqa: E402
 
 
 def kld_case(seed):
@@ -28,9 +29,9 @@ def kld_case(seed):
     P = K * S * r
     B = int(rng.integers(1, 4))
     H, W = int(rng.integers(1, 120)), int(rng.integers(1, 400))
-    ident = T.O.default_class_identity(P, K, S)
-    ranges = T.O.default_scale_ranges(P, S)
-    lay = T._layout(P, K, S, 16, ranges)
+    ident = O.default_class_identity(P, K, S)
+    ranges = O.default_scale_ranges(P, S)
+    lay = T.bank_layout(P, K, S, 16, ranges)
     keys, J, table = spx.class_gather_table(lay, ident, dev)
     gen = torch.Generator(device=dev).manual_seed(seed)
     ph, pw = int(rng.choice([1, 3, 16, 40])), int(rng.choice([1, 5, 64, 100]))
@@ -77,7 +78,7 @@ def push_case(seed):
     dist = torch.floor(torch.rand(B, P, H, W, generator=g) * 64 * q) / q
     target = torch.randint(0, K if void is None else K + 1, (B, H, W), generator=g)
     ident = (torch.rand(P, K, generator=g) < 1.5 / K).float()      # 0, 1 or several classes per prototype
-    ref_idx, ref_val = T.O.push_masked_argmin(dist, target, ident, K, void_class=void)
+    ref_idx, ref_val = O.push_masked_argmin(dist, target, ident, K, void_class=void)
     idx, val = push_masked_argmin(dist.to(dev), target.to(dev), ident, void_class=void)
     tag = f"B{B} P{P} K{K} {H}x{W} void {void}"
     assert torch.equal(idx.cpu(), ref_idx), tag
@@ -103,22 +104,22 @@ def push_fused_case(seed):
     void = None if seed % 3 == 0 else int(rng.integers(0, K + 1))
     xdt = torch.bfloat16 if seed % 2 else torch.float32
     g = torch.Generator().manual_seed(seed)
-    conv = T.O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=g)))
+    conv = O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=g)))
     if H > 2:
         conv[:, :, 1] = conv[:, :, 0]                  # a repeated row of pixels: exact ties
-    bank = T.O.bf16_representable(torch.rand(P, Cs, 1, 1, generator=g))
-    ranges = T.O.default_scale_ranges(P, S)
+    bank = O.bf16_representable(torch.rand(P, Cs, 1, 1, generator=g))
+    ranges = O.default_scale_ranges(P, S)
     ident = torch.zeros(P, K)
     cls = torch.randint(0, K, (P,), generator=g)
     ident[torch.arange(P), cls] = 1.0
     ident[torch.rand(P, generator=g) < 0.1] = 0.0      # prototypes of no class
     target = torch.randint(0, K if void is None else K + 1, (B, H, W), generator=g)
-    lay = T._layout(P, 1, S, Cs, ranges)
+    lay = T.bank_layout(P, 1, S, Cs, ranges)
     x = conv.to(dev, xdt)
     _, dist, _ = proto_head_forward(x, bank.to(dev), None, lay)
     idx2, val2 = push_masked_argmin(dist, target.to(dev), ident, void_class=void)
     idx, val = push_min_from_features(x, bank.to(dev), lay, target.to(dev), ident, void_class=void)
-    ref_idx, ref_val = T.O.push_masked_argmin(dist.cpu(), target, ident, K, void_class=void)
+    ref_idx, ref_val = O.push_masked_argmin(dist.cpu(), target, ident, K, void_class=void)
     tag = f"B{B} S{S} Cs{Cs} P{P} K{K} {H}x{W} void {void} {xdt}"
     assert torch.equal(idx, idx2) and torch.equal(val, val2), "fused vs two-step: " + tag
     assert torch.equal(idx.cpu(), ref_idx) and torch.equal(val.cpu(), ref_val), "fused vs oracle: " + tag
@@ -134,10 +135,9 @@ def grad_stats(first, last):
         key = what.split()[0]
         peaks[key] = max(peaks.get(key, 0.0), ratio)
 
-    T._grad_close = record
     for seed in range(first, last):
-        for fn in (T.test_random_configurations, T.test_random_gather_and_tail):
-            fn(seed)
+        for fn in (T.check_random_configuration, T.check_random_gather_and_tail):
+            fn(seed, grad_close=record)
     print("peak err / max|ref|:", {k: f"{v:.2e}" for k, v in sorted(peaks.items())})
     return 0
 
@@ -166,7 +166,7 @@ def main():
     log = open(sys.argv[3], "a") if len(sys.argv) > 3 else sys.stdout
     fails = []
     for seed in range(first, last):
-        for fn in (T.test_random_configurations, T.test_random_gather_and_tail):
+        for fn in (T.check_random_configuration, T.check_random_gather_and_tail):
             try:
                 fn(seed)
             except Exception as e:  # noqa: BLE001

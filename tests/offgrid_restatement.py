@@ -16,8 +16,8 @@ import torch
 
 from oracle import ppnet_oracle as O
 
-GRAD_TOL = 1e-3            # tests/test_gpu_parity.py
-DIST_TOL = 1e-4            # |d - d_ref| <= DIST_TOL (1 + d_ref), tests/test_gpu_parity.py::_assert_fwd
+GRAD_TOL = 1e-3            # tests/support.py
+DIST_TOL = 1e-4            # |d - d_ref| <= DIST_TOL (1 + d_ref), tests/parity_cases.py::assert_fwd
 
 # id -> (B, S, Cs, P, K, H, W)
 CASES = {
@@ -199,7 +199,7 @@ def restated_gradients(pb, sites=None, rounding=bf16_rne, check_grid=True, loss_
 
 
 def max_normalised(got, ref):
-    """_grad_close's measure: max|got - ref| / max|ref|."""
+    """grad_close's measure (tests/support.py): max|got - ref| / max|ref|."""
     return ((got.double() - ref.double()).abs().max() / (ref.double().abs().max() + 1e-30)).item()
 
 

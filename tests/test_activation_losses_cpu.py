@@ -2,79 +2,12 @@
 of their definitions, held against the fixture recorded from the reference (tools/gen_activation_loss_golden.py), and the
 package's refusal of anything but the GPU kernels.  The restatement is what the GPU tests hold the kernels against."""
 import math
-import os
 
-import numpy as np
 import pytest
 import torch
 
-from test_regularizers_cpu import close
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "activation_losses.npz")
-CASES = ("even", "ragged", "ties")
-TERMS = ("spat", "sampl", "l1", "linf")
-EPS = 1e-4
-
-
-def load_case(name):
-    z = np.load(GOLDEN)
-    c = {k[len(name) + 2:]: torch.from_numpy(z[k]) for k in z.files if k.startswith(name + "__")}
-    c["ranges"] = [tuple(int(x) for x in r) for r in c["scales"].tolist()]
-    return c
-
-
-def log_activation(d, eps=EPS):
-    return torch.log((d + 1) / (d + eps))
-
-
-def restate(act, target, ident, ranges, norm_type="l1"):
-    """The three terms from their definitions, in ``act``'s dtype, differentiable to ``act`` [B * HW, P] (or [B, HW, P]).
-    Returns ({"spat", "sampl", "norm"}: 0-d tensors, {the same}: number of segments / items of each term).
-      segment = (image, class with >= 1 prototype) with n pixels, Jc = the class's prototypes
-      spat   segments with n >= 2: mean_j H_j / ln n, H_j = entropy of softmax over the segment's pixels of column j
-      sampl  items (segment, scale) with n >= 1 and ns >= 2 prototypes of the class in the scale: mean_px H_px / ln ns, H_px =
-             entropy of the softmax over the ns columns (an item with ns < 2 is skipped)
-      norm   segments with n >= 1: mean_j sum_px |a| / n (l1) or mean_j max_px |a| (linf: amax splits the gradient evenly among ties)
-    each the mean over its segments / items, 0 without any."""
-    Bn = target.shape[0]
-    P, K = ident.shape
-    lab = target.reshape(Bn, -1).long() - 1
-    a = act.reshape(Bn, -1, P)
-    spat, sampl, norm = [], [], []
-    for b in range(Bn):
-        for c in range(K):
-            protos = torch.nonzero(ident[:, c]).flatten().tolist()
-            mask = lab[b] == c
-            n = int(mask.sum())
-            if not protos or n == 0:
-                continue
-            seg = a[b][mask][:, protos]                       # [n, Jc]
-            if n >= 2:
-                logp = torch.log_softmax(seg, dim=0)
-                spat.append((-(logp.exp() * logp).sum(0)).mean() / math.log(n))
-            for lo, hi in ranges:
-                cols = [i for i, p in enumerate(protos) if lo <= p < hi]
-                if len(cols) < 2:
-                    continue
-                logp = torch.log_softmax(seg[:, cols], dim=1)
-                sampl.append((-(logp.exp() * logp).sum(1) / math.log(len(cols))).mean())
-            if norm_type == "l1":
-                norm.append((seg.abs().sum(0) / n).mean())
-            elif norm_type == "linf":
-                norm.append(seg.abs().amax(dim=0).mean())
-            else:
-                raise ValueError(norm_type)
-    zero = (a * 0).sum()
-    mean = lambda xs: torch.stack(xs).mean() if xs else zero
-    return ({"spat": mean(spat), "sampl": mean(sampl), "norm": mean(norm)},
-            {"spat": len(spat), "sampl": len(sampl), "norm": len(norm)})
-
-
-def restate_term(term, act, target, ident, ranges):
-    """One fixture term (spat / sampl / l1 / linf) of the restatement."""
-    vals, counts = restate(act, target, ident, ranges, norm_type=term if term in ("l1", "linf") else "l1")
-    key = "norm" if term in ("l1", "linf") else term
-    return vals[key], counts[key]
+from activation_loss_cases import CASES, TERMS, load_case, log_activation, restate, restate_term
+from regularizer_cases import close
 
 
 @pytest.mark.parametrize("name", CASES)

@@ -1,38 +1,9 @@
 """world_size = 2 over gloo (CPU): the data-parallel exchange logic of scaleprotoseg_amd.dp.
 The same code runs over RCCL (backend "nccl") on the GPUs; kernels are not involved here."""
-import os
-import socket
-import sys
-
-import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _worker(rank, world, port, fn, out):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        res = fn(rank, world)
-        torch.save(res, os.path.join(out, f"r{rank}.pt"))
-    finally:
-        dist.destroy_process_group()
-
-
-def _run(fn, tmp_path, world=2):
-    mp.spawn(_worker, args=(world, _free_port(), fn, str(tmp_path)), nprocs=world, join=True)
-    return [torch.load(os.path.join(tmp_path, f"r{r}.pt")) for r in range(world)]
+from push_cases import patch_kernels_with_oracle
+from support import proto_net, run_gloo
 
 
 def _grad_case(rank, world):
@@ -52,7 +23,7 @@ def _grad_case(rank, world):
 
 
 def test_flat_bucket_allreduce_sums_and_keeps_replicas_identical(tmp_path):
-    res = _run(_grad_case, tmp_path)
+    res = run_gloo(_grad_case, tmp_path)
     exp_bank = sum(torch.randn(12, 8, 1, 1, generator=torch.Generator().manual_seed(100 + r)) for r in range(2))
     # second tensor drawn from the same generator stream per rank
     exp_head = 0
@@ -92,7 +63,7 @@ def _push_case(rank, world):
 
 
 def test_sharded_push_matches_single_process_argmin(tmp_path):
-    res = _run(_push_case, tmp_path)
+    res = run_gloo(_push_case, tmp_path)
     vals, flats = _push_tables()
     best = vals.argmin(dim=0)                                          # push_multiscale_optimization.py:137
     ar = torch.arange(P)
@@ -121,17 +92,6 @@ def test_shard_range_covers_everything():
 # the data-parallel push DRIVER and the data-parallel optimizer step (composition logic; the kernels are replaced by
 # the CPU oracle here - the same drivers run on the real kernels in tests/test_gpu_dp.py)
 # ---------------------------------------------------------------------------------------------------------------
-class _Backbone(torch.nn.Module):
-    def __init__(self, ch):
-        super().__init__()
-        self.base = torch.nn.Sequential(torch.nn.Conv2d(3, ch, 1), torch.nn.Conv2d(ch, ch, 1))
-        self.pool = torch.nn.AvgPool2d(4)
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return self.base(self.pool(x))
 
 
 class _PushData:
@@ -154,39 +114,17 @@ class _PushData:
 
 
 def _push_setup():
-    import scaleprotoseg_amd as spx
-
     S, Cs, K, per = 2, 16, 3, 2
-    P = S * K * per
-    torch.manual_seed(11)
-    net = spx.PPNetMultiScale(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S)
-    with torch.no_grad():
-        net.prototype_vectors[1].copy_(net.prototype_vectors[0])      # forced duplicate
+    net = proto_net(S * K * per, K, S, Cs, seed=11, backbone="pool",
+                    init=lambda net: net.prototype_vectors[1].copy_(net.prototype_vectors[0]))      # forced duplicate
     return net, _PushData(7, K, absent=2, seed=12), S, K
-
-
-def _patch_kernels_with_oracle(S):
-    """compute_distances / argmin_over_images on the CPU oracle (tests may use it; the product path never does)."""
-    from oracle import ppnet_oracle as O
-    from scaleprotoseg_amd import push as push_mod
-
-    def compute_distances(ppnet, dataset, img, target, num_classes, max_dist=1e10, device=None, void_class=None):
-        conv = ppnet.conv_features(img.unsqueeze(0))
-        ranges = {s: tuple(ppnet.scale_num_prototypes[s]) for s in range(S)}
-        d = O.scale_l2_convolution(conv, ppnet.prototype_vectors.detach(), ranges, S)
-        lab = O.resize_label(target, (d.shape[3], d.shape[2])).unsqueeze(0)
-        return O.push_masked_argmin(d, lab, ppnet.prototype_class_identity, num_classes, max_dist, void_class)
-
-    push_mod.compute_distances = compute_distances
-    push_mod.argmin_over_images = lambda v: v.argmin(dim=0)
 
 
 def _dp_push_case(rank, world):
     from scaleprotoseg_amd.push import push_prototypes_multiscale
 
     net, data, S, K = _push_setup()
-    _patch_kernels_with_oracle(S)
+    patch_kernels_with_oracle(S)
     best, _, dup = push_prototypes_multiscale(data, net, log=lambda *_: None, device="cpu")
     return (net.prototype_vectors.detach().clone(), best.clone(), list(dup),
             {s: tuple(net.scale_num_prototypes[s]) for s in range(S)}, net.last_layer.weight.detach().clone())
@@ -195,9 +133,9 @@ def _dp_push_case(rank, world):
 def test_data_parallel_push_driver_equals_single_process(tmp_path):
     from scaleprotoseg_amd.push import push_prototypes_multiscale
 
-    res = _run(_dp_push_case, tmp_path)
+    res = run_gloo(_dp_push_case, tmp_path)
     net, data, S, K = _push_setup()
-    _patch_kernels_with_oracle(S)
+    patch_kernels_with_oracle(S)
     best, _, dup = push_prototypes_multiscale(data, net, log=lambda *_: None, device="cpu")    # world = 1 here
     assert 1 in dup and len(dup) >= 2                    # forced duplicate + the absent class's prototypes per scale
     for bank, gbest, gdup, ranges, wl in res:
@@ -239,7 +177,7 @@ def _dp_step_case(rank, world):
 def test_data_parallel_step_keeps_replicas_bit_identical(tmp_path):
     from scaleprotoseg_amd.utils import projection_simplex_sort
 
-    res = _run(_dp_step_case, tmp_path)
+    res = run_gloo(_dp_step_case, tmp_path)
     (p0, s0), (p1, s1) = res
     assert s0 == s1 == [False, True] * 3
     assert all(torch.equal(a, b) for a, b in zip(p0, p1))               # replicas bit-identical after 3 steps
@@ -286,7 +224,7 @@ def _dp_hook_case(rank, world):
 
 
 def test_data_parallel_step_grad_hook_and_scheduler(tmp_path):
-    res = _run(_dp_hook_case, tmp_path)
+    res = run_gloo(_dp_hook_case, tmp_path)
     (w_a, w0, lr_a, views_a), (w_b, _, lr_b, views_b) = res
     assert torch.equal(w_a, w_b) and lr_a == lr_b == 1e-2 * 0.5 ** 3
     mask = torch.zeros(3, 9)

@@ -14,44 +14,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import explain_restatement as E  # noqa: E402
+from map_cases import EXPLAIN_CASES as CASES, class_planes, planes_of, weights_of  # noqa: E402
+from support import EPS  # noqa: E402
 
 GOLDEN = os.path.join(HERE, "golden", "explanation_maps.npz")
-EPS = 1e-4
 SYMBOLS = ("spx_explain_range", "spx_explain_heat", "spx_explain_dominant")
-
-
-def load_cases():
-    z = np.load(GOLDEN)
-    cases = {}
-    for key in z.files:
-        name, field = key.split("__")
-        cases.setdefault(name, {})[field] = z[key]
-    return cases
-
-
-def planes_of(case):
-    """The float32 activation planes [N, C, h, w] the reference upsampled."""
-    if str(case["kind"]) == "proto":
-        d = case["distances"]
-        return np.log((d + 1) / (d + EPS))                    # sample_activations_prototype.py:85 on float32
-    return case["activations"]
-
-
-def weights_of(case):
-    """float32 [K, J]: 1 for prototypes, last_layer_group.weight[k, channel of (k, j)] for groups."""
-    table = case["table"]
-    if str(case["kind"]) == "proto":
-        return np.ones(table.shape, np.float32)
-    K = table.shape[0]
-    return np.stack([case["head"][k, np.maximum(table[k], 0)] for k in range(K)]).astype(np.float32)
-
-
-def class_planes(case, n, k):
-    planes, table = planes_of(case), case["table"]
-    return [planes[n, c] if c >= 0 else None for c in table[k]]
-
-
-CASES = load_cases()
 
 
 def test_fixture_holds_the_cases_of_the_issue():

@@ -1,37 +1,14 @@
 """GPU checks of the activation losses (csrc/spx_actloss.hip through EntropySpatLoss, EntropySamplLoss, NormLoss and
 ActivationRegularizers): against the reference-recorded fixture (tests/golden/activation_losses.npz) and the float64
-restatement of tests/test_activation_losses_cpu.py.  Tolerances are those of the KLD kernels' tests for the same comparisons."""
-import math
-
+restatement of tests/activation_loss_cases.py.  Tolerances are those of the KLD kernels' tests for the same comparisons."""
 import pytest
 import torch
-import torch.nn as nn
 
 pytestmark = pytest.mark.gpu
 
-from test_activation_losses_cpu import CASES, EPS, TERMS, load_case, log_activation, restate, restate_term
-
-W3 = (0.7, 1.3, 0.5)
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-def _identity(scale_counts):
-    """scale_counts[s][k]: prototypes of class k in scale s, laid out scale-major / class-minor."""
-    rows, ranges = [], []
-    for counts in scale_counts:
-        lo = len(rows)
-        for k, n in enumerate(counts):
-            rows += [k] * n
-        ranges.append((lo, len(rows)))
-    ident = torch.zeros(len(rows), len(scale_counts[0]))
-    for i, k in enumerate(rows):
-        ident[i, k] = 1
-    return ident, ranges
+from activation_loss_cases import (CASES, EPS, TERMS, W3, check_against_reference64, identity, load_case, log_activation, reference64,
+                                   restate_term)
+from support import gpu_device, proto_net
 
 
 def _patchy_target(B, H, W, K, gen, salt=0.03):
@@ -68,29 +45,6 @@ def _from_map(m):
     return m.reshape(B, P, -1).permute(0, 2, 1).reshape(-1, P)
 
 
-def _reference64(d, target, ident, ranges, norm_type, weights, transform):
-    """float64 restatement on ``d`` [B*HW, P] with a = transform(d): (terms dict, counts, gradient of the weighted total to d)."""
-    dd = d.double().clone().requires_grad_(True)
-    vals, counts = restate(transform(dd), target, ident, ranges, norm_type=norm_type)
-    total = weights[0] * vals["spat"] + weights[1] * vals["sampl"] + weights[2] * vals["norm"]
-    total.backward()
-    return {k: v.item() for k, v in vals.items()}, counts, total.item(), dd.grad
-
-
-def _check_against_reference64(got_total, got_terms, got_grad, ref, what):
-    vals, counts, total, grad = ref
-    for i, k in enumerate(("spat", "sampl", "norm")):
-        err = abs(got_terms[i].item() - vals[k])
-        print(f"{what}: {k} got {got_terms[i].item():.9g} ref {vals[k]:.9g} err {err:.3g} items {counts[k]}")
-        assert counts[k] > 0
-        assert err <= 1e-5 * max(1.0, abs(vals[k])), (what, k)
-    assert abs(got_total.item() - total) <= 1e-5 * max(1.0, abs(total)), what
-    gmax = grad.abs().max().item()
-    gerr = (got_grad.double().cpu() - grad).abs().max().item()
-    print(f"{what}: gradient err {gerr:.3g} of max {gmax:.3g}")
-    assert gerr <= 1e-4 * gmax + 1e-12, what
-
-
 def _drop_in(spx, term, ident, S, ranges):
     if term == "spat":
         return spx.EntropySpatLoss(ident)
@@ -114,7 +68,7 @@ def test_fixture_parity(name):
     fixture's own distance from that restatement, computed here (not a constant)."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     c = load_case(name)
     ident, target = c["ident"], c["target"]
     B, H, W = target.shape
@@ -182,42 +136,42 @@ def test_edges_against_the_float64_restatement(grid, linear_walk):
     """2: the column walk, partial tiles and the linear walk; ragged per-class counts with ns = 1 and a class without prototypes."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     H, W = grid
     B, K = 2, 6
     gen = torch.Generator().manual_seed(1000 * H + W)
-    ident, rl = _identity(EDGE_COUNTS)
+    ident, rl = identity(EDGE_COUNTS)
     ranges = {s: r for s, r in enumerate(rl)}
     target = _patchy_target(B, H, W, K, gen)
     d = torch.rand(B * H * W, ident.shape[0], generator=gen) * 2.0
     for nt in ("l1", "linf"):
-        ref = _reference64(d, target, ident, rl, nt, W3, log_activation)
+        ref = reference64(d, target, ident, rl, nt, W3, log_activation)
         x = _to_map(d, B, H, W).to(dev).requires_grad_(True)
         cd, tgt = _class_distances(x, target, ident, dev, grid=(1, H * W) if linear_walk else (H, W))
         tot, terms = spx.ActivationRegularizers(ident, 2, ranges, *W3, norm_type=nt)(cd, tgt)
         tot.backward()
-        _check_against_reference64(tot, terms, _from_map(x.grad), ref, f"{grid} linear={linear_walk} {nt}")
+        check_against_reference64(tot, terms, _from_map(x.grad), ref, f"{grid} linear={linear_walk} {nt}")
 
 
 def test_slot_limit():
     """3: sixteen slots per class run; seventeen are refused."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, H, W, K = 2, 9, 33, 3
     gen = torch.Generator().manual_seed(16)
-    ident, rl = _identity([[4, 4, 4]] * 4)
+    ident, rl = identity([[4, 4, 4]] * 4)
     ranges = {s: r for s, r in enumerate(rl)}
     target = _patchy_target(B, H, W, K, gen, salt=0.1)
     d = torch.rand(B * H * W, ident.shape[0], generator=gen) * 2.0
-    ref = _reference64(d, target, ident, rl, "l1", W3, log_activation)
+    ref = reference64(d, target, ident, rl, "l1", W3, log_activation)
     x = _to_map(d, B, H, W).to(dev).requires_grad_(True)
     cd, tgt = _class_distances(x, target, ident, dev)
     assert cd.values.shape[1] == 16
     tot, terms = spx.ActivationRegularizers(ident, 4, ranges, *W3)(cd, tgt)
     tot.backward()
-    _check_against_reference64(tot, terms, _from_map(x.grad), ref, "J = 16")
-    ident17, rl17 = _identity([[17, 2, 2]])
+    check_against_reference64(tot, terms, _from_map(x.grad), ref, "J = 16")
+    ident17, rl17 = identity([[17, 2, 2]])
     act = torch.rand(B * H * W, 21, generator=gen).to(dev)
     with pytest.raises(spx.SpxError):
         spx.NormLoss(ident17, "l1")(act, target.to(dev))
@@ -229,20 +183,20 @@ def test_large_class_count():
     """4: 150 classes x 12 slots: the per-class tables of the sums and gradient passes span several class blocks."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, H, W, K = 2, 33, 65, 150
     gen = torch.Generator().manual_seed(150)
-    ident, rl = _identity([[3] * K] * 4)
+    ident, rl = identity([[3] * K] * 4)
     ranges = {s: r for s, r in enumerate(rl)}
     target = _patchy_target(B, H, W, K, gen, salt=0.3)
     d = torch.rand(B * H * W, ident.shape[0], generator=gen) * 2.0
-    ref = _reference64(d, target, ident, rl, "l1", W3, log_activation)
+    ref = reference64(d, target, ident, rl, "l1", W3, log_activation)
     x = _to_map(d, B, H, W).to(dev).requires_grad_(True)
     cd, tgt = _class_distances(x, target, ident, dev)
     assert cd.values.shape[1] == 12
     tot, terms = spx.ActivationRegularizers(ident, 4, ranges, *W3)(cd, tgt)
     tot.backward()
-    _check_against_reference64(tot, terms, _from_map(x.grad), ref, "K = 150")
+    check_against_reference64(tot, terms, _from_map(x.grad), ref, "K = 150")
 
 
 def test_linf_ties():
@@ -250,10 +204,10 @@ def test_linf_ties():
     the same on equal activations (mode 0)."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, H, W, K = 2, 7, 9, 3
     gen = torch.Generator().manual_seed(5)
-    ident, rl = _identity([[2, 2, 2], [2, 2, 2]])
+    ident, rl = identity([[2, 2, 2], [2, 2, 2]])
     target = torch.randint(0, K + 1, (B, H, W), generator=gen)
     seg = torch.nonzero(target[1].reshape(-1) == 2).flatten() + H * W          # rows of segment (image 1, class 1) in [B*HW, P]
     assert len(seg) >= 8
@@ -287,9 +241,9 @@ def test_empty():
     """6: no labelled pixel: every term is exactly 0 on the device, the gradient is all zero."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, H, W = 2, 7, 9
-    ident, rl = _identity([[2, 2, 2], [2, 2, 2]])
+    ident, rl = identity([[2, 2, 2], [2, 2, 2]])
     ranges = {s: r for s, r in enumerate(rl)}
     gen = torch.Generator().manual_seed(6)
     target = torch.zeros(B, H, W, dtype=torch.long)
@@ -311,30 +265,30 @@ def test_linear_activation():
     """7: activation = "linear" (a = -d) against the restatement."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, H, W, K = 2, 19, 37, 6
     gen = torch.Generator().manual_seed(7)
-    ident, rl = _identity(EDGE_COUNTS)
+    ident, rl = identity(EDGE_COUNTS)
     ranges = {s: r for s, r in enumerate(rl)}
     target = _patchy_target(B, H, W, K, gen, salt=0.1)
     d = torch.rand(B * H * W, ident.shape[0], generator=gen) * 2.0
     for nt in ("l1", "linf"):
-        ref = _reference64(d, target, ident, rl, nt, W3, lambda t: -t)
+        ref = reference64(d, target, ident, rl, nt, W3, lambda t: -t)
         x = _to_map(d, B, H, W).to(dev).requires_grad_(True)
         cd, tgt = _class_distances(x, target, ident, dev)
         tot, terms = spx.ActivationRegularizers(ident, 2, ranges, *W3, norm_type=nt, activation="linear")(cd, tgt)
         tot.backward()
-        _check_against_reference64(tot, terms, _from_map(x.grad), ref, f"linear {nt}")
+        check_against_reference64(tot, terms, _from_map(x.grad), ref, f"linear {nt}")
 
 
 def test_fused_equals_separate_terms():
     """8: ActivationRegularizers(w1, w2, w3) = sum of w_i x drop-in i, value and gradient."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, H, W, K = 2, 19, 37, 6
     gen = torch.Generator().manual_seed(8)
-    ident, rl = _identity(EDGE_COUNTS)
+    ident, rl = identity(EDGE_COUNTS)
     ranges = {s: r for s, r in enumerate(rl)}
     target = _patchy_target(B, H, W, K, gen, salt=0.1)
     d = _to_map(torch.rand(B * H * W, ident.shape[0], generator=gen) * 2.0, B, H, W)
@@ -355,29 +309,6 @@ def test_fused_equals_separate_terms():
         assert gmax > 0 and (x.grad - y.grad).abs().max().item() <= 1e-6 * gmax
 
 
-class _Backbone(nn.Module):
-    """Stand-in for the DeepLab backbone (features are fed directly)."""
-
-    def __init__(self, ch):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return x
-
-
-def _net(dev, seed, P=24, K=3, S=2, Cs=16):
-    import scaleprotoseg_amd as spx
-
-    torch.manual_seed(seed)
-    net = spx.PPNetMultiScale(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S)
-    return net.to(dev)
-
-
 def _regs(spx, net, **kw):
     return spx.ActivationRegularizers(net.prototype_class_identity, net.num_scales, net.scale_num_prototypes, *W3,
                                       epsilon=net.epsilon, **kw)
@@ -388,9 +319,9 @@ def test_through_the_module():
     return_activations=True activations: value and the gradients to the prototypes and the features."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, H, W, K, S, Cs = 2, 9, 9, 3, 2, 16
-    net = _net(dev, 9)
+    net = proto_net(24, 3, 2, 16, seed=9, device=dev)
     gen = torch.Generator().manual_seed(9)
     conv = torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=gen)).to(torch.bfloat16).float()
     target = torch.randint(0, K + 1, (B, H, W), generator=gen).to(dev)
@@ -423,9 +354,9 @@ def test_no_host_synchronisation():
     """10: after a first call (caches), forward and backward run without a host synchronisation, in both input forms."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, H, W, K, S, Cs = 2, 9, 9, 3, 2, 16
-    net = _net(dev, 10)
+    net = proto_net(24, 3, 2, 16, seed=10, device=dev)
     gen = torch.Generator().manual_seed(10)
     x = torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=gen)).to(dev)
     target = torch.randint(0, K + 1, (B, H, W), generator=gen).to(dev)
@@ -465,9 +396,9 @@ def test_captured_step_replays_eager_bit_for_bit():
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.graphs import capture_step
 
-    dev = _dev()
+    dev = gpu_device()
     B, H, W, K, S, Cs = 2, 9, 9, 3, 2, 16
-    net = _net(dev, 11)
+    net = proto_net(24, 3, 2, 16, seed=11, device=dev)
     gen = torch.Generator().manual_seed(11)
     x = torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=gen)).to(dev)
     target = torch.randint(0, K + 1, (B, H, W), generator=gen).to(dev)

@@ -22,9 +22,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import ppnet_oracle as O
+from support import BF16_DX_TOL, gpu_device, GRAD_TOL
 
-GRAD_TOL = 1e-3        # tests/test_gpu_parity.py
-BF16_DX_TOL = 4e-3     # dX returned in bf16: one output rounding
 
 K = 19
 # name: (S, Cs, per-scale prototype counts, H, W)
@@ -38,12 +37,7 @@ CASES = {
 }
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
+# (local: a cached case with its oracle gradients; parity_cases.problem only draws inputs)
 @functools.lru_cache(maxsize=None)
 def _problem(name):
     """Inputs, upstream gradients and the oracle's results of one case; computed once, shared by the tests, never modified."""
@@ -133,7 +127,7 @@ def _check(pr, x_dtype, dev, ref_key, **kw):
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_backward_instance(name, x_dtype, monkeypatch):
     """Cases a-f of the table above, both feature types (d: the fp32 instance sums in dX, the bf16 one in the scratch)."""
-    dev = _dev()
+    dev = gpu_device()
     pr = _problem(name)
     _nan_filled_empty_like(monkeypatch)
     _check(pr, x_dtype, dev, "both")
@@ -143,7 +137,7 @@ def test_backward_instance(name, x_dtype, monkeypatch):
 def test_backward_instance_partial_inputs(variant, monkeypatch):
     """Case a with one input of the backward missing: no distance gradient, no logits gradient (no head), features frozen
     (the kernel then writes no dX at all)."""
-    dev = _dev()
+    dev = gpu_device()
     pr = _problem("a_six_blocks_partial_last")
     _nan_filled_empty_like(monkeypatch)
     if variant == "no_ddist":

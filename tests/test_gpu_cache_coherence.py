@@ -5,11 +5,11 @@ the ``target`` / ``target_version`` attachment of ``ClassDistances``.
 
 Every result that follows an edit is held against the CPU oracle (oracle/ppnet_oracle.py, the float64 restatements of the
 loss tests) evaluated on the values AS THEY ARE NOW, with the bounds the suite already states:
-  forward      ``_assert_fwd`` of tests/test_gpu_parity.py (distances 1e-4 (1 + d), activations 2e-4 (1 + |a|), logits 1e-4)
-  gradients    ``GRAD_TOL`` = 1e-3 of max|g|, ``BF16_DX_TOL`` = 4e-3 for dX returned in bf16 (tests/test_gpu_parity.py)
+  forward      ``assert_fwd`` of tests/parity_cases.py (distances 1e-4 (1 + d), activations 2e-4 (1 + |a|), logits 1e-4)
+  gradients    ``GRAD_TOL`` = 1e-3 of max|g|, ``BF16_DX_TOL`` = 4e-3 for dX returned in bf16 (tests/support.py)
   KLD          1e-4 max(1, |ref|)      (tests/test_gpu_parity.py::test_kld_through_the_module)
-  activation   1e-5 max(1, |ref|)      (tests/test_gpu_activation_losses.py::_check_against_reference64)
-  regularisers 1e-6                    (tests/test_gpu_regularizers.py::_check_against_f64)
+  activation   1e-5 max(1, |ref|)      (tests/activation_loss_cases.py::check_against_reference64)
+  regularisers 1e-6                    (tests/regularizer_cases.py::check_against_f64)
   push / prune bit for bit on the same distance map
 and every case first asserts, with the oracle alone, that the reference before the edit and after it differ by at least
 100x the bound used at the maximum element: a stale result cannot pass."""
@@ -23,27 +23,24 @@ import torch.nn as nn
 pytestmark = pytest.mark.gpu
 
 from oracle import ppnet_oracle as O
-from test_activation_losses_cpu import log_activation
-from test_activation_losses_cpu import restate as act_restate
-from test_gpu_parity import BF16_DX_TOL, GRAD_TOL, _assert_fwd, _grad_close
+from activation_loss_cases import W3, log_activation
+from activation_loss_cases import restate as act_restate
+from parity_cases import assert_fwd, close_fwd
+from push_cases import push_problem
+from regularizer_cases import check_against_f64
+from regularizer_cases import restate as reg_restate
+from support import BF16_DX_TOL, GRAD_TOL, gpu_device, grad_close, group_net, proto_net
 
 KLD_TOL = 1e-4           # tests/test_gpu_parity.py::test_kld_through_the_module
-ACT_TOL = 1e-5           # tests/test_gpu_activation_losses.py::_check_against_reference64
-REG_TOL = 1e-6           # tests/test_gpu_regularizers.py::_check_against_f64
+ACT_TOL = 1e-5           # tests/activation_loss_cases.py::check_against_reference64
+REG_TOL = 1e-6           # tests/regularizer_cases.py::check_against_f64
 GROUP_ACT_TOL = 2e-4     # tests/test_gpu_modules.py: |g - ref| <= 2e-4 (1 + |ref|) for compute_group's list
-W3 = (0.7, 1.3, 0.5)     # weights of the three activation terms (tests/test_gpu_activation_losses.py)
 
 # the smallest problem that still runs every cached consumer of the prototype-phase module: two scales, 4 prototypes per
 # (class, scale), a 128-pixel grid (one tile per image, two images)
 B, S, Cs, P, K, H, W = 2, 2, 32, 40, 5, 8, 16
 # the group module: P = 60, K = 6, G = 2 on a ragged 9 x 11 grid
 GS, GCs, GP, GK, GG, GH, GW = 2, 16, 60, 6, 2, 9, 11
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(autouse=True)
@@ -100,6 +97,7 @@ def _cotangents(rows, group=False):
     return _once(("cot", rows, group), make)
 
 
+# (local: memoised 2 x 4 label patches of this module's two grids; parity_cases.gather_labels draws per pixel)
 def _labels(seed=0, group=False):
     """[B, H, W] in the reference's convention (0 = void, 1..K): 2 x 4 patches of one label, so that every segment has pixels."""
     def make():
@@ -110,30 +108,13 @@ def _labels(seed=0, group=False):
     return _once(("labels", seed, group), make)
 
 
-class _Backbone(nn.Module):
-    """Stand-in for the DeepLab backbone (features are fed directly)."""
-
-    def __init__(self, ch):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return x
-
-
 def _net(dev, seed=1):
-    import scaleprotoseg_amd as spx
-
-    net = spx.PPNetMultiScale(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S)
-    net.add_on_layers = nn.Sequential()             # conv_features(x) = x: push_min_distances sees the features as they are
-    with torch.no_grad():
+    def init(net):
         net.prototype_vectors.copy_(_bank(seed))
         net.last_layer.weight.copy_(_head(seed, net.prototype_class_identity))
-    return net.to(dev)
+
+    # (an empty add-on: conv_features(x) = x, so push_min_distances sees the features as they are)
+    return proto_net(P, K, S, Cs, add_on=nn.Sequential(), init=init, device=dev)
 
 
 def _ranges(net):
@@ -160,7 +141,7 @@ def _bound(kind, ref, dx_tol=GRAD_TOL):
     if kind in ("act", "groups"):
         return 2e-4 * (1 + top)
     if kind == "logits":
-        return 1.1e-4 * 1.2 * max(1.0, top)             # the per-element bound of _assert_fwd at the largest element
+        return 1.1e-4 * 1.2 * max(1.0, top)             # the per-element bound of assert_fwd at the largest element
     if kind in ("push", "wd"):
         return 0.0                                       # bit for bit
     return (dx_tol if kind == "dx" else GRAD_TOL) * top  # gradients: max-normalised
@@ -185,17 +166,17 @@ def _check_consumers(net, dev, ref, x_dtype=torch.float32):
     x0 = _conv().to(dev, x_dtype)
     with torch.no_grad():
         logits, dist = net.forward_from_conv_features(x0)
-    _assert_fwd(logits, dist, None, ref["logits"], ref["dist"], None)
+    assert_fwd(logits, dist, None, ref["logits"], ref["dist"], None)
     gl, gd, _ = _cotangents(rows)
     net.zero_grad(set_to_none=True)
     x = _conv().to(dev, x_dtype).requires_grad_(True)
     lg, d = net.forward_from_conv_features(x)
     torch.autograd.backward([lg, d], [gl.to(dev), gd.to(dev)])
-    _assert_fwd(lg.detach(), d.detach(), None, ref["logits"], ref["dist"], None)
+    assert_fwd(lg.detach(), d.detach(), None, ref["logits"], ref["dist"], None)
     assert x.grad.dtype == x_dtype
-    _grad_close(x.grad, ref["dx"], "dX", tol=GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL)
-    _grad_close(net.prototype_vectors.grad, ref["dp"], "dPrototypes")
-    _grad_close(net.last_layer.weight.grad, ref["dw"], "dLastLayer")
+    grad_close(x.grad, ref["dx"], "dX", tol=GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL)
+    grad_close(net.prototype_vectors.grad, ref["dp"], "dPrototypes")
+    grad_close(net.last_layer.weight.grad, ref["dw"], "dLastLayer")
     net.zero_grad(set_to_none=True)
     del lg, d, x
     # the fused push minimum and the fused prune search: bit for bit what the two-step forms give on the map just verified
@@ -223,7 +204,7 @@ def _plain_problem(dev, grad=False):
 
 
 def test_untouched_parameters_are_served_from_the_cache():
-    dev = _dev()
+    dev = gpu_device()
     net = _net(dev)
     ref = _oracle(net)
     x = _conv().to(dev)
@@ -232,20 +213,20 @@ def test_untouched_parameters_are_served_from_the_cache():
         with torch.no_grad():
             logits, dist = net.forward_from_conv_features(x)
     assert _stats() == (1, n - 1)
-    _assert_fwd(logits, dist, None, ref["logits"], ref["dist"], None)
+    assert_fwd(logits, dist, None, ref["logits"], ref["dist"], None)
 
 
 def test_packs_with_and_without_the_transposed_operands_are_separate_entries():
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     x, pv, w, lay, ident, ranges = _plain_problem(dev)
     rl, rd, _ = O.forward_from_conv_features(_conv(), _bank(1), ranges, S, _head(1, ident))
     for grad in (False, True, False, True):
         pv.requires_grad_(grad)
         w.requires_grad_(grad)
         logits, dist, _ = proto_head_forward(x, pv, w, lay(K))
-        _assert_fwd(logits, dist, None, rl, rd, None)
+        assert_fwd(logits, dist, None, rl, rd, None)
     assert _stats() == (2, 2)
     (logits.sum() + dist.sum()).backward()                  # the entry served to a differentiable forward carries bank^T / head^T
     assert torch.isfinite(pv.grad).all() and torch.isfinite(w.grad).all()
@@ -257,7 +238,7 @@ def test_push_and_prune_share_the_distance_only_packs():
     another entry."""
     from scaleprotoseg_amd.functional import proto_head_forward, prune_nearest_from_features, push_min_from_features
 
-    dev = _dev()
+    dev = gpu_device()
     x, pv, w, lay, ident, ranges = _plain_problem(dev)
     lab = _labels().to(dev)
     idx, val = push_min_from_features(x, pv, lay(1), lab, ident, void_class=0)
@@ -269,7 +250,7 @@ def test_push_and_prune_share_the_distance_only_packs():
     proto_head_forward(x, pv, w, lay(K))
     assert _stats() == (2, 2)
     rd = O.scale_l2_convolution(_conv(), _bank(1), ranges, S)
-    _assert_fwd(None, dist, None, None, rd, None)
+    assert_fwd(None, dist, None, None, rd, None)
     ridx, rval = O.push_masked_argmin(dist.cpu(), _labels(), ident, K, void_class=0)
     assert torch.equal(idx.cpu(), ridx) and torch.equal(val.cpu(), rval)
 
@@ -280,7 +261,7 @@ def test_nothing_is_cached_during_stream_capture():
     from scaleprotoseg_amd import functional as F
     from scaleprotoseg_amd.graphs import capture_step
 
-    dev = _dev()
+    dev = gpu_device()
     x, pv, w, lay, ident, ranges = _plain_problem(dev)
 
     def step():
@@ -295,19 +276,19 @@ def test_nothing_is_cached_during_stream_capture():
     _assert_discriminates(dict(logits=before[0], dist=before[1]), dict(logits=after[0], dist=after[1]), ("logits", "dist"))
     graph.replay()
     torch.cuda.synchronize()
-    _assert_fwd(logits, dist, None, before[0], before[1], None)
+    assert_fwd(logits, dist, None, before[0], before[1], None)
     with torch.no_grad():
         pv.copy_(_bank(2).to(dev))
     graph.replay()
     torch.cuda.synchronize()
-    _assert_fwd(logits, dist, None, after[0], after[1], None)
+    assert_fwd(logits, dist, None, after[0], after[1], None)
     assert _stats() == (1, 0) and len(F._PACK_CACHE) == 0
 
 
 def test_the_cache_holds_a_bounded_number_of_entries():
     from scaleprotoseg_amd import functional as F
 
-    dev = _dev()
+    dev = gpu_device()
     x, pv, w, lay, ident, ranges = _plain_problem(dev)
     heads = [_head(10 + i, ident).to(dev) for i in range(F._PACK_CACHE_MAX + 3)]       # all alive: distinct objects and addresses
     for h in heads:
@@ -319,7 +300,7 @@ def test_the_cache_holds_a_bounded_number_of_entries():
     F.proto_head_forward(x, pv, heads[0], lay(K))                                 # ... the oldest was dropped
     assert _stats() == (len(heads) + 1, 1)
     rl, rd, _ = O.forward_from_conv_features(_conv(), _bank(1), ranges, S, heads[-1].cpu())
-    _assert_fwd(logits, dist, None, rl, rd, None)
+    assert_fwd(logits, dist, None, rl, rd, None)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -448,7 +429,7 @@ BF16_EDITS = ("sgd", "data_assign", "prune")        # bf16 features: dX through 
 @pytest.mark.parametrize("edit,x_dtype", [(e, torch.float32) for e in EDITS] + [(e, torch.bfloat16) for e in BF16_EDITS],
                          ids=[e + "-fp32" for e in EDITS] + [e + "-bf16" for e in BF16_EDITS])
 def test_every_consumer_sees_the_edit(edit, x_dtype):
-    dev = _dev()
+    dev = gpu_device()
     dx_tol = GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL
     net = _net(dev)
     before = _oracle(net)
@@ -464,14 +445,13 @@ def test_every_consumer_sees_the_edit(edit, x_dtype):
 
 
 def test_the_push_commit_reaches_every_consumer(tmp_path):
-    """``push_prototypes_multiscale`` end to end (the problem of tests/test_gpu_modules.py) on a module whose packs are
+    """``push_prototypes_multiscale`` end to end (the problem of tests/push_cases.py) on a module whose packs are
     cached: the push's own forwards cache the old bank, the commit writes through ``.data`` and prunes the duplicate."""
     from scaleprotoseg_amd.push import push_prototypes_multiscale
-    from test_gpu_modules import _close_fwd, _push_problem
 
-    dev = _dev()
+    dev = gpu_device()
     S_, K_ = 4, 5
-    net, data, _ = _push_problem(dev, S=S_, K=K_)
+    net, data, _ = push_problem(dev, S=S_, K=K_)
     with torch.no_grad():
         conv = net.conv_features(data[0][0].unsqueeze(0).to(dev))
 
@@ -482,8 +462,8 @@ def test_the_push_commit_reaches_every_consumer(tmp_path):
     def check(ref):
         with torch.no_grad():
             logits, dist = net.forward_from_conv_features(conv)
-        _close_fwd(dist, ref[1], "distances")
-        _close_fwd(logits, ref[0], "logits")
+        close_fwd(dist, ref[1], "distances")
+        close_fwd(logits, ref[0], "logits")
 
     before = oracle()
     check(before)
@@ -500,19 +480,17 @@ def test_the_push_commit_reaches_every_consumer(tmp_path):
 
 # ---- the group module: the cached tail (last_layer_group.weight) and the per-forward dense matrix wd ---------------------
 def _group_net(dev, seed=1):
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet
     from scaleprotoseg_amd.utils import projection_simplex_sort
 
-    net = GroupNet(_Backbone(GS * GCs), 64, (GP, GCs, 1, 1), [], GK, add_on_layers_type="deeplab_simple",
-                   patch_classification=True, num_scales=GS, num_groups=GG)
-    net.add_on_layers = nn.Sequential()
     g = _gen(200 + seed)
-    with torch.no_grad():
+
+    def init(net):
         net.prototype_vectors.copy_(_bank(seed, GP, GCs))
         for gp in net.group_projection:
             gp.weight.copy_(projection_simplex_sort(torch.rand(gp.weight.shape, generator=g)))
         net.last_layer_group.weight.add_(0.3 * torch.randn(net.last_layer_group.weight.shape, generator=g))
-    return net.to(dev)
+
+    return group_net(GP, GK, GS, GCs, GG, add_on=nn.Sequential(), init=init, device=dev)
 
 
 def _group_oracle(net):
@@ -535,15 +513,15 @@ def _check_group_consumers(net, dev, ref):
     net.zero_grad(set_to_none=True)
     x = _conv(group=True).to(dev).requires_grad_(True)
     logits, dist, act = net.forward_from_conv_features(x, return_activations=True, return_distances=True)
-    _assert_fwd(logits.detach(), dist.detach(), act.detach(), ref["logits"], ref["dist"], ref["act"])
+    assert_fwd(logits.detach(), dist.detach(), act.detach(), ref["logits"], ref["dist"], ref["act"])
     for a in (act, act.detach().clone()):                   # the forward's own tag, and the product kernels on foreign activations
         groups = torch.cat(net.compute_group(a), dim=-1).detach().cpu()
         assert ((groups - ref["groups"]).abs() <= GROUP_ACT_TOL * (1 + ref["groups"].abs())).all(), "compute_group"
     torch.autograd.backward([logits, dist, act], [gl.to(dev), gd.to(dev), ga.to(dev)])
-    _grad_close(x.grad, ref["dx"], "dX")
-    _grad_close(net.prototype_vectors.grad, ref["dp"], "dPrototypes")
-    _grad_close(net.last_layer_group.weight.grad, ref["dtail"], "dLastLayerGroup")
-    _grad_close(torch.cat([gp.weight.grad.reshape(-1) for gp in net.group_projection]), ref["dgw"], "dGroupProjection")
+    grad_close(x.grad, ref["dx"], "dX")
+    grad_close(net.prototype_vectors.grad, ref["dp"], "dPrototypes")
+    grad_close(net.last_layer_group.weight.grad, ref["dtail"], "dLastLayerGroup")
+    grad_close(torch.cat([gp.weight.grad.reshape(-1) for gp in net.group_projection]), ref["dgw"], "dGroupProjection")
     net.zero_grad(set_to_none=True)
 
 
@@ -603,7 +581,7 @@ GROUP_EDITS = {f.__name__[len("_gedit_"):]: f for f in (_gedit_sgd, _gedit_simpl
 
 @pytest.mark.parametrize("edit", list(GROUP_EDITS))
 def test_the_group_module_sees_the_edit(edit):
-    dev = _dev()
+    dev = gpu_device()
     net = _group_net(dev)
     before = _group_oracle(net)
     _check_group_consumers(net, dev, before)
@@ -623,7 +601,7 @@ def _forward_checked(net, dev, what):
         logits, dist = net.forward_from_conv_features(_conv().to(dev))
     torch.cuda.synchronize()
     try:
-        _assert_fwd(logits, dist, None, ref["logits"], ref["dist"], None)
+        assert_fwd(logits, dist, None, ref["logits"], ref["dist"], None)
     except AssertionError as e:
         raise AssertionError(f"{what}: {e}") from None
     return ref
@@ -641,7 +619,7 @@ def test_rebinding_onto_a_recycled_address_never_hits(which):
     parameter's size is then the block of the value before the last.  The test asserts that precondition - some rebind within
     six lands on an address an earlier, different value was packed from - and fails, not skips, when the allocator does not
     comply (the cache holds 8 entries: six rebinds stay below that)."""
-    dev = _dev()
+    dev = gpu_device()
     net = _net(dev)
     p = net.prototype_vectors if which == "bank" else net.last_layer.weight
     torch.cuda.synchronize()
@@ -675,7 +653,7 @@ def test_two_rebinds_without_a_forward_in_between(which):
     """v1 is packed; the parameter is rebound to v2 and at once to v3 - where the block v1 lived in is the natural candidate.
     (While an entry packed from v1's storage is alive that block must not be reissued at all; either way the forward computes
     with v3.)"""
-    dev = _dev()
+    dev = gpu_device()
     net = _net(dev)
     p = net.prototype_vectors if which == "bank" else net.last_layer.weight
     first = _forward_checked(net, dev, "value 1")
@@ -696,7 +674,7 @@ def test_cpu_round_trips_onto_recycled_addresses_never_hit():
     """``net.cpu()``, ``p.data = new``, ``net.to(dev)``: ``Module._apply`` rebinds every parameter (same object, same version)
     and the allocator serves the same sizes in the same order, so a parameter comes back to an address it had.  Precondition
     asserted as above: within six round trips some value lands where an earlier one was packed from."""
-    dev = _dev()
+    dev = gpu_device()
     net = _net(dev)
     pv, w = net.prototype_vectors, net.last_layer.weight
     seen = {(pv.data_ptr(), w.data_ptr()): 1}
@@ -724,7 +702,7 @@ def test_a_new_model_on_a_recycled_parameter_is_not_served_the_old_packs():
     """Models built and dropped in sequence: a new Parameter may land on the ``id`` and the address of a dead one, at the same
     version.  The entry's weak reference tells them apart.  (Whether ids and addresses do recur is up to the interpreter and the
     allocator; the recurrences are printed, the results are held to the oracle either way.)"""
-    dev = _dev()
+    dev = gpu_device()
     seen, prev = {}, None
     for i in range(1, 6):
         net = _net(dev, seed=i)
@@ -812,7 +790,7 @@ def _check_table_consumers(net, dev, losses, target):
     with torch.no_grad():
         logits, cd = net.forward_from_conv_features(x, target_labels=tgt)
         _, dist, act = net.forward_from_conv_features(x, return_activations=True, return_distances=True)
-    _assert_fwd(logits, dist, act, ref["logits"], ref["dist"], ref["act"])
+    assert_fwd(logits, dist, act, ref["logits"], ref["dist"], ref["act"])
     assert isinstance(cd, spx.ClassDistances) and torch.equal(cd.table.cpu(), lref["table"])
     got = cd.values.cpu().permute(0, 2, 1)
     assert got.shape == lref["gathered"].shape
@@ -835,7 +813,7 @@ def _check_table_consumers(net, dev, losses, target):
 def test_table_caches_follow_the_edit(edit):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     net = _net(dev)
     target = _labels(1)
     kld = spx.KLDLoss(net.prototype_class_identity, S, net.scale_num_prototypes)
@@ -896,25 +874,21 @@ REG_WEIGHTS = (0.25, 0.1, 0.3, 1e-3)
 
 
 def _check_group_tables(net, dev, reg):
-    from test_gpu_regularizers import _check_against_f64
-
     wd_ref = _dense_reference(net)
     assert torch.equal(net._dense_group_matrix().detach().cpu(), wd_ref), "_dense_group_matrix"
     act = torch.rand(37, net.num_prototypes, generator=_gen(9)) * 3.0
     ref = torch.cat(O.compute_group(act, net.prototype_class_identity.cpu(), [gp.weight.detach().cpu() for gp in net.group_projection]), dim=-1)
     got = torch.cat(net.compute_group(act.to(dev)), dim=-1).detach().cpu()
     assert ((got - ref).abs() <= GROUP_ACT_TOL * (1 + ref.abs())).all(), "compute_group"
-    _check_against_f64(net, reg, REG_WEIGHTS, 1e-5)
+    check_against_f64(net, reg, REG_WEIGHTS, 1e-5)
     return dict(wd=wd_ref, groups=ref)
 
 
 def _reg_reference(net):
-    from test_regularizers_cpu import restate
-
     ident = net.prototype_class_identity.cpu()
     hg = net.last_layer_group.weight.detach().cpu().numpy()
     w = torch.cat([gp.weight.detach().reshape(-1) for gp in net.group_projection]).cpu().numpy()
-    r = restate(ident, net.scale_num_prototypes, net.num_groups, 1e-5, w, hg, np.zeros((ident.shape[1], ident.shape[0]), np.float32))
+    r = reg_restate(ident, net.scale_num_prototypes, net.num_groups, 1e-5, w, hg, np.zeros((ident.shape[1], ident.shape[0]), np.float32))
     return torch.stack([r["ent"], r["ceg"], r["sm"], r["l1_group"]])
 
 
@@ -922,7 +896,7 @@ def _reg_reference(net):
 def test_group_table_caches_follow_the_edit(edit):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     net = _group_net(dev)
     reg = spx.GroupRegularizers(net, group_ent=REG_WEIGHTS[0], crs_ent_group=REG_WEIGHTS[1], scale_max=REG_WEIGHTS[2], l1=REG_WEIGHTS[3],
                                 epsilon=1e-5)
@@ -959,7 +933,7 @@ def test_the_group_kld_tables_follow_the_group_identity():
     re-assignment to such a swapped copy (finetune_wandb_group.py:77-78 re-assigns it)."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     net = _group_net(dev)
     target, acts = _labels(0, group=True), _group_acts()
     tgt, dacts = target.to(dev), [a.to(dev) for a in acts]
@@ -988,7 +962,7 @@ def test_the_group_kld_tables_follow_the_group_identity():
 def test_an_in_place_edit_of_the_returned_activations_voids_the_group_tag():
     """``compute_group(act)`` takes the group activations the forward left on ``act`` (``spx_group``) only while ``act`` is as the
     forward returned it: after an in-place edit it recomputes from the edited values."""
-    dev = _dev()
+    dev = gpu_device()
     net = _group_net(dev)
     ref = _group_oracle(net)
     with torch.no_grad():
@@ -1013,7 +987,7 @@ def test_losses_given_class_distances_and_labels(variant):
     not give a finite number (the planes cannot be re-gathered): the loss is NaN."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     net = _net(dev)
     target = _labels(1)
     ref = _oracle(net)
@@ -1054,7 +1028,7 @@ def test_the_label_check_does_not_synchronise():
     and for changed ones."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     net = _net(dev)
     tgt = _labels(1).to(dev)
     equal, other = tgt.clone(), (tgt % K + 1)

@@ -27,18 +27,11 @@ import torch
 
 import ce_cases as CC
 from oracle import ppnet_oracle as O
+from support import BF16_DX_TOL, bits_equal, gpu_device, grad_close, GRAD_TOL
 
 pytestmark = pytest.mark.gpu
 
-GRAD_TOL = 1e-3          # tests/test_gpu_modules.py: gradients against the oracle, max-normalised
-BF16_DX_TOL = 4e-3       # dX returned in bf16
 SENTINEL = 0x5A5A5A5A
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
 
 
 @pytest.fixture
@@ -65,10 +58,6 @@ def poisoned(monkeypatch):
     monkeypatch.setattr(torch, "empty", empty)
     monkeypatch.setattr(torch, "empty_like", empty_like)
     return made
-
-
-def _bits_equal(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def _coef(count):
@@ -154,7 +143,7 @@ def _module_run(lg, lab):
 
 @pytest.mark.parametrize("name", CC.CASE_NAMES)
 def test_standalone_kernels_against_float64(name, poisoned):
-    dev = _dev()
+    dev = gpu_device()
     c = CC.case(name)
     ref = _case_reference(name)
     lg, lab = c.logits.to(dev).contiguous(), c.labels.to(dev).contiguous()
@@ -169,12 +158,12 @@ def test_standalone_kernels_against_float64(name, poisoned):
     _check_forward(f"{name} module", ref, lse, m_pred, ref["count"], m_loss, c.no_loss)
     _check_dlogits(f"{name} module", m_grad, lg, lab, ref["count"])
     # the two routes are the same kernels on the same inputs, and a second run of either changes nothing
-    assert _bits_equal(m_loss, loss) and torch.equal(m_pred, pred) and _bits_equal(m_grad, d)
+    assert bits_equal(m_loss, loss) and torch.equal(m_pred, pred) and bits_equal(m_grad, d)
     again = _abi_run(lg, lab)
     for a, b in zip((lse, pred, partials, loss, aux, d), again):
-        assert _bits_equal(a, b)
+        assert bits_equal(a, b)
     m_again = _module_run(lg, lab)
-    assert _bits_equal(m_again[0], m_loss) and torch.equal(m_again[1], m_pred) and _bits_equal(m_again[2], m_grad)
+    assert bits_equal(m_again[0], m_loss) and torch.equal(m_again[1], m_pred) and bits_equal(m_again[2], m_grad)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -184,7 +173,7 @@ def test_standalone_kernels_against_float64(name, poisoned):
 def test_finish_kernel_on_crafted_pairs(n, poisoned):
     from scaleprotoseg_amd.functional import _ce_finish
 
-    dev = _dev()
+    dev = gpu_device()
     pairs, count, total = CC.finish_pairs(n)
     loss, aux = _ce_finish(pairs.to(dev))                               # its outputs come from the poisoned torch.empty
     torch.cuda.synchronize()
@@ -202,7 +191,7 @@ def test_finish_kernel_on_crafted_pairs(n, poisoned):
 def test_shift_labels_kernel(n, dtype, poisoned):
     from scaleprotoseg_amd.functional import shifted_labels_i32
 
-    dev = _dev()
+    dev = gpu_device()
     K = 19
     v = CC.shift_values(n, K, dtype)
     out = shifted_labels_i32(v.to(dev), dev)                             # on the device: the kernel
@@ -297,25 +286,16 @@ def _oracle_grads(conv, bank, head, lab, ranges, S, extra=None):
     return c0.grad, p0.grad, w0.grad
 
 
-def _grad_close(got, ref, what, tol=GRAD_TOL):
-    got, ref = got.detach().float().cpu(), ref.float()
-    assert got.shape == ref.shape
-    scale = ref.abs().max().item() + 1e-30
-    err = (got - ref).abs().max().item()
-    print(f"CE64 {what}: against the oracle {err / scale:.3e} of the maximum (bound {tol:.0e})")
-    assert err <= tol * scale, f"{what}: err {err:.3e} vs scale {scale:.3e}"
-
-
 def _check_oracle(what, res, conv, bank, head, lab, S, x_dtype, extra=None):
     dx, dp, dw = _oracle_grads(conv, bank, head, lab, res["ranges"], S, extra)
-    _grad_close(res["w"].grad, dw, f"{what} dLastLayer")
-    _grad_close(res["x"].grad, dx, f"{what} dX", tol=GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL)
-    _grad_close(res["pv"].grad, dp, f"{what} dPrototypes")
+    grad_close(res["w"].grad, dw, f"{what} dLastLayer", report="CE64")
+    grad_close(res["x"].grad, dx, f"{what} dX", tol=GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL, report="CE64")
+    grad_close(res["pv"].grad, dp, f"{what} dPrototypes", report="CE64")
 
 
 @pytest.mark.parametrize("K,grid,x_dtype", FUSED_RUNS, ids=[f"K{K}-{g}-{'bf16' if t == torch.bfloat16 else 'fp32'}" for K, g, t in FUSED_RUNS])
 def test_fused_epilogue_and_prologue_against_float64(K, grid, x_dtype, poisoned):
-    dev = _dev()
+    dev = gpu_device()
     B, H, W = FUSED_GRIDS[grid]
     S, Cs, P = 1, 32, 48
     conv, bank, head, lab = _fused_inputs(B, S, Cs, P, K, H, W, seed=1000 * K + H * W)
@@ -332,7 +312,7 @@ def test_fused_epilogue_class_gathered(poisoned):
     logits none, so d_logits still comes from the prologue."""
     from scaleprotoseg_amd.functional import ClassGather, class_gather_table
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = 2, 1, 32, 40, 5, 9, 11
     conv, bank, head, _ = _fused_inputs(B, S, Cs, P, K, H, W, seed=5911)
     gen = torch.Generator().manual_seed(5912)
@@ -358,7 +338,7 @@ def test_fused_epilogue_class_gathered(poisoned):
 def test_fused_epilogue_two_scales_above_the_split_limit(K, poisoned):
     """S = 2 takes the epilogue only past 1024 tiles of 128 pixels: 257 x 511 px are 1026.  (K = 3 keeps every class in one
     lane half of the accumulator layout - rows 0 - 3 - so the sums across the halves only matter with K = 19.)"""
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, H, W = 1, 2, 16, 16, 257, 511
     assert (H * W + 127) // 128 == 1026
     conv, bank, head, lab = _fused_inputs(B, S, Cs, P, K, H, W, seed=257511 + K)
@@ -371,7 +351,7 @@ def test_fused_epilogue_two_scales_above_the_split_limit(K, poisoned):
 def test_standalone_forward_behind_a_scale_parallel_launch(K, poisoned):
     """Two scales on a small grid (the training crops' launch): the forward runs scale-parallel, spx_ce_fwd takes the summed
     logits, and the backward's prologue reads the lse that kernel left."""
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, H, W = 2, 2, 32, 48, 17, 19
     conv, bank, head, lab = _fused_inputs(B, S, Cs, P, K, H, W, seed=2200 + K)
     res = _fused_run(conv, bank, head, lab, S, torch.float32, dev, poisoned, split=True)
@@ -384,7 +364,7 @@ def test_standalone_forward_behind_a_scale_parallel_launch(K, poisoned):
 def test_fused_epilogue_breaks_ties_to_the_lower_class(K, lo, hi, poisoned):
     """Two identical positive head rows, every other row zero: the two logit columns are bit-equal and the largest, and
     sit in different lane halves / class blocks of the accumulator layout."""
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, H, W = 1, 1, 32, 48, 17, 19
     gen = torch.Generator().manual_seed(K)
     head = torch.zeros(K, P)
@@ -392,7 +372,7 @@ def test_fused_epilogue_breaks_ties_to_the_lower_class(K, lo, hi, poisoned):
     conv, bank, head, lab = _fused_inputs(B, S, Cs, P, K, H, W, seed=77 + K, head=head)
     res = _fused_run(conv, bank, head, lab, S, torch.float32, dev, poisoned)
     lg = res["logits"]
-    assert _bits_equal(lg[:, lo].contiguous(), lg[:, hi].contiguous()) and bool((lg[:, lo] > 0).all())
+    assert bits_equal(lg[:, lo].contiguous(), lg[:, hi].contiguous()) and bool((lg[:, lo] > 0).all())
     others = torch.ones(K, dtype=torch.bool)
     others[[lo, hi]] = False
     assert not lg[:, others.to(dev)].any()
@@ -402,7 +382,7 @@ def test_fused_epilogue_breaks_ties_to_the_lower_class(K, lo, hi, poisoned):
 
 @pytest.mark.parametrize("K", [19, 65])
 def test_fused_epilogue_on_an_all_zero_head(K, poisoned):
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, H, W = 1, 1, 32, 48, 17, 19
     conv, bank, head, lab = _fused_inputs(B, S, Cs, P, K, H, W, seed=99 + K, head=torch.zeros(K, P))
     res = _fused_run(conv, bank, head, lab, S, torch.float32, dev, poisoned)
@@ -416,7 +396,7 @@ def test_fused_epilogue_on_an_all_zero_head(K, poisoned):
 
 
 def test_fused_epilogue_with_every_pixel_ignored(poisoned):
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = 1, 1, 32, 48, 19, 17, 19
     conv, bank, head, _ = _fused_inputs(B, S, Cs, P, K, H, W, seed=4242)
     bad = torch.tensor([-1, -2, K, K + 7, CC.INT32_MIN, CC.INT32_MAX])
@@ -464,7 +444,7 @@ def _tail_run(U, K2, B, H, W, dev, made, wg=None, lab=None, seed=0):
 
 @pytest.mark.parametrize("U,K2,B,H,W", TAIL_RUNS)
 def test_group_tail_against_float64(U, K2, B, H, W, poisoned):
-    dev = _dev()
+    dev = gpu_device()
     M = B * H * W
     res = _tail_run(U, K2, B, H, W, dev, poisoned)
     what = f"tail U={U} K2={K2} M={M}"
@@ -479,13 +459,13 @@ def test_group_tail_against_float64(U, K2, B, H, W, poisoned):
 
 def test_group_tail_breaks_ties_across_class_quarters(poisoned):
     """Classes 3 and 19 (class quarters 0 and 2) with identical positive rows of W_g, every other row zero."""
-    dev = _dev()
+    dev = gpu_device()
     U, K2, B, H, W = 63, 21, 1, 7, 9
     gen = torch.Generator().manual_seed(319)
     wg = torch.zeros(K2, U)
     wg[3] = wg[19] = torch.rand(U, generator=gen) * 0.1 + 0.01
     res = _tail_run(U, K2, B, H, W, dev, poisoned, wg=wg, seed=1)
     lg = res["logits"]
-    assert _bits_equal(lg[:, 3].contiguous(), lg[:, 19].contiguous()) and bool((lg[:, 3] > 0).all())
+    assert bits_equal(lg[:, 3].contiguous(), lg[:, 19].contiguous()) and bool((lg[:, 3] > 0).all())
     assert bool((res["pred"] == 3).all())
     _fused_check("tail tie 3 / 19", res, res["lab"])

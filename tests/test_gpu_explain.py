@@ -14,32 +14,19 @@ import sys
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import explain_restatement as E  # noqa: E402
 import overlap_restatement as OR  # noqa: E402
-from test_explain_cpu import CASES, class_planes, planes_of, weights_of  # noqa: E402
+from map_cases import EXPLAIN_CASES as CASES, class_planes, planes_of, weights_of  # noqa: E402
+from support import gpu_device, group_net  # noqa: E402
+from support import release_cached_blocks  # noqa: E402,F401  (a module-scoped autouse fixture, taken by importing its name)
 
 pytestmark = pytest.mark.gpu
 
 LABEL_TYPES = [torch.uint8, torch.int32, torch.int64]
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _release_cached_blocks():
-    yield
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-        torch.cuda.empty_cache()
 
 
 def _strided(planes, dev):
@@ -114,7 +101,7 @@ def _expect(name):
 def test_fixture_parity(name, dtype):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     c, e = CASES[name], _expect(name)
     lab = torch.from_numpy(c["labels"]).to(dtype).to(dev)
     act = _strided(e["planes"], dev)
@@ -143,7 +130,7 @@ def test_every_byte_is_written_and_none_besides(name):
     what the definition says (a surviving 0xA5 would have to be one)."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     c, e = CASES[name], _expect(name)
     lab = torch.from_numpy(c["labels"]).to(dev)
     act = torch.from_numpy(e["planes"]).to(dev)
@@ -213,7 +200,7 @@ def _big_case():
 def test_513_against_the_restatement_and_itself():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     b = _big_case()
     e = b["e"]
     act, lab = torch.from_numpy(b["planes"]).to(dev), torch.from_numpy(b["labels"]).to(dev)
@@ -230,16 +217,6 @@ def test_513_against_the_restatement_and_itself():
 
 
 # ---- the module ------------------------------------------------------------------------------------------------------------
-class _Backbone(nn.Module):
-    def __init__(self, ch):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return x
 
 
 @pytest.mark.parametrize("name", ["group_5x7_33x41", "group_3x3_17x19"])
@@ -248,12 +225,11 @@ def test_for_groups_on_a_real_module(name):
     (a negative weight flips the argmax of class 0), the list compute_group returns as input."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     c, e = CASES[name], _expect(name)
     K, G, S, Cs = 3, 3, 2, 16
     torch.manual_seed(3)
-    net = spx.PPNetMultiScaleGroup(_Backbone(Cs * S), 64, (12, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                                   patch_classification=True, num_scales=S, num_groups=G).to(dev).eval()
+    net = group_net(12, K, S, Cs, G, device=dev).eval()
     assert tuple(net.last_layer_group.weight.shape) == tuple(c["head"].shape)
     net.last_layer_group.weight.data.copy_(torch.from_numpy(c["head"]))
     ex = spx.ExplanationMaps.for_groups(net)
@@ -281,7 +257,7 @@ def test_for_prototypes_with_distances_and_no_synchronisation():
     nothing in them waits for the device."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     c = CASES["proto_5x7_33x41"]
 
     class Net:

@@ -10,7 +10,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from test_gpu_parity import _dev
+from support import gpu_device
 
 
 def _ref(A, B, flags=0, E=None):
@@ -52,7 +52,7 @@ SHAPES = [
 def test_rows_gemm_three_layouts(M, N, K):
     from scaleprotoseg_amd import functional as F_
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(M * 7 + N * 3 + K)
     a = torch.randn(M, K, generator=g)
     w = torch.randn(N, K, generator=g)
@@ -72,7 +72,7 @@ def test_rows_gemm_long_contraction_is_split_and_deterministic():
     from scaleprotoseg_amd import _lib
     from scaleprotoseg_amd import functional as F_
 
-    dev = _dev()
+    dev = gpu_device()
     M, n1, n2 = 40000, 182, 190
     assert _lib.load().spx_rows_gemm_workspace_bytes(n1, n2, M, 0) > 0           # few tiles, long k: slabs
     g = torch.Generator().manual_seed(3)
@@ -88,7 +88,7 @@ def test_wide_group_tail_forward_backward():
     """logits = exp(units) . W_g^T and its gradients (model_multiscale_group.py:303-308 through autograd)."""
     from scaleprotoseg_amd import functional as F_
 
-    dev = _dev()
+    dev = gpu_device()
     M, U, K2 = 333, 150, 50
     g = torch.Generator().manual_seed(4)
     units = torch.randn(M, U, generator=g)
@@ -112,7 +112,7 @@ def test_wide_group_tail_on_the_bf16x3_kernel():
     (flags 1 / 2 / 4 of spx_rows_gemm)."""
     from scaleprotoseg_amd import functional as F_
 
-    dev = _dev()
+    dev = gpu_device()
     M, U, K2 = 1024, 450, 256
     g = torch.Generator().manual_seed(5)
     units = torch.randn(M, U, generator=g)
@@ -135,7 +135,7 @@ def test_rows_gemm_rejects_bad_arguments():
     from scaleprotoseg_amd import SpxError
     from scaleprotoseg_amd import functional as F_
 
-    dev = _dev()
+    dev = gpu_device()
     a = torch.zeros(8, 8, device=dev)
     with pytest.raises(SpxError):
         F_._rows_gemm(a, (2, 2), a, (8, 1), 4, 4, 4)                # no unit stride

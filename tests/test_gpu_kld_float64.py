@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import kld_cases as KC
+from support import gpu_device
 
 pytestmark = pytest.mark.gpu
 
@@ -25,16 +26,10 @@ WALKS = ("grid", "linear")                                          # the reduct
 RUNS = [(n, w) for n in KC.CASE_NAMES for w in KC.case(n).walks]
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
 @functools.lru_cache(maxsize=None)
 def _reference(name):
     """The float64 reference of a case on the device: computed once, shared by the tests, never modified."""
-    return KC.reference(KC.case(name), torch.float64, _dev())
+    return KC.reference(KC.case(name), torch.float64, gpu_device())
 
 
 def _run(c, walk, dev):
@@ -53,7 +48,7 @@ def _run(c, walk, dev):
 @pytest.mark.parametrize("name,walk", RUNS)
 def test_loss_and_gradient_against_float64(name, walk):
     """KLDLoss through the kernels: value, gradient globally and per segment, exact zeros; the tall cases twice, bit-identical."""
-    dev = _dev()
+    dev = gpu_device()
     c = KC.case(name)
     ref = _reference(name)
     if c.tile_rows is not None:
@@ -85,7 +80,7 @@ def test_pair_sums_against_float64(name):
     """The three reduction passes' A[b][c][j][k], element by element, under both walks."""
     from scaleprotoseg_amd.loss import segment_pair_sums
 
-    dev = _dev()
+    dev = gpu_device()
     c = KC.case(name)
     ref = _reference(name)
     B, H, W = c.shape
@@ -108,7 +103,7 @@ def test_counts_and_lse_against_float64(name):
     from scaleprotoseg_amd import _lib
     from scaleprotoseg_amd.loss import _kld_segment_passes
 
-    dev = _dev()
+    dev = gpu_device()
     c = KC.case(name)
     ref = _reference(name)
     B, H, W = c.shape

@@ -5,31 +5,12 @@ built with torch from spx_upsample_argext's full-resolution maps."""
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
 from oracle import ppnet_oracle as O
+from support import gpu_device, group_net, Guarded, proto_net
+from support import release_cached_blocks  # noqa: F401  (a module-scoped autouse fixture, taken by importing its name)
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _release_cached_blocks():
-    """Hand the blocks these tests cached back to the device, so the modules that follow see the caching allocator in a
-    state that does not depend on these tests.  Known order dependence elsewhere in the suite:
-    test_gpu_parity.py::test_gathered_forward_writes_every_slot_of_uninitialised_planes passes ``_lib.ptr(x.to(dev))``
-    and ``_lib.ptr(labels.to(dev))`` as arguments of one call; the first temporary is freed before the kernel runs and
-    the second allocation can be carved from its block, overwriting the features.  Whether it is depends on the pool, so
-    that test fails in some suite orders and when run alone, with or without this module; this fixture does not fix it."""
-    yield
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-        torch.cuda.empty_cache()
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -114,6 +95,7 @@ def _check_against_reference(m, ref, K, S_total=None):
     return res
 
 
+# (local: labels with values beyond K from the caller's generator; parity_cases.gather_labels draws 0..K from a seed)
 def _labels(g, N, H, W, K):
     """Random labels with void (0), every class, and values > K (non-void, no class)."""
     return torch.randint(0, K + 4, (N, H, W), generator=g)
@@ -134,7 +116,7 @@ def _ident(g, P, K):
 def _run_restated(N, K, P, h, w, H, W, seed):
     from scaleprotoseg_amd import SegmentationMetrics
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(seed)
     logits = torch.randn(N, h, w, K, generator=g) * 3
     dist = torch.rand(N, P, h, w, generator=g) * 10
@@ -176,7 +158,7 @@ def _torch_counters(pred, near, ann, cls, K, P):
 def _run_against_argext(N, K, P, h, w, H, W, seed, diag_frac=0.0):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(seed)
     logits = (torch.randn(N, h, w, K, generator=g) * 3).to(dev)
     dist = (torch.rand(N, P, h, w, generator=g) * 10).to(dev)
@@ -209,31 +191,17 @@ def test_wide_heads_against_upsample_argext(case):
 
 
 # (4) layout and accumulation
-class _Backbone(nn.Module):
-    def __init__(self, ch):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return x
-
-
 def _net(kind, dev, P=40, K=10, S=4, Cs=64, G=6):
     import scaleprotoseg_amd as spx
 
     torch.manual_seed(5)
     if kind == "ppnet":
-        net = spx.PPNet(_Backbone(Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple", patch_classification=True)
+        net = proto_net(P, K, 1, Cs, cls=spx.PPNet)
         S = 1
     elif kind == "group":
-        net = spx.PPNetMultiScaleGroup(_Backbone(Cs * S), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                                       patch_classification=True, num_scales=S, num_groups=G)
+        net = group_net(P, K, S, Cs, G)
     else:
-        net = spx.PPNetMultiScale(_Backbone(Cs * S), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                                  patch_classification=True, num_scales=S)
+        net = proto_net(P, K, S, Cs)
     net = net.to(dev).eval()
     g = torch.Generator().manual_seed(9)
     conv = torch.randn(2, S * Cs, 17, 23, generator=g).to(dev)
@@ -245,7 +213,7 @@ def _net(kind, dev, P=40, K=10, S=4, Cs=64, G=6):
 def test_strided_logits_equal_contiguous():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     net, logits, dist = _net("ms", dev)
     N, h, w, K = logits.shape
     g = torch.Generator().manual_seed(1)
@@ -269,7 +237,7 @@ def test_strided_logits_equal_contiguous():
 def test_updates_accumulate_and_label_dtypes_agree():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(21)
     N, K, P, h, w, H, W = 6, 12, 36, 11, 13, 87, 101
     logits = torch.randn(N, h, w, K, generator=g).to(dev)
@@ -299,7 +267,7 @@ def test_updates_accumulate_and_label_dtypes_agree():
 def test_ties_resolve_to_the_lowest_index():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(4)
     N, K, P, h, w, H, W = 1, 6, 8, 7, 9, 30, 40
     logits = torch.full((N, h, w, K), 0.25)                       # constant planes: pred = 0 everywhere
@@ -327,7 +295,7 @@ def test_ties_resolve_to_the_lowest_index():
 def test_module_forward_to_compute(kind):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     net, logits, dist = _net(kind, dev)
     N, h, w, K = logits.shape
     H, W = 120, 150
@@ -352,7 +320,7 @@ def test_module_forward_to_compute(kind):
 def test_update_does_not_synchronise():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(13)
     N, K, P, h, w, H, W = 2, 9, 27, 10, 12, 80, 96
     logits = torch.randn(N, h, w, K, generator=g).to(dev)
@@ -387,27 +355,13 @@ def test_update_does_not_synchronise():
 
 
 # (8) nothing lands outside the counter buffers
-class _Guarded:
-    GUARD = 64 * 1024
-
-    def __init__(self, n_int64, dev):
-        self.n = int(n_int64) * 8
-        self.buf = torch.full((self.n + 2 * self.GUARD,), 0xA5, dtype=torch.uint8, device=dev)
-        self.body = self.buf[self.GUARD:self.GUARD + self.n].view(torch.int64)
-        self.body.zero_()
-
-    def intact(self):
-        g = self.GUARD
-        return bool((self.buf[:g] == 0xA5).all()) and bool((self.buf[g + self.n:] == 0xA5).all())
-
-
 @pytest.mark.parametrize("case", [(1, 3, 5, 3, 4, 5, 7), (2, 19, 37, 9, 13, 65, 67), (1, 150, 1800, 5, 6, 33, 45),
                                   (3, 182, 364, 7, 3, 19, 100), (1, 91, 91, 4, 4, 4, 4)])
 def test_no_write_outside_the_counters(case):
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.metrics import eval_accumulate, eval_topk
 
-    dev = _dev()
+    dev = gpu_device()
     N, K, P, h, w, H, W = case
     g = torch.Generator().manual_seed(sum(case))
     logits = torch.randn(N, h, w, K, generator=g).to(dev)
@@ -417,10 +371,11 @@ def test_no_write_outside_the_counters(case):
     smp = _samples(g, N, H, W).to(dev)
     ref = spx.SegmentationMetrics(K, ident, dev)
     ref.update(logits, ann, dist, smp)
-    conf, hits, topk, seen = (_Guarded(n, dev) for n in ((K + 1) * K, P, P, 1))
-    eval_accumulate(logits, ann, conf.body, dist, ref.proto_class, hits.body)
-    eval_topk(logits, dist, ref.proto_class, smp, (H, W), topk.body, seen.body)
+    guarded = [Guarded(8 * n, dev) for n in ((K + 1) * K, P, P, 1)]
+    conf, hits, topk, seen = (g.body(torch.int64).zero_() for g in guarded)          # zeroed int64 counters between the bands
+    eval_accumulate(logits, ann, conf, dist, ref.proto_class, hits)
+    eval_topk(logits, dist, ref.proto_class, smp, (H, W), topk, seen)
     torch.cuda.synchronize()
-    assert conf.intact() and hits.intact() and topk.intact() and seen.intact()
-    assert torch.equal(conf.body.view(K + 1, K), ref.conf) and torch.equal(hits.body, ref.hits)
-    assert torch.equal(topk.body, ref.topk) and torch.equal(seen.body, ref.samples_seen)
+    assert all(g.intact() for g in guarded)
+    assert torch.equal(conf.view(K + 1, K), ref.conf) and torch.equal(hits, ref.hits)
+    assert torch.equal(topk, ref.topk) and torch.equal(seen, ref.samples_seen)

@@ -13,86 +13,22 @@ import torch.nn as nn
 pytestmark = pytest.mark.gpu
 
 from oracle import ppnet_oracle as O
-
-GRAD_TOL = 1e-3          # gradients rel 1e-3 (max-normalised)
-BF16_DX_TOL = 4e-3     # dX returned in bf16 (bf16 features): ONE output rounding is half a bf16 ulp = 2^-8 of the element
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-class _RoundBf16(nn.Module):
-    """Test stand-in: makes the add-on output bf16-representable (SURVEY.md 8d 'identical inputs')."""
-
-    def forward(self, x):
-        return x.to(torch.bfloat16).to(torch.float32)
-
-
-class _Backbone(nn.Module):
-    """Stand-in for the DeepLab backbone (out of scope): ``str()`` starts with MSC and ``.base`` holds two Conv2d, which
-    is all model_multiscale.py:153-171 asks of it.  ``mode``: identity (features are fed directly), pool (image ->
-    features for the push tests) or list (MSC training output: a list of feature maps)."""
-
-    def __init__(self, ch, mode="identity", stride=4):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-        self.pool = nn.AvgPool2d(stride)
-        self.mode = mode
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        if self.mode == "identity":
-            return x
-        if self.mode == "list":
-            return [x, x[..., ::2, ::2].contiguous()]
-        return self.base(self.pool(x))
-
-
-def _close_fwd(got, ref, kind):
-    got, ref = got.detach().float().cpu(), torch.as_tensor(ref)
-    assert got.shape == ref.shape, f"{kind}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
-    err = (got - ref).abs()
-    if kind == "distances":
-        assert (err <= 1e-4 * (1 + ref)).all(), f"distance err {err.max().item()}"
-    elif kind == "activations":
-        assert (err <= 2e-4 * (1 + ref.abs())).all(), f"activation err {err.max().item()}"
-    else:
-        assert err.max().item() <= 1e-4 * max(1.0, ref.abs().max().item()), f"{kind} err {err.max().item()}"
-        if kind == "logits":    # per element: 1e-4 relative with an absolute floor (a logit is a signed sum through zero)
-            floor = 0.2 * max(1.0, ref.abs().max().item())
-            assert (err <= 1e-4 * (ref.abs() + floor)).all(), f"per-element logit err {(err / (ref.abs() + floor)).max().item()}"
-
-
-def _grad_close(got, ref, what, tol=GRAD_TOL):
-    got, ref = got.detach().float().cpu(), torch.as_tensor(ref).float()
-    assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
-    scale = ref.abs().max().item() + 1e-30
-    err = (got - ref).abs().max().item()
-    assert err <= tol * scale, f"{what}: err {err:.3e} vs scale {scale:.3e} (rel {err / scale:.2e})"
+from parity_cases import close_fwd
+from push_cases import push_problem
+from support import BF16_DX_TOL, gpu_device, grad_close, GRAD_TOL, group_net, proto_net
 
 
 def _proto_net(g, dev, cls=None, **kw):
-    import scaleprotoseg_amd as spx
-
+    """The module carrying a fixture's bank and, where it has one, head."""
     P, K = g["class_identity"].shape
-    Cs = g["prototype_vectors"].shape[1]
     S = int(g["num_scales"]) if "num_scales" in g.files else 1
-    cls = cls or spx.PPNetMultiScale
-    if cls is spx.PPNet:
-        net = cls(_Backbone(Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple", patch_classification=True, **kw)
-    else:
-        net = cls(_Backbone(Cs * S), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                  patch_classification=True, num_scales=S, **kw)
-    with torch.no_grad():
+
+    def init(net):
         net.prototype_vectors.copy_(torch.from_numpy(g["prototype_vectors"]))
         if "last_layer_weight" in g.files:
             net.last_layer.weight.copy_(torch.from_numpy(g["last_layer_weight"]))
-    return net.to(dev)
+
+    return proto_net(P, K, S, g["prototype_vectors"].shape[1], cls=cls, init=init, device=dev, **kw)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -101,7 +37,7 @@ def _proto_net(g, dev, cls=None, **kw):
 # ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["proto_ms_city", "proto_ms_small", "proto_s3", "proto_floor", "proto_s1_wide"])
 def test_module_forward_three_tuple_modes(golden, name):
-    dev = _dev()
+    dev = gpu_device()
     g = golden(name)
     net = _proto_net(g, dev)
     np.testing.assert_array_equal(net.prototype_class_identity.cpu().numpy(), g["class_identity"])
@@ -109,23 +45,23 @@ def test_module_forward_three_tuple_modes(golden, name):
 
     out = net.forward_from_conv_features(conv)                                  # default: (logits, distances)
     assert isinstance(out, tuple) and len(out) == 2
-    _close_fwd(out[0], g["logits"], "logits")
-    _close_fwd(out[1], g["default_1"], "distances")
+    close_fwd(out[0], g["logits"], "logits")
+    close_fwd(out[1], g["default_1"], "distances")
 
     out = net.forward_from_conv_features(conv, return_activations=True)         # (logits, activations)
     assert len(out) == 2
-    _close_fwd(out[0], g["logits"], "logits")
-    _close_fwd(out[1], g["act_1"], "activations")
+    close_fwd(out[0], g["logits"], "logits")
+    close_fwd(out[1], g["act_1"], "activations")
 
     out = net.forward_from_conv_features(conv, return_activations=True, return_distances=True)
     assert len(out) == 3
-    _close_fwd(out[0], g["logits"], "logits")
-    _close_fwd(out[1], g["distances"], "distances")
-    _close_fwd(out[2], g["activations"], "activations")
+    close_fwd(out[0], g["logits"], "logits")
+    close_fwd(out[1], g["distances"], "distances")
+    close_fwd(out[2], g["activations"], "activations")
 
     out = net.forward_from_conv_features(conv, return_distances=True)           # falls to the else branch (:382)
     assert len(out) == 2
-    _close_fwd(out[1], g["distances"], "distances")
+    close_fwd(out[1], g["distances"], "distances")
 
     # forward(x) = conv_features -> forward_from_conv_features (:332-338); the stand-in backbone is the identity and
     # the deeplab_simple add-on a Sigmoid (:206-208), so the values differ from the fixture here: shapes only
@@ -134,17 +70,17 @@ def test_module_forward_three_tuple_modes(golden, name):
 
     # stand-alone methods of the surface
     d = net._scale_l2_convolution(conv)
-    _close_fwd(d, g["distances"], "distances")
+    close_fwd(d, g["distances"], "distances")
     sim = net.distance_2_similarity(d)
     ref_act = torch.from_numpy(g["activations"])
     got = sim.permute(0, 2, 3, 1).reshape(ref_act.shape)
-    _close_fwd(got, ref_act, "activations")
-    _close_fwd(net.run_last_layer(torch.from_numpy(g["activations"]).to(dev)).reshape(g["logits"].shape), g["logits"], "logits")
+    close_fwd(got, ref_act, "activations")
+    close_fwd(net.run_last_layer(torch.from_numpy(g["activations"]).to(dev)).reshape(g["logits"].shape), g["logits"], "logits")
 
 
 def test_module_msc_list_recursion(golden):
     """MSC training inputs: conv_features is a LIST; the recursion drops the flags (model_multiscale.py:358-359)."""
-    dev = _dev()
+    dev = gpu_device()
     g = golden("proto_ms_small")
     net = _proto_net(g, dev)
     conv = torch.from_numpy(g["conv"]).to(dev)
@@ -152,36 +88,36 @@ def test_module_msc_list_recursion(golden):
     outs = net.forward_from_conv_features([conv, half], return_activations=True, return_distances=True)
     assert isinstance(outs, list) and len(outs) == 2
     assert all(isinstance(o, tuple) and len(o) == 2 for o in outs)        # flags dropped: (logits, distances)
-    _close_fwd(outs[0][0], g["logits"], "logits")
-    _close_fwd(outs[0][1], g["distances"], "distances")
+    close_fwd(outs[0][0], g["logits"], "logits")
+    close_fwd(outs[0][1], g["distances"], "distances")
     S = int(g["num_scales"])
     ranges = {s: tuple(int(v) for v in g["scale_ranges"][s]) for s in range(S)}
     rl, rd, _ = O.forward_from_conv_features(half.cpu(), torch.from_numpy(g["prototype_vectors"]), ranges, S,
                                              torch.from_numpy(g["last_layer_weight"]))
-    _close_fwd(outs[1][0], rl, "logits")
-    _close_fwd(outs[1][1], rd, "distances")
+    close_fwd(outs[1][0], rl, "logits")
+    close_fwd(outs[1][1], rd, "distances")
 
     # forward() over a list-valued backbone (:335-336) keeps the flags
     net.features.mode = "list"
     net.add_on_layers = nn.Sequential()             # features are fed as they are
     outs = net(conv, return_activations=True)
     assert isinstance(outs, list) and len(outs) == 2
-    _close_fwd(outs[0][1], g["act_1"], "activations")
+    close_fwd(outs[0][1], g["act_1"], "activations")
     pf = net.push_forward(conv)                     # :390-398, list form
     assert isinstance(pf, list) and torch.equal(pf[0][0], conv)
-    _close_fwd(pf[0][1], g["distances"], "distances")
+    close_fwd(pf[0][1], g["distances"], "distances")
     net.features.mode = "identity"
     c2, d2 = net.push_forward(conv)
     assert torch.equal(c2, conv)
-    _close_fwd(d2, g["distances"], "distances")
-    _close_fwd(net.prototype_distances(conv), g["distances"], "distances")
+    close_fwd(d2, g["distances"], "distances")
+    close_fwd(net.prototype_distances(conv), g["distances"], "distances")
 
 
 @pytest.mark.parametrize("name", ["proto_ms_city", "proto_ms_small", "proto_s1_wide"])
 def test_module_backward_matches_reference(golden, name):
     """loss = sum(logits r1) + sum(distances r2) + sum(activations r3) through the MODULE: parameter .grad of
     prototype_vectors and last_layer.weight and the feature gradient against the reference's autograd."""
-    dev = _dev()
+    dev = gpu_device()
     g = golden(name)
     net = _proto_net(g, dev)
     conv = torch.from_numpy(g["conv"]).to(dev).requires_grad_(True)
@@ -192,9 +128,9 @@ def test_module_backward_matches_reference(golden, name):
         + (act * torch.from_numpy(g["g_act"]).to(dev)).sum()
     )
     loss.backward()
-    _grad_close(conv.grad, g["d_conv"], "dX")
-    _grad_close(net.prototype_vectors.grad, g["d_prototypes"], "dPrototypes")
-    _grad_close(net.last_layer.weight.grad, g["d_last_layer"], "dLastLayer")
+    grad_close(conv.grad, g["d_conv"], "dX")
+    grad_close(net.prototype_vectors.grad, g["d_prototypes"], "dPrototypes")
+    grad_close(net.last_layer.weight.grad, g["d_last_layer"], "dLastLayer")
     assert net.ones.grad is None
 
 
@@ -202,19 +138,15 @@ def test_module_backward_matches_reference(golden, name):
 # (ii) PPNetMultiScale of the group phase (model_multiscale_group.py:283-308, :404-452)
 # ------------------------------------------------------------------------------------------------------------------
 def _group_net(g, dev):
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet   # the reference's class name
-
     P, K = g["class_identity"].shape
-    Cs = g["prototype_vectors"].shape[1]
-    S, G = int(g["num_scales"]), int(g["num_groups"])
-    net = GroupNet(_Backbone(Cs * S), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                   patch_classification=True, num_scales=S, num_groups=G)
-    with torch.no_grad():
+
+    def init(net):
         net.prototype_vectors.copy_(torch.from_numpy(g["prototype_vectors"]))
         for i, gp in enumerate(net.group_projection):
             gp.weight.copy_(torch.from_numpy(g[f"group_w_{i}"]))
         net.last_layer_group.weight.copy_(torch.from_numpy(g["last_layer_group_weight"]))
-    return net.to(dev)
+
+    return group_net(P, K, int(g["num_scales"]), g["prototype_vectors"].shape[1], int(g["num_groups"]), init=init, device=dev)
 
 
 def test_group_train_step_call_pattern_matches_reference(golden):
@@ -225,7 +157,7 @@ def test_group_train_step_call_pattern_matches_reference(golden):
     reaches the kernels' backward as part of dUnits."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = golden("group_train_step")
     net = _group_net(g, dev)
     K, G = g["class_identity"].shape[1], int(g["num_groups"])
@@ -242,9 +174,9 @@ def test_group_train_step_call_pattern_matches_reference(golden):
     assert abs(kld.item() - float(g["kld"])) <= 2e-4 * max(1.0, abs(float(g["kld"])))
     loss = ce + float(g["w_kld"]) * kld + (dist * torch.from_numpy(g["g_dist"]).to(dev)).sum()
     loss.backward()
-    _grad_close(conv.grad, g["d_conv"], "dX")
-    _grad_close(net.prototype_vectors.grad, g["d_prototypes"], "dPrototypes")
-    _grad_close(net.last_layer_group.weight.grad, g["d_last_layer_group"], "dLastLayerGroup")
+    grad_close(conv.grad, g["d_conv"], "dX")
+    grad_close(net.prototype_vectors.grad, g["d_prototypes"], "dPrototypes")
+    grad_close(net.last_layer_group.weight.grad, g["d_last_layer_group"], "dLastLayerGroup")
     scale = max(np.abs(g[f"d_group_w_{i}"]).max() for i in range(len(net.group_projection)))
     for i, gp in enumerate(net.group_projection):
         err = (gp.weight.grad.cpu() - torch.from_numpy(g[f"d_group_w_{i}"])).abs().max().item()
@@ -255,7 +187,7 @@ def test_group_train_step_call_pattern_matches_reference(golden):
 
 
 def test_group_module_forward_backward_matches_reference(golden):
-    dev = _dev()
+    dev = gpu_device()
     g = golden("group_ms_small")
     net = _group_net(g, dev)
     np.testing.assert_array_equal(net.group_class_identity.cpu().numpy(), g["group_class_identity"])
@@ -263,23 +195,23 @@ def test_group_module_forward_backward_matches_reference(golden):
 
     out = net.forward_from_conv_features(conv)
     assert len(out) == 2
-    _close_fwd(out[0], g["logits"], "logits")
-    _close_fwd(out[1], g["distances"], "distances")
+    close_fwd(out[0], g["logits"], "logits")
+    close_fwd(out[1], g["distances"], "distances")
     out = net.forward_from_conv_features(conv, return_activations=True)
     assert len(out) == 2
-    _close_fwd(out[1], g["activations"], "activations")
+    close_fwd(out[1], g["activations"], "activations")
 
     logits, dist, act = net.forward_from_conv_features(conv, return_activations=True, return_distances=True)
-    _close_fwd(logits, g["logits"], "logits")
-    _close_fwd(dist, g["distances"], "distances")
-    _close_fwd(act, g["activations"], "activations")
+    close_fwd(logits, g["logits"], "logits")
+    close_fwd(dist, g["distances"], "distances")
+    close_fwd(act, g["activations"], "activations")
     # compute_group returns a LIST of per-class [M, G] tensors (consumed by KLDLossGroup); run_last_layer on top
     groups = net.compute_group(act.detach())
     assert isinstance(groups, list) and len(groups) == len(net.group_projection)
     cat = torch.cat(groups, dim=-1)
     ref_cat = torch.from_numpy(g["group_cat"])
     assert ((cat.cpu() - ref_cat).abs() <= 2e-4 * (1 + ref_cat.abs())).all()
-    _close_fwd(net.run_last_layer(act.detach()).reshape(g["logits"].shape), g["logits"], "logits")
+    close_fwd(net.run_last_layer(act.detach()).reshape(g["logits"].shape), g["logits"], "logits")
 
     loss = (
         (logits * torch.from_numpy(g["g_logits"]).to(dev)).sum()
@@ -287,9 +219,9 @@ def test_group_module_forward_backward_matches_reference(golden):
         + (act * torch.from_numpy(g["g_act"]).to(dev)).sum()
     )
     loss.backward()
-    _grad_close(conv.grad, g["d_conv"], "dX")
-    _grad_close(net.prototype_vectors.grad, g["d_prototypes"], "dPrototypes")
-    _grad_close(net.last_layer_group.weight.grad, g["d_last_layer_group"], "dLastLayerGroup")
+    grad_close(conv.grad, g["d_conv"], "dX")
+    grad_close(net.prototype_vectors.grad, g["d_prototypes"], "dPrototypes")
+    grad_close(net.last_layer_group.weight.grad, g["d_last_layer_group"], "dLastLayerGroup")
     scale = max(np.abs(g[f"d_group_w_{i}"]).max() for i in range(len(net.group_projection)))
     for i, gp in enumerate(net.group_projection):
         assert gp.weight.grad is not None and gp.weight.grad.shape == gp.weight.shape
@@ -303,22 +235,22 @@ def test_group_module_forward_backward_matches_reference(golden):
 def test_ppnet_single_scale_matches_reference(golden):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = golden("ppnet_single")
     net = _proto_net(g, dev, cls=spx.PPNet)
     conv = torch.from_numpy(g["conv"]).to(dev)
     logits, dist = net.forward_from_conv_features(conv)
-    _close_fwd(logits, g["logits"], "logits")
-    _close_fwd(dist, g["distances"], "distances")
+    close_fwd(logits, g["logits"], "logits")
+    close_fwd(dist, g["distances"], "distances")
     logits, act = net.forward_from_conv_features(conv, return_activations=True, return_distances=True)   # model.py:357-360
-    _close_fwd(logits, g["logits"], "logits")
-    _close_fwd(act, g["activations"], "activations")
-    _close_fwd(net._l2_convolution(conv), g["distances"], "distances")
+    close_fwd(logits, g["logits"], "logits")
+    close_fwd(act, g["activations"], "activations")
+    close_fwd(net._l2_convolution(conv), g["distances"], "distances")
     net.add_on_layers = nn.Sequential()              # the fixture's conv is the add-on OUTPUT: feed it as it is
     lg, ds, cv = net.forward_with_features(conv)     # model.py:317-326
     assert torch.equal(cv, conv)
-    _close_fwd(ds, g["distances"], "distances")
-    _close_fwd(lg, g["logits"], "logits")
+    close_fwd(ds, g["distances"], "distances")
+    close_fwd(lg, g["logits"], "logits")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -329,7 +261,7 @@ def test_ppnet_single_scale_matches_reference(golden):
 def test_linear_activation_forward_backward(shape, x_dtype):
     from scaleprotoseg_amd.functional import BankLayout, proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = shape
     gen = torch.Generator().manual_seed(20220227 + 11)
     conv = O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=gen)))
@@ -351,26 +283,26 @@ def test_linear_activation_forward_backward(shape, x_dtype):
     wg = Wl.to(dev).requires_grad_(True)
     lay = BankLayout(P, K, S, Cs, tuple(ranges[s] for s in range(S)))
     logits, dist, act = proto_head_forward(x, pvg, wg, lay, want_distances=True, want_activations=True, activation="linear")
-    _close_fwd(dist, rd.detach(), "distances")
-    _close_fwd(act, ra.detach(), "activations")
-    _close_fwd(logits.reshape(rl.shape), rl.detach(), "logits")
+    close_fwd(dist, rd.detach(), "distances")
+    close_fwd(act, ra.detach(), "activations")
+    close_fwd(logits.reshape(rl.shape), rl.detach(), "logits")
     ((logits * g_logits.reshape(-1, K).to(dev)).sum() + (dist * g_dist.to(dev)).sum() + (act * g_act.to(dev)).sum()).backward()
-    _grad_close(x.grad, c.grad, "dX", tol=GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL)
-    _grad_close(pvg.grad, pv.grad, "dPrototypes")
-    _grad_close(wg.grad, w.grad, "dLastLayer")
+    grad_close(x.grad, c.grad, "dX", tol=GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL)
+    grad_close(pvg.grad, pv.grad, "dPrototypes")
+    grad_close(wg.grad, w.grad, "dLastLayer")
 
 
 def test_linear_activation_through_the_module(golden):
-    dev = _dev()
+    dev = gpu_device()
     g = golden("proto_ms_small")
     net = _proto_net(g, dev, prototype_activation_function="linear")
     conv = torch.from_numpy(g["conv"]).to(dev)
     logits, dist, act = net.forward_from_conv_features(conv, return_activations=True, return_distances=True)
-    _close_fwd(dist, g["distances"], "distances")
+    close_fwd(dist, g["distances"], "distances")
     ref_act = -torch.from_numpy(g["distances"]).permute(0, 2, 3, 1).reshape(act.shape)
-    _close_fwd(act, ref_act, "activations")
-    _close_fwd(logits.reshape(-1, logits.shape[-1]), ref_act @ torch.from_numpy(g["last_layer_weight"]).t(), "logits")
-    _close_fwd(net.distance_2_similarity(dist), -torch.from_numpy(g["distances"]), "activations")
+    close_fwd(act, ref_act, "activations")
+    close_fwd(logits.reshape(-1, logits.shape[-1]), ref_act @ torch.from_numpy(g["last_layer_weight"]).t(), "logits")
+    close_fwd(net.distance_2_similarity(dist), -torch.from_numpy(g["distances"]), "activations")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -388,7 +320,7 @@ def test_linear_activation_through_the_module(golden):
 def test_em_and_ade_literal_configs(shape, x_dtype):
     from scaleprotoseg_amd.functional import BankLayout, proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = shape
     gen = torch.Generator().manual_seed(20220227 + 17)
     conv = O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=gen)))
@@ -404,53 +336,17 @@ def test_em_and_ade_literal_configs(shape, x_dtype):
     w = Wl.to(dev).requires_grad_(True)
     lay = BankLayout(P, K, S, Cs, tuple(ranges[s] for s in range(S)))
     logits, dist, _ = proto_head_forward(x, pv, w, lay, want_distances=True)
-    _close_fwd(dist, rd, "distances")
-    _close_fwd(logits.reshape(rl.shape), rl, "logits")
+    close_fwd(dist, rd, "distances")
+    close_fwd(logits.reshape(rl.shape), rl, "logits")
     torch.autograd.backward([logits, dist], [g_logits.reshape(-1, K).to(dev), g_dist.to(dev)])
-    _grad_close(x.grad, dx_ref, "dX", tol=GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL)
-    _grad_close(pv.grad, dp_ref, "dPrototypes")
-    _grad_close(w.grad, dw_ref, "dLastLayer")
+    grad_close(x.grad, dx_ref, "dX", tol=GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL)
+    grad_close(pv.grad, dp_ref, "dPrototypes")
+    grad_close(w.grad, dw_ref, "dLastLayer")
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # (iv) the push, end to end through the module (push_multiscale_optimization.py:34-190, :323-335)
 # ------------------------------------------------------------------------------------------------------------------
-class _PushDataset:
-    """len / [i] -> (image [3,h,w] float, target [h,w] int with 0 = void, 1..K); see scaleprotoseg_amd/push.py."""
-
-    convert_targets = None
-
-    def __init__(self, n, h, w, K, absent, seed):
-        gen = torch.Generator().manual_seed(seed)
-        self.items = []
-        for i in range(n):
-            img = torch.randn(3, h, w, generator=gen)
-            t = torch.randint(0, K + 1, (h // 8, w // 8), generator=gen).repeat_interleave(8, 0).repeat_interleave(8, 1)
-            t[t == absent + 1] = 0                          # class `absent` never appears anywhere
-            self.items.append((img, t.numpy().astype(np.int64)))
-
-    def __len__(self):
-        return len(self.items)
-
-    def __getitem__(self, i):
-        return self.items[i]
-
-
-def _push_problem(dev, S=4, Cs=16, K=5, per=2, n_img=6, seed=3):
-    import scaleprotoseg_amd as spx
-
-    P = S * K * per
-    torch.manual_seed(seed)
-    net = spx.PPNetMultiScale(_Backbone(S * Cs, mode="pool", stride=4), 64, (P, Cs, 1, 1), [], K,
-                              add_on_layers_type="deeplab_simple", patch_classification=True, num_scales=S)
-    net.add_on_layers = nn.Sequential(nn.Sigmoid(), _RoundBf16())
-    with torch.no_grad():
-        net.prototype_vectors.copy_(O.bf16_representable(net.prototype_vectors.data))
-        # a forced duplicate: prototypes 0 and 1 (same class, same scale) start equal -> same winning pixel
-        net.prototype_vectors[1].copy_(net.prototype_vectors[0])
-    net = net.to(dev)
-    data = _PushDataset(n_img, 40, 56, K, absent=3, seed=seed + 1)
-    return net, data, P
 
 
 def _oracle_push(net, data, P, S, K):
@@ -481,9 +377,9 @@ def test_push_stages_match_oracle():
     """compute_distances / min_across_dataset / global_min, one by one."""
     from scaleprotoseg_amd import push as push_mod
 
-    dev = _dev()
+    dev = gpu_device()
     S, K = 4, 5
-    net, data, P = _push_problem(dev, S=S, K=K)
+    net, data, P = push_problem(dev, S=S, K=K)
     ref = _oracle_push(net, data, P, S, K)
     img, tgt = data[2]
     idx, val = push_mod.compute_distances(net, data, img, tgt, K, void_class=0)
@@ -508,9 +404,9 @@ def test_compute_distances_takes_the_fused_minimum_and_falls_back_when_it_must()
     whenever the class identity is one-hot, and reduces the written map otherwise - with the same result either way."""
     from scaleprotoseg_amd import push as push_mod
 
-    dev = _dev()
+    dev = gpu_device()
     S, K = 4, 5
-    net, data, P = _push_problem(dev, S=S, K=K)
+    net, data, P = push_problem(dev, S=S, K=K)
     img, tgt = data[1]
     calls = []
     orig = net.push_min_distances
@@ -546,9 +442,9 @@ def test_compute_distances_takes_the_fused_minimum_and_falls_back_when_it_must()
 def test_push_prototypes_multiscale_end_to_end(tmp_path):
     from scaleprotoseg_amd.push import push_prototypes_multiscale
 
-    dev = _dev()
+    dev = gpu_device()
     S, K = 4, 5
-    net, data, P = _push_problem(dev, S=S, K=K)
+    net, data, P = push_problem(dev, S=S, K=K)
     ref = _oracle_push(net, data, P, S, K)
     assert 1 in ref["dups"], "the forced duplicate must be dropped"
     w_before = net.last_layer.weight.detach().clone()
@@ -568,8 +464,8 @@ def test_push_prototypes_multiscale_end_to_end(tmp_path):
     logits, dist = net.forward_from_conv_features(conv)
     rl, rd, _ = O.forward_from_conv_features(ref["convs"][0], net.prototype_vectors.detach().cpu(), ref["ranges"], S,
                                              net.last_layer.weight.detach().cpu())
-    _close_fwd(dist, rd, "distances")
-    _close_fwd(logits, rl, "logits")
+    close_fwd(dist, rd, "distances")
+    close_fwd(logits, rl, "logits")
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -578,16 +474,13 @@ def test_push_prototypes_multiscale_end_to_end(tmp_path):
 # through the fp32 MFMA product kernels on the activations (functional.wide_linear / wide_group_tail, csrc/spx_gemm.hip)
 # ------------------------------------------------------------------------------------------------------------------
 def test_ade_group_phase_wide_head_forward_backward():
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet
-
-    dev = _dev()
+    dev = gpu_device()
     S, Cs, K, G, P, B, H, W = 4, 64, 150, 3, 1800, 1, 9, 8
     gen = torch.Generator().manual_seed(20220227 + 23)
     conv = O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=gen)))
     bank = O.bf16_representable(torch.rand(P, Cs, 1, 1, generator=gen))
     torch.manual_seed(5)
-    net = GroupNet(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                   patch_classification=True, num_scales=S, num_groups=G)
+    net = group_net(P, K, S, Cs, G)
     assert net.last_layer_group.weight.shape == (K, G * K) and len(net.group_projection) == K
     with torch.no_grad():
         net.prototype_vectors.copy_(bank)
@@ -607,29 +500,26 @@ def test_ade_group_phase_wide_head_forward_backward():
 
     x = conv.to(dev).requires_grad_(True)
     logits, dist = net.forward_from_conv_features(x)
-    _close_fwd(dist, rd.detach(), "distances")
-    _close_fwd(logits, rl.detach(), "logits")
+    close_fwd(dist, rd.detach(), "distances")
+    close_fwd(logits, rl.detach(), "logits")
     ((logits * g_logits.to(dev)).sum() + (dist * g_dist.to(dev)).sum()).backward()
-    _grad_close(x.grad, c0.grad, "dX")
-    _grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
-    _grad_close(net.last_layer_group.weight.grad, wg.grad, "dLastLayerGroup")
+    grad_close(x.grad, c0.grad, "dX")
+    grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
+    grad_close(net.last_layer_group.weight.grad, wg.grad, "dLastLayerGroup")
     scale = max(w.grad.abs().max().item() for w in gw)
     for i, gp in enumerate(net.group_projection):
         err = (gp.weight.grad.cpu() - gw[i].grad).abs().max().item()
         assert err <= GRAD_TOL * scale, f"d group_projection[{i}]: {err:.3e} vs {scale:.3e}"
     out = net.forward_from_conv_features(x.detach(), return_activations=True, return_distances=True)
     assert len(out) == 3
-    _close_fwd(out[2], ra.detach(), "activations")
+    close_fwd(out[2], ra.detach(), "activations")
 
 
 @pytest.mark.parametrize("K,G", [(182, None), (50, 3)])
 def test_wide_class_heads(K, G):
     """182 classes (scaleproto_coco.gin) on the prototype-phase module; 50 classes x 3 groups = 150 units with a 50-class
     tail (unit product in the kernel, tail in the fp32 MFMA product kernel) on the group-phase module."""
-    import scaleprotoseg_amd as spx
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet
-
-    dev = _dev()
+    dev = gpu_device()
     S, Cs, B, H, W = 4, 16, 2, 7, 9
     P = S * K * 1
     gen = torch.Generator().manual_seed(20220227 + 29)
@@ -637,11 +527,9 @@ def test_wide_class_heads(K, G):
     bank = O.bf16_representable(torch.rand(P, Cs, 1, 1, generator=gen))
     torch.manual_seed(6)
     if G is None:
-        net = spx.PPNetMultiScale(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                                  patch_classification=True, num_scales=S)
+        net = proto_net(P, K, S, Cs)
     else:
-        net = GroupNet(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                       patch_classification=True, num_scales=S, num_groups=G)
+        net = group_net(P, K, S, Cs, G)
     with torch.no_grad():
         net.prototype_vectors.copy_(bank)
     net = net.to(dev)
@@ -660,20 +548,20 @@ def test_wide_class_heads(K, G):
     (rl * g_logits).sum().backward()
     x = conv.to(dev).requires_grad_(True)
     logits, dist = net.forward_from_conv_features(x)
-    _close_fwd(dist, rd.detach(), "distances")
-    _close_fwd(logits, rl.detach(), "logits")
+    close_fwd(dist, rd.detach(), "distances")
+    close_fwd(logits, rl.detach(), "logits")
     (logits * g_logits.to(dev)).sum().backward()
-    _grad_close(x.grad, c0.grad, "dX")
-    _grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
+    grad_close(x.grad, c0.grad, "dX")
+    grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
     head = net.last_layer.weight if G is None else net.last_layer_group.weight
-    _grad_close(head.grad, w0.grad, "dHead")
+    grad_close(head.grad, w0.grad, "dHead")
 
 
 def test_user_supplied_similarity_function(golden):
     """A callable ``prototype_activation_function`` (segmentation/model/model_multiscale.py:329-330): the reference calls it
     on the [B, P, H, W] distance map and feeds the result to ``last_layer``.  Here: the distance kernel, the user's torch
     code, the fp32 MFMA product kernel - forward and backward against the same op sequence on the CPU."""
-    dev = _dev()
+    dev = gpu_device()
     g = golden("proto_ms_small")
 
     def similarity(d):
@@ -697,13 +585,13 @@ def test_user_supplied_similarity_function(golden):
 
     x = conv.to(dev).requires_grad_(True)
     logits, dist, act = net.forward_from_conv_features(x, return_activations=True, return_distances=True)
-    _close_fwd(dist, rd.detach(), "distances")
-    _close_fwd(act, ra.detach(), "activations")
-    _close_fwd(logits, rl.detach(), "logits")
+    close_fwd(dist, rd.detach(), "distances")
+    close_fwd(act, ra.detach(), "activations")
+    close_fwd(logits, rl.detach(), "logits")
     ((logits * g_logits.to(dev)).sum() + (dist * g_dist.to(dev)).sum()).backward()
-    _grad_close(x.grad, c0.grad, "dX")
-    _grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
-    _grad_close(net.last_layer.weight.grad, w0.grad, "dLastLayer")
+    grad_close(x.grad, c0.grad, "dX")
+    grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
+    grad_close(net.last_layer.weight.grad, w0.grad, "dLastLayer")
     assert len(net.forward_from_conv_features(x.detach())) == 2
 
 
@@ -714,7 +602,7 @@ def test_user_supplied_similarity_function(golden):
 def test_cross_entropy_kernels_match_reference_golden(golden):
     from scaleprotoseg_amd.loss import PixelWiseCrossEntropyLoss
 
-    dev = _dev()
+    dev = gpu_device()
     g = golden("kld_loss")
     lg = torch.from_numpy(g["ce_logits"]).to(dev).requires_grad_(True)
     tgt = torch.from_numpy(g["ce_target"]).to(dev)
@@ -747,16 +635,14 @@ def test_cross_entropy_kernels_match_reference_golden(golden):
                                                               # (strided logits path) in the forward's stores and the prologue only
 ])
 def test_fused_cross_entropy_through_the_module(shape, x_dtype, gather):
-    import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.loss import ClassDistances, KLDLoss, PixelWiseCrossEntropyLoss
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = shape
     gen = torch.Generator().manual_seed(20220227 + 41)
     conv = O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=gen)))
     bank = O.bf16_representable(torch.rand(P, Cs, 1, 1, generator=gen))
-    net = spx.PPNetMultiScale(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S)
+    net = proto_net(P, K, S, Cs)
     with torch.no_grad():
         net.prototype_vectors.copy_(bank)
         net.last_layer.weight.add_(0.05 * torch.randn(K, P, generator=gen))
@@ -787,7 +673,7 @@ def test_fused_cross_entropy_through_the_module(shape, x_dtype, gather):
     else:
         logits, dist = net.forward_from_conv_features(x, ce_target=tgt)
     assert hasattr(logits, "spx_ce")
-    _close_fwd(logits, rl.detach(), "logits")
+    close_fwd(logits, rl.detach(), "logits")
     ce, correct = PixelWiseCrossEntropyLoss(ignore_index=-1, return_correct=True)(logits, tgt)
     assert ce is logits.spx_ce.loss                                    # the epilogue's value, no second pass
     assert abs(ce.item() - ref_ce.item()) <= 1e-4 * max(1.0, abs(ref_ce.item()))
@@ -798,21 +684,18 @@ def test_fused_cross_entropy_through_the_module(shape, x_dtype, gather):
     else:
         loss = 0.7 * ce + (dist * g_dist.to(dev)).sum()
     loss.backward()
-    _grad_close(x.grad, c0.grad, "dX", tol=GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL)
-    _grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
-    _grad_close(net.last_layer.weight.grad, w0.grad, "dLastLayer")
+    grad_close(x.grad, c0.grad, "dX", tol=GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL)
+    grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
+    grad_close(net.last_layer.weight.grad, w0.grad, "dLastLayer")
 
 
 def test_fused_cross_entropy_with_a_second_use_of_the_logits():
     """The logits feed the fused cross entropy AND another term: both gradients reach d_logits."""
-    import scaleprotoseg_amd as spx
-
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = 1, 4, 16, 40, 5, 9, 11
     gen = torch.Generator().manual_seed(3)
     conv = O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=gen)))
-    net = spx.PPNetMultiScale(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S)
+    net = proto_net(P, K, S, Cs)
     with torch.no_grad():
         net.prototype_vectors.copy_(O.bf16_representable(net.prototype_vectors.data))
     bank = net.prototype_vectors.detach().clone()
@@ -828,23 +711,21 @@ def test_fused_cross_entropy_with_a_second_use_of_the_logits():
     x = conv.to(dev).requires_grad_(True)
     logits, _ = net.forward_from_conv_features(x, ce_target=target.to(dev))
     (logits.spx_ce.loss + (logits * r.to(dev)).sum()).backward()
-    _grad_close(x.grad, c0.grad, "dX")
-    _grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
-    _grad_close(net.last_layer.weight.grad, w0.grad, "dLastLayer")
+    grad_close(x.grad, c0.grad, "dX")
+    grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
+    grad_close(net.last_layer.weight.grad, w0.grad, "dLastLayer")
 
 
 def test_fused_cross_entropy_is_dropped_when_the_labels_change():
     """The attachment is only valid for the label tensor it was computed from, AS IT WAS: another tensor or an in-place
     edit (version counter) sends the loss through the stand-alone kernels on the current labels."""
-    import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.loss import PixelWiseCrossEntropyLoss
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = 1, 2, 16, 20, 5, 6, 7
     gen = torch.Generator().manual_seed(9)
     conv = O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=gen))).to(dev)
-    net = spx.PPNetMultiScale(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S).to(dev)
+    net = proto_net(P, K, S, Cs, device=dev)
     tgt = torch.randint(1, K + 1, (B, H, W), generator=gen).to(dev)
     crit = PixelWiseCrossEntropyLoss(ignore_index=-1)
     with torch.no_grad():
@@ -865,15 +746,13 @@ def test_group_module_fused_cross_entropy(golden, B, H, W):
     """Group phase: ce_target through the module (tail kernel: summed units -> exp -> W_g -> logits -> CE statistics),
     forward value, `correct`, and the gradients of CE + a distance term against the oracle's autograd."""
     from scaleprotoseg_amd.loss import PixelWiseCrossEntropyLoss
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet
 
-    dev = _dev()
+    dev = gpu_device()
     S, Cs, K, G, P = 4, 16, 5, 3, 40
     gen = torch.Generator().manual_seed(20220227 + 53)
     conv = O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=gen)))
     torch.manual_seed(9)
-    net = GroupNet(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                   patch_classification=True, num_scales=S, num_groups=G)
+    net = group_net(P, K, S, Cs, G)
     with torch.no_grad():
         net.prototype_vectors.copy_(O.bf16_representable(net.prototype_vectors.data))
         net.last_layer_group.weight.add_(0.05 * torch.randn(K, G * K, generator=gen))
@@ -894,15 +773,15 @@ def test_group_module_fused_cross_entropy(golden, B, H, W):
     x = conv.to(dev).requires_grad_(True)
     tgt = target.to(dev)
     logits, dist = net.forward_from_conv_features(x, ce_target=tgt)
-    _close_fwd(logits, rl.detach(), "logits")
-    _close_fwd(dist, rd.detach(), "distances")
+    close_fwd(logits, rl.detach(), "logits")
+    close_fwd(dist, rd.detach(), "distances")
     ce, correct = PixelWiseCrossEntropyLoss(ignore_index=-1, return_correct=True)(logits, tgt)
     assert ce is logits.spx_ce.loss
     assert abs(ce.item() - ref_ce.item()) <= 1e-4 * max(1.0, abs(ref_ce.item()))
     (ce + (dist * g_dist.to(dev)).sum()).backward()
-    _grad_close(x.grad, c0.grad, "dX")
-    _grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
-    _grad_close(net.last_layer_group.weight.grad, wg.grad, "dLastLayerGroup")
+    grad_close(x.grad, c0.grad, "dX")
+    grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes")
+    grad_close(net.last_layer_group.weight.grad, wg.grad, "dLastLayerGroup")
     scale = max(w.grad.abs().max().item() for w in gw)
     for i, gp in enumerate(net.group_projection):
         err = (gp.weight.grad.cpu() - gw[i].grad).abs().max().item()
@@ -913,17 +792,15 @@ def test_fused_cross_entropy_leaves_no_graph_alive():
     """The step's autograd graph must die with the step (an operator that kept an output on its ctx would form a
     node -> ctx -> tensor -> node cycle: a memory leak, and a stale graph that capture_step rightly refuses)."""
     import gc
-    import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.graphs import capture_step
     from scaleprotoseg_amd.loss import PixelWiseCrossEntropyLoss
 
-    dev = _dev()
+    dev = gpu_device()
     gc.collect()
     gc.disable()                                        # the claim is about reference counts, not about the collector
     try:
         B, S, Cs, P, K, H, W = 2, 4, 16, 40, 5, 9, 11
-        net = spx.PPNetMultiScale(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                                  patch_classification=True, num_scales=S).to(dev)
+        net = proto_net(P, K, S, Cs, device=dev)
         net.add_on_layers = nn.Sequential()
         x = torch.rand(B, S * Cs, H, W, device=dev).requires_grad_(True)
         tgt = torch.randint(0, K + 1, (B, H, W), device=dev)
@@ -950,15 +827,13 @@ def test_group_step_leaves_no_graph_alive():
     backward through save_for_backward, not as a ctx attribute (round 4: that cycle made capture_step refuse the step)."""
     import gc
     from scaleprotoseg_amd.graphs import capture_step
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet
 
-    dev = _dev()
+    dev = gpu_device()
     gc.collect()
     gc.disable()
     try:
         B, S, Cs, P, K, H, W = 2, 4, 16, 40, 5, 9, 11
-        net = GroupNet(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                       patch_classification=True, num_scales=S, num_groups=3).to(dev)
+        net = group_net(P, K, S, Cs, 3, device=dev)
         net.add_on_layers = nn.Sequential()
         x = torch.rand(B, S * Cs, H, W, device=dev).requires_grad_(True)
         gl = torch.randn(B, H, W, K, device=dev) * 1e-3
@@ -986,12 +861,9 @@ def test_group_dense_matrix_kernel_matches_index_put(P, K, G, drop):
     """spx_group_dense / spx_group_dense_bwd (the dense [U, P] form of the per-class group projections in one launch each,
     model_multiscale_group.py:249-269) against torch's zeros + cat + index_put and its autograd; classes in ``drop`` own no
     prototype (pruned away): their columns / rows do not exist."""
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet
-
     dev = torch.device("cuda:0")
     torch.manual_seed(P + K)
-    net = GroupNet(_Backbone(64), 64, (P, 16, 1, 1), [], K, add_on_layers_type="deeplab_simple", patch_classification=True,
-                   num_scales=4, num_groups=G).to(dev)
+    net = group_net(P, K, 4, 16, G, device=dev)
     if drop:
         keep = [p for p in range(P) if int(net.prototype_class_identity[p].argmax()) not in drop]
         net.prune_prototypes([p for p in range(P) if p not in keep])

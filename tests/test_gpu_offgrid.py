@@ -2,10 +2,10 @@
 one optimizer step or one push hand the kernels), and bf16 features with an unrounded bank (autocast).
 
 The contract (DESIGN.md 4 "operand sites", restated in float64 by tests/offgrid_restatement.py), with x~ = bf16_rne(x), p~ = bf16_rne(p):
-  forward    every output equals the oracle at (x~, p~), within the on-grid tolerances of test_gpu_parity._assert_fwd
+  forward    every output equals the oracle at (x~, p~), within the on-grid tolerances of parity_cases.assert_fwd
   backward   dX and dPrototypes equal the per-site restatement (G at (x~, p~); 2 rs x with the caller's x, P^T G with p~, G^T X with
              x~, p colsum(G) with the fp32 p), head / grouping gradients float64 autograd at (x~, p~); GRAD_TOL / BF16_DX_TOL under
-             _grad_close's max-normalised measure
+             grad_close's max-normalised measure
 tests/test_offgrid_cpu.py shows on the CPU that the references this file tells apart lie further apart than these tolerances.
 Every check prints its worst error / tolerance ratio before asserting (profiles/offgrid_summary.md records them)."""
 import functools
@@ -22,7 +22,8 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import offgrid_restatement as R  # noqa: E402
 from oracle import ppnet_oracle as O  # noqa: E402
-from test_gpu_parity import GRAD_TOL, PUSH_FUSED_SHAPES, _assert_fwd, _dx_tol, _grad_close, _labels, _layout  # noqa: E402
+from parity_cases import PUSH_FUSED_SHAPES, assert_fwd, bank_layout, dx_tolerance, gather_labels  # noqa: E402
+from support import gpu_device, grad_close, GRAD_TOL, ListData, proto_net  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -34,12 +35,7 @@ def _id(v):
     return v if isinstance(v, str) else str(v).replace("torch.", "")
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
+# (local: an off-grid case of offgrid_restatement with its oracle forward; parity_cases.problem draws on-grid inputs)
 @functools.lru_cache(maxsize=None)
 def _problem(case, x_dtype, signed=False):
     """(inputs, fp32 oracle forward at (x~, p~)): computed once, shared, never written to."""
@@ -57,7 +53,7 @@ def _report(tag, **ratios):
 
 
 def forward_ratios(logits, dist, act, ref_logits, ref_dist, ref_act):
-    """Worst error / tolerance of each bound in _assert_fwd."""
+    """Worst error / tolerance of each bound in assert_fwd."""
     out = {}
     if dist is not None:
         out["dist"] = R.distance_ratio(dist.detach().cpu(), ref_dist)
@@ -76,7 +72,7 @@ def run_forward(pb, dev, **kw):
     from scaleprotoseg_amd.functional import proto_head_forward
 
     B, S, Cs, P, K, H, W = pb.shape
-    out = proto_head_forward(pb.conv.to(dev, pb.x_dtype), pb.bank.to(dev), pb.Wl.to(dev), _layout(P, K, S, Cs, pb.ranges),
+    out = proto_head_forward(pb.conv.to(dev, pb.x_dtype), pb.bank.to(dev), pb.Wl.to(dev), bank_layout(P, K, S, Cs, pb.ranges),
                              want_distances=True, want_activations=True, **kw)
     torch.cuda.synchronize()
     return out
@@ -90,7 +86,7 @@ def run_backward(pb, dev):
     x = pb.conv.to(dev, pb.x_dtype).requires_grad_(True)
     pv = pb.bank.to(dev).requires_grad_(True)
     w = pb.Wl.to(dev).requires_grad_(True)
-    logits, dist, act = proto_head_forward(x, pv, w, _layout(P, K, S, Cs, pb.ranges), want_distances=True, want_activations=True)
+    logits, dist, act = proto_head_forward(x, pv, w, bank_layout(P, K, S, Cs, pb.ranges), want_distances=True, want_activations=True)
     ((logits * pb.g_logits.reshape(-1, K).to(dev)).sum() + (dist * pb.g_dist.to(dev)).sum() + (act * pb.g_act.to(dev)).sum()).backward()
     torch.cuda.synchronize()
     assert x.grad.dtype == pb.x_dtype and x.grad.shape == x.shape
@@ -99,36 +95,36 @@ def run_backward(pb, dev):
 
 @pytest.mark.parametrize("case,x_dtype", FP32 + BF16, ids=_id)
 def test_forward_off_grid(case, x_dtype):
-    dev = _dev()
+    dev = gpu_device()
     pb, (rl, rd, ra) = _problem(case, x_dtype)
     logits, dist, act = run_forward(pb, dev)
     _report(f"forward {case} {_id(x_dtype)}", **forward_ratios(logits, dist, act, rl, rd, ra))
-    _assert_fwd(logits, dist, act, rl, rd, ra)
+    assert_fwd(logits, dist, act, rl, rd, ra)
 
 
 def test_forward_off_grid_signed_features():
     """3 randn features against a randn bank: the kernels document no sign assumption (functional.proto_head_forward: "any
     bf16 / fp32 values are accepted") and take none."""
-    dev = _dev()
+    dev = gpu_device()
     pb, (rl, rd, ra) = _problem("F1", torch.float32, True)
     assert (pb.conv < 0).any() and (pb.bank < 0).any() and pb.conv.abs().max() > 8
     logits, dist, act = run_forward(pb, dev)
     _report("forward F1 signed", **forward_ratios(logits, dist, act, rl, rd, ra))
-    _assert_fwd(logits, dist, act, rl, rd, ra)
+    assert_fwd(logits, dist, act, rl, rd, ra)
 
 
 @pytest.mark.parametrize("case,x_dtype", FP32 + BF16, ids=_id)
 def test_backward_off_grid(case, x_dtype):
-    dev = _dev()
+    dev = gpu_device()
     pb, _ = _problem(case, x_dtype)
     dx_ref, dp_ref, dw_ref = _restated(case, x_dtype)
     dx, dp, dw = run_backward(pb, dev)
-    tol = _dx_tol(x_dtype, pb.ranges)
+    tol = dx_tolerance(x_dtype, pb.ranges)
     _report(f"backward {case} {_id(x_dtype)}", dX=R.max_normalised(dx.float().cpu(), dx_ref) / tol,
             dP=R.max_normalised(dp.cpu(), dp_ref) / GRAD_TOL, dW=R.max_normalised(dw.cpu(), dw_ref) / GRAD_TOL)
-    _grad_close(dx, dx_ref, "dX", tol=tol)
-    _grad_close(dp, dp_ref, "dPrototypes")
-    _grad_close(dw, dw_ref, "dLastLayer")
+    grad_close(dx, dx_ref, "dX", tol=tol)
+    grad_close(dp, dp_ref, "dPrototypes")
+    grad_close(dw, dw_ref, "dLastLayer")
 
 
 @pytest.mark.parametrize("case,x_dtype", [("F1", torch.float32), ("F3", torch.float32), ("F1", torch.bfloat16)], ids=_id)
@@ -138,18 +134,18 @@ def test_gathered_and_tail_off_grid(case, x_dtype):
     per-site restatement of each loss, head / projection / grouping-head gradients against float64 autograd at (x~, p~)."""
     from scaleprotoseg_amd.functional import ClassGather, class_gather_table, proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     pb, (rl, rd, _) = _problem(case, x_dtype)
     B, S, Cs, P, K, H, W = pb.shape
     ident, ranges = pb.ident, pb.ranges
     g = torch.Generator().manual_seed(41)
     g_logits = pb.g_logits
-    dx_tol = _dx_tol(x_dtype, ranges)
+    dx_tol = dx_tolerance(x_dtype, ranges)
     tag = f"{case} {_id(x_dtype)}"
 
     # ---- class gather
-    lay = _layout(P, K, S, Cs, ranges)
-    lab0 = _labels(B, H, W, K, seed=5).reshape(B, -1) - 1
+    lay = bank_layout(P, K, S, Cs, ranges)
+    lab0 = gather_labels(B, H, W, K, seed=5).reshape(B, -1) - 1
     keys, J, table = class_gather_table(lay, ident, dev)
     gather = ClassGather(labels=lab0.to(dev, torch.int32).contiguous(), keys=keys, width=J, table=table)
     g_cls = torch.randn(B, H * W, J, generator=g) * 1e-3
@@ -174,10 +170,10 @@ def test_gathered_and_tail_off_grid(case, x_dtype):
             dW=R.max_normalised(w.grad.cpu(), w0.grad) / GRAD_TOL)
     assert ((got - cd_ref).abs() <= 1e-4 * (1 + cd_ref)).all()
     assert (got[cd_ref == 0] == 0).all()
-    _assert_fwd(logits, None, None, rl, None, None)
-    _grad_close(x.grad, dx_ref, "dX (gather)", tol=dx_tol)
-    _grad_close(pv.grad, dp_ref, "dPrototypes (gather)")
-    _grad_close(w.grad, w0.grad, "dLastLayer (gather)")
+    assert_fwd(logits, None, None, rl, None, None)
+    grad_close(x.grad, dx_ref, "dX (gather)", tol=dx_tol)
+    grad_close(pv.grad, dp_ref, "dPrototypes (gather)")
+    grad_close(w.grad, w0.grad, "dLastLayer (gather)")
 
     # ---- fused grouping tail
     G = 3
@@ -209,7 +205,7 @@ def test_gathered_and_tail_off_grid(case, x_dtype):
     pv = pb.bank.to(dev).requires_grad_(True)
     wdd = wd.to(dev).requires_grad_(True)
     wgd = wg.to(dev).requires_grad_(True)
-    logits, dist, _, gact = proto_head_forward(x, pv, wdd, _layout(P, U, S, Cs, ranges), group_tail=wgd)
+    logits, dist, _, gact = proto_head_forward(x, pv, wdd, bank_layout(P, U, S, Cs, ranges), group_tail=wgd)
     ((logits * g_logits.reshape(-1, K).to(dev)).sum() + (dist * pb.g_dist.to(dev)).sum()).backward()
     torch.cuda.synchronize()
     top = max(1.0, l_ref.abs().max().item())
@@ -221,10 +217,10 @@ def test_gathered_and_tail_off_grid(case, x_dtype):
     assert (logits.detach().cpu() - l_ref).abs().max().item() <= 1e-4 * top
     assert ((gact.detach().cpu() - units_ref).abs() <= 2e-4 * (1 + units_ref.abs())).all()
     assert ((dist.detach().cpu() - rd).abs() <= 1e-4 * (1 + rd)).all()
-    _grad_close(x.grad, dx_ref, "dX (tail)", tol=dx_tol)
-    _grad_close(pv.grad, dp_ref, "dPrototypes (tail)")
-    _grad_close(wgd.grad, wg0.grad, "dLastLayerGroup")
-    _grad_close(wdd.grad.cpu() * mask, dwd_ref, "dGroupProjection")
+    grad_close(x.grad, dx_ref, "dX (tail)", tol=dx_tol)
+    grad_close(pv.grad, dp_ref, "dPrototypes (tail)")
+    grad_close(wgd.grad, wg0.grad, "dLastLayerGroup")
+    grad_close(wdd.grad.cpu() * mask, dwd_ref, "dGroupProjection")
 
 
 def test_prototype_equal_to_an_off_grid_pixel():
@@ -233,7 +229,7 @@ def test_prototype_equal_to_an_off_grid_pixel():
     9.2 to about 3.5).  The argmin lands on the planted pixel, or on an EARLIER pixel with the same x~ (one is planted)."""
     from scaleprotoseg_amd.functional import proto_head_forward, push_masked_argmin
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = shape = (1, 4, 64, 228, 19, 12, 16)
     pb = R.build(shape, seed=4)
     conv, bank, ident, ranges = pb.conv.clone(), pb.bank.clone(), pb.ident, pb.ranges
@@ -252,7 +248,7 @@ def test_prototype_equal_to_an_off_grid_pixel():
     assert not torch.equal(R.bf16_rne(bank), bank) and not torch.equal(flat[:, :, twin_q], flat[:, :, planted[twin_p]])
     xt = R.bf16_rne(conv).view(S, Cs, H * W)
 
-    _, dist, _ = proto_head_forward(conv.to(dev), bank.to(dev), None, _layout(P, 1, S, Cs, ranges))
+    _, dist, _ = proto_head_forward(conv.to(dev), bank.to(dev), None, bank_layout(P, 1, S, Cs, ranges))
     idx, val = push_masked_argmin(dist, target.view(1, H, W).to(dev), ident, void_class=0)
     dist, idx = dist.cpu().view(P, H * W), idx.cpu()
     ref = O.scale_l2_convolution(R.bf16_rne(conv), R.bf16_rne(bank), ranges, S).view(P, H * W)
@@ -273,7 +269,7 @@ def test_fused_push_minimum_off_grid():
     minimum, the two-step path and the oracle's push on the written map agree bit for bit, distance ~0 at the copied pixel."""
     from scaleprotoseg_amd.functional import proto_head_forward, push_masked_argmin, push_min_from_features
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = shape = PUSH_FUSED_SHAPES[2]
     pb = R.build(shape, seed=31)
     conv, bank, ident, ranges = pb.conv.clone(), pb.bank.clone(), pb.ident, pb.ranges
@@ -287,7 +283,7 @@ def test_fused_push_minimum_off_grid():
     target = torch.randint(0, K + 1, (B, H, W), generator=g)
     target[target == 3] = 1                                # class 2 absent everywhere
     target[0, 1, 2] = target[0, 3, 2] = int(ident[p_sel].argmax()) + 1
-    layout = _layout(P, 1, S, Cs, ranges)
+    layout = bank_layout(P, 1, S, Cs, ranges)
     x = conv.to(dev)
     _, dist, _ = proto_head_forward(x, bank.to(dev), None, layout)
     idx2, val2 = push_masked_argmin(dist, target.to(dev), ident, void_class=0)
@@ -304,43 +300,20 @@ def test_fused_push_minimum_off_grid():
     assert ((dist.cpu() - ref).abs() <= 1e-4 * (1 + ref)).all()
 
 
-class _Fp32Backbone(nn.Module):
-    """Stand-in backbone (as tests/test_gpu_modules.py::_Backbone in its pool mode); with a bare Sigmoid behind it the module
-    hands the kernels unrounded fp32 features."""
-
-    def __init__(self, ch, stride=4):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-        self.pool = nn.AvgPool2d(stride)
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return self.base(self.pool(x))
-
-
 def test_push_is_a_fixed_point_off_grid():
     """push_prototypes_multiscale twice on 3 in-memory images (F3-sized bank, 8 x 12 latent grid, unrounded fp32 features).
     After the first push every surviving prototype lies within 1e-4 of its source pixel; the second push leaves bf16(bank)
     bit-identical and drops nothing.  The fp32 bank itself may move to another pixel with the same x~ - an exact tie of the
     distances, broken towards the lowest image and flat index as everywhere: the tie rule, not an error."""
-    import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.push import push_prototypes_multiscale
 
-    dev = _dev()
+    dev = gpu_device()
     _, S, Cs, P, K, _, _ = R.CASES["F3"]
-    torch.manual_seed(5)
-    net = spx.PPNetMultiScale(_Fp32Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S)
-    net.add_on_layers = nn.Sequential(nn.Sigmoid())
-    net = net.to(dev)
+    # the pooling stand-in with a bare Sigmoid behind it: the module hands the kernels unrounded fp32 features
+    net = proto_net(P, K, S, Cs, seed=5, backbone="pool", add_on=nn.Sequential(nn.Sigmoid()), device=dev)
     gen = torch.Generator().manual_seed(6)
 
-    class _Data(list):
-        convert_targets = None
-
-    data = _Data()
+    data = ListData()
     for _ in range(3):
         t = torch.randint(0, K + 1, (4, 6), generator=gen).repeat_interleave(8, 0).repeat_interleave(8, 1)
         data.append((torch.randn(3, 32, 48, generator=gen), t.numpy().astype(np.int64)))

@@ -13,29 +13,16 @@ import sys
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import overlap_restatement as R  # noqa: E402
-from test_overlap_cpu import CASES, planes_of  # noqa: E402
+from map_cases import OVERLAP_CASES as CASES, planes_of  # noqa: E402
+from support import gpu_device, group_net, proto_net  # noqa: E402
+from support import release_cached_blocks  # noqa: E402,F401  (a module-scoped autouse fixture, taken by importing its name)
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _release_cached_blocks():
-    yield
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-        torch.cuda.empty_cache()
 
 
 def _run(planes, labels, table, q, dev):
@@ -70,7 +57,7 @@ def _check_counts(res, ref_inter, ref_area, amb, labels, table):
 def test_fixture_thresholds_and_counts(name):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     c = CASES[name]
     planes, q, labels, table = planes_of(c), float(c["q"]), c["labels"], c["table"]
     H, W = labels.shape[1:]
@@ -123,7 +110,7 @@ def _wide_case(dev):
 
 
 def test_twelve_slots_and_a_repeated_channel_against_the_restatement():
-    dev = _dev()
+    dev = gpu_device()
     planes, labels, table, ref, _, res = _wide_case(dev)
     _check_counts(res, ref["inter"], ref["area"], ref["ambiguous"], labels.numpy(), table)
     assert int(res.inter[1, 1, 3]) == int(res.area[1, 1]) == int(res.area[1, 3]) > 0      # the same channel in two slots
@@ -133,7 +120,7 @@ def test_twelve_slots_and_a_repeated_channel_against_the_restatement():
 
 def test_partially_staged_tall_plane_against_the_restatement():
     """150 x 60 latent rows do not fit the LDS stage at once: every band stages its own rows plus the halo."""
-    dev = _dev()
+    dev = gpu_device()
     planes, labels = _random_case(11, 1, 3, 150, 60, 310, 97, 1, [[0]])
     table = np.array([[0, 1, 2]])
     ref = R.overlap_counts(planes.numpy(), labels.numpy(), table, 0.95)
@@ -144,7 +131,7 @@ def test_partially_staged_tall_plane_against_the_restatement():
 def test_strided_pixel_major_view_equals_contiguous():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     planes, labels, table, _, buf, _ = _wide_case(dev)
     N, C, h, w = planes.shape
     pix = planes.permute(0, 2, 3, 1).reshape(N * h * w, C).contiguous().to(dev)          # the forward's [M, P] layout
@@ -164,7 +151,7 @@ def test_strided_pixel_major_view_equals_contiguous():
 def test_two_updates_equal_the_sum_and_repeats_are_identical():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     planes, labels, table, _, buf, _ = _wide_case(dev)
     p, l = planes.to(dev), labels.to(dev)
     again = spx.ActivationOverlap(2, torch.as_tensor(table), dev, quantile=0.9)
@@ -184,7 +171,7 @@ def test_update_inside_a_captured_step():
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd import graphs
 
-    dev = _dev()
+    dev = gpu_device()
     planes, labels, table, _, buf, _ = _wide_case(dev)
     p, l = planes.to(dev), labels.to(dev)
     m = spx.ActivationOverlap(2, torch.as_tensor(table), dev, quantile=0.9)
@@ -194,18 +181,6 @@ def test_update_inside_a_captured_step():
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(m._buf, 2 * buf)
-
-
-class _Backbone(nn.Module):
-    def __init__(self, ch):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return x
 
 
 def _module_labels(N, H, W, classes):
@@ -219,11 +194,10 @@ def _module_labels(N, H, W, classes):
 def test_for_prototypes_with_distances_on_a_real_module():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     torch.manual_seed(5)
     P, K, S, Cs = 40, 10, 4, 64
-    net = spx.PPNetMultiScale(_Backbone(Cs * S), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S).to(dev).eval()
+    net = proto_net(P, K, S, Cs, device=dev).eval()
     conv = torch.randn(2, S * Cs, 9, 11, generator=torch.Generator().manual_seed(9)).to(dev)
     with torch.no_grad():
         _, dist = net.forward_from_conv_features(conv)
@@ -243,11 +217,10 @@ def test_for_prototypes_with_distances_on_a_real_module():
 def test_for_groups_on_a_real_module():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     torch.manual_seed(5)
     P, K, S, Cs, G = 40, 10, 4, 64, 6
-    net = spx.PPNetMultiScaleGroup(_Backbone(Cs * S), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                                   patch_classification=True, num_scales=S, num_groups=G).to(dev).eval()
+    net = group_net(P, K, S, Cs, G, device=dev).eval()
     conv = torch.randn(2, S * Cs, 9, 11, generator=torch.Generator().manual_seed(9)).to(dev)
     with torch.no_grad():
         _, act = net.forward_from_conv_features(conv, return_activations=True)

@@ -20,49 +20,9 @@ pytestmark = pytest.mark.gpu
 from oracle import loss_oracle as LO
 from oracle import ppnet_oracle as O
 from kld_cases import MIN_LOSS, correlated_planes
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-def _problem(B, S, Cs, P, K, H, W, seed=0, x_dtype=torch.float32):
-    g = torch.Generator().manual_seed(20220227 + seed)
-    conv = O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=g)))
-    bank = O.bf16_representable(torch.rand(P, Cs, 1, 1, generator=g))
-    ident = O.default_class_identity(P, K, S)
-    Wl = O.last_layer_init(ident) + 0.05 * torch.randn(K, P, generator=g)
-    return conv, bank, Wl, ident, O.default_scale_ranges(P, S)
-
-
-def _layout(P, K, S, Cs, ranges):
-    from scaleprotoseg_amd.functional import BankLayout
-
-    return BankLayout(P, K, S, Cs, tuple(ranges[s] for s in range(S)))
-
-
-def _assert_fwd(logits, dist, act, ref_logits, ref_dist, ref_act):
-    if dist is not None:
-        err = (dist.cpu() - ref_dist).abs()
-        assert (err <= 1e-4 * (1 + ref_dist)).all(), f"distance err {err.max().item()}"
-    if act is not None:
-        err = (act.cpu() - ref_act).abs()
-        assert (err <= 2e-4 * (1 + ref_act.abs())).all(), f"activation err {err.max().item()}"
-    if logits is not None:
-        rl = ref_logits.reshape(-1, ref_logits.shape[-1])
-        d = (logits.cpu().reshape(rl.shape) - rl).abs()
-        err = d.max().item()
-        assert err <= 1e-4 * max(1.0, rl.abs().max().item()), f"logit err {err}"
-        # ... and per element, relative with an absolute floor (a logit is a signed sum of P terms that passes through zero):
-        # |err| <= 1.1e-4 (|l| + 0.2 max|l|).  What bounds it is the operand precision of the head product - activations and head
-        # weights enter the MFMA as bf16 hi + lo pairs, 2^-17 of each TERM |a_p w_kp| (a <= 9.2) - so an element's error scales
-        # with the sum of its terms' magnitudes, not with the element.  700 fuzzed configurations peak at 1.002e-4 of this
-        # measure (seed 378 of test_random_gather_and_tail, in the suite below); 1e-4 with a 0.1 floor would take 24-bit
-        # operands (a third bf16 plane of W and a: twice the head MFMAs) - DESIGN.md 4
-        floor = 0.2 * max(1.0, rl.abs().max().item())
-        assert (d <= 1.1e-4 * (rl.abs() + floor)).all(), f"per-element logit err {(d / (rl.abs() + floor)).max().item()}"
+from parity_cases import (PUSH_FUSED_SHAPES, assert_fwd, bank_layout, check_random_configuration, check_random_gather_and_tail,
+                          dx_tolerance, gather_labels, problem, random_case)
+from support import Guarded, gpu_device, grad_close
 
 
 SHAPES = [
@@ -85,17 +45,17 @@ SHAPES = [
 def test_forward_matches_oracle(shape, x_dtype):
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = shape
-    conv, bank, Wl, ident, ranges = _problem(*shape)
+    conv, bank, Wl, ident, ranges = problem(*shape)
     ref_logits, ref_dist, ref_act = O.forward_from_conv_features(conv, bank, ranges, S, Wl)
     logits, dist, act = proto_head_forward(
-        conv.to(dev, x_dtype), bank.to(dev), Wl.to(dev), _layout(P, K, S, Cs, ranges),
+        conv.to(dev, x_dtype), bank.to(dev), Wl.to(dev), bank_layout(P, K, S, Cs, ranges),
         want_distances=True, want_activations=True,
     )
     torch.cuda.synchronize()
     assert dist.shape == (B, P, H, W) and act.shape == (B * H * W, P) and logits.shape == (B * H * W, K)
-    _assert_fwd(logits, dist, act, ref_logits, ref_dist, ref_act)
+    assert_fwd(logits, dist, act, ref_logits, ref_dist, ref_act)
 
 
 @pytest.mark.parametrize("name", ["proto_ms_city", "proto_s1_wide", "proto_s3", "proto_floor", "proto_ms_small"])
@@ -103,7 +63,7 @@ def test_forward_matches_golden(golden, name):
     """Fixtures generated from the reference's own classes (oracle/gen_golden.py)."""
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     g = golden(name)
     S = int(g["num_scales"])
     conv = torch.from_numpy(g["conv"])
@@ -112,29 +72,11 @@ def test_forward_matches_golden(golden, name):
     P, Cs = bank.shape[0], bank.shape[1]
     ranges = {s: (int(lo), int(hi)) for s, (lo, hi) in enumerate(g["scale_ranges"])}
     logits, dist, act = proto_head_forward(
-        conv.to(dev), bank.to(dev), Wl.to(dev), _layout(P, Wl.shape[0], S, Cs, ranges),
+        conv.to(dev), bank.to(dev), Wl.to(dev), bank_layout(P, Wl.shape[0], S, Cs, ranges),
         want_distances=True, want_activations=True,
     )
-    _assert_fwd(logits, dist, act, torch.from_numpy(g["logits"]), torch.from_numpy(g["distances"]),
+    assert_fwd(logits, dist, act, torch.from_numpy(g["logits"]), torch.from_numpy(g["distances"]),
                 torch.from_numpy(g["activations"]))
-
-
-GRAD_TOL = 1e-3        # gradients rel 1e-3 (max-normalised)
-BF16_DX_TOL = 4e-3     # dX returned in bf16 (bf16 features): ONE output rounding is half a bf16 ulp = 2^-8 of the element
-
-
-def _dx_tol(x_dtype, ranges=None):
-    """fp32 features: 1e-3.  bf16 features: dX is returned in bf16 - ONE output rounding, also for scales of more than 192
-    prototypes (several panels: their shares are summed in an fp32 scratch, round 4; through the bf16 buffer it was one
-    rounding per panel)."""
-    return GRAD_TOL if x_dtype == torch.float32 else BF16_DX_TOL
-
-
-def _grad_close(got, ref, what, tol=GRAD_TOL):
-    got, ref = got.detach().float().cpu(), ref.detach().float().cpu()
-    scale = ref.abs().max().item() + 1e-30
-    err = (got - ref).abs().max().item()
-    assert err <= tol * scale, f"{what}: err {err:.3e} vs scale {scale:.3e}"
 
 
 BWD_SHAPES = [
@@ -157,9 +99,9 @@ BWD_SHAPES = [
 def test_backward_matches_oracle(shape, x_dtype):
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = shape
-    conv, bank, Wl, ident, ranges = _problem(*shape, seed=1)
+    conv, bank, Wl, ident, ranges = problem(*shape, seed=1)
     g = torch.Generator().manual_seed(7)
     g_logits = torch.randn(B, H, W, K, generator=g) * 1e-3
     g_dist = torch.randn(B, P, H, W, generator=g) * 1e-3
@@ -169,21 +111,21 @@ def test_backward_matches_oracle(shape, x_dtype):
     x = conv.to(dev, x_dtype).requires_grad_(True)
     pv = bank.to(dev).requires_grad_(True)
     w = Wl.to(dev).requires_grad_(True)
-    logits, dist, act = proto_head_forward(x, pv, w, _layout(P, K, S, Cs, ranges), want_distances=True, want_activations=True)
+    logits, dist, act = proto_head_forward(x, pv, w, bank_layout(P, K, S, Cs, ranges), want_distances=True, want_activations=True)
     loss = (logits * g_logits.reshape(-1, K).to(dev)).sum() + (dist * g_dist.to(dev)).sum() + (act * g_act.to(dev)).sum()
     loss.backward()
     torch.cuda.synchronize()
     assert x.grad.dtype == x_dtype and x.grad.shape == x.shape
-    _grad_close(x.grad, dx_ref, "dX", tol=_dx_tol(x_dtype, ranges))
-    _grad_close(pv.grad, dp_ref, "dPrototypes")
-    _grad_close(w.grad, dw_ref, "dLastLayer")
+    grad_close(x.grad, dx_ref, "dX", tol=dx_tolerance(x_dtype, ranges))
+    grad_close(pv.grad, dp_ref, "dPrototypes")
+    grad_close(w.grad, dw_ref, "dLastLayer")
 
 
 @pytest.mark.parametrize("name", ["proto_ms_city", "proto_s1_wide"])
 def test_backward_matches_golden(golden, name):
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     g = golden(name)
     S = int(g["num_scales"])
     bank = torch.from_numpy(g["prototype_vectors"])
@@ -193,51 +135,51 @@ def test_backward_matches_golden(golden, name):
     x = torch.from_numpy(g["conv"]).to(dev).requires_grad_(True)
     pv = bank.to(dev).requires_grad_(True)
     w = Wl.to(dev).requires_grad_(True)
-    logits, dist, act = proto_head_forward(x, pv, w, _layout(P, K, S, Cs, ranges), want_distances=True, want_activations=True)
+    logits, dist, act = proto_head_forward(x, pv, w, bank_layout(P, K, S, Cs, ranges), want_distances=True, want_activations=True)
     loss = (
         (logits * torch.from_numpy(g["g_logits"]).reshape(-1, K).to(dev)).sum()
         + (dist * torch.from_numpy(g["g_dist"]).to(dev)).sum()
         + (act * torch.from_numpy(g["g_act"]).to(dev)).sum()
     )
     loss.backward()
-    _grad_close(x.grad, torch.from_numpy(g["d_conv"]), "dX")
-    _grad_close(pv.grad, torch.from_numpy(g["d_prototypes"]), "dPrototypes")
-    _grad_close(w.grad, torch.from_numpy(g["d_last_layer"]), "dLastLayer")
+    grad_close(x.grad, torch.from_numpy(g["d_conv"]), "dX")
+    grad_close(pv.grad, torch.from_numpy(g["d_prototypes"]), "dPrototypes")
+    grad_close(w.grad, torch.from_numpy(g["d_last_layer"]), "dLastLayer")
 
 
 def test_backward_partial_inputs():
     """Only logits consumed, bank frozen: dX and dW still flow; distances-only: dX and dP flow."""
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     shape = (1, 4, 64, 228, 19, 9, 16)
     B, S, Cs, P, K, H, W = shape
-    conv, bank, Wl, ident, ranges = _problem(*shape, seed=2)
+    conv, bank, Wl, ident, ranges = problem(*shape, seed=2)
     g = torch.Generator().manual_seed(3)
     g_logits = torch.randn(B, H, W, K, generator=g) * 1e-3
     zeros_d = torch.zeros(B, P, H, W)
     _, _, _, dx_ref, dp_ref, dw_ref = O.fwd_bwd_reference(conv, bank, ranges, S, Wl, g_logits, zeros_d)
     x = conv.to(dev).requires_grad_(True)
     w = Wl.to(dev).requires_grad_(True)
-    logits, dist, _ = proto_head_forward(x, bank.to(dev), w, _layout(P, K, S, Cs, ranges))
+    logits, dist, _ = proto_head_forward(x, bank.to(dev), w, bank_layout(P, K, S, Cs, ranges))
     (logits * g_logits.reshape(-1, K).to(dev)).sum().backward()
-    _grad_close(x.grad, dx_ref, "dX (logits only)")
-    _grad_close(w.grad, dw_ref, "dW (logits only)")
+    grad_close(x.grad, dx_ref, "dX (logits only)")
+    grad_close(w.grad, dw_ref, "dW (logits only)")
 
     g_dist = torch.randn(B, P, H, W, generator=g) * 1e-3
     _, _, _, dx_ref, dp_ref, _ = O.fwd_bwd_reference(conv, bank, ranges, S, Wl, torch.zeros(B, H, W, K), g_dist)
     x = conv.to(dev).requires_grad_(True)
     pv = bank.to(dev).requires_grad_(True)
-    _, dist, _ = proto_head_forward(x, pv, None, _layout(P, 1, S, Cs, ranges))
+    _, dist, _ = proto_head_forward(x, pv, None, bank_layout(P, 1, S, Cs, ranges))
     (dist * g_dist.to(dev)).sum().backward()
-    _grad_close(x.grad, dx_ref, "dX (distances only)")
-    _grad_close(pv.grad, dp_ref, "dP (distances only)")
+    grad_close(x.grad, dx_ref, "dX (distances only)")
+    grad_close(pv.grad, dp_ref, "dP (distances only)")
 
 
 def test_push_argmin_golden(golden):
     from scaleprotoseg_amd.functional import push_masked_argmin
 
-    dev = _dev()
+    dev = gpu_device()
     g = golden("push_argmin")
     idx, val = push_masked_argmin(
         torch.from_numpy(g["distances"]).to(dev), torch.from_numpy(g["target"])[None].to(dev),
@@ -252,7 +194,7 @@ def test_push_argmin_random(hw):
     """Bit-exact indices incl. absent classes, exact ties and multi-chunk rows."""
     from scaleprotoseg_amd.functional import push_masked_argmin
 
-    dev = _dev()
+    dev = gpu_device()
     H, W = hw
     B, K, S, r = 2, 19, 4, 3
     P = K * S * r
@@ -271,15 +213,6 @@ def test_push_argmin_random(hw):
     assert (ref_val == 1e10).any()
 
 
-PUSH_FUSED_SHAPES = [
-    # B, S, Cs,  P,   K,  H,   W
-    (2, 4, 64, 228, 19, 33, 65),      # the gin's bank, odd grid (ragged last tile, unaligned rows)
-    (1, 1, 256, 190, 19, 64, 128),    # north-star bank, 64 full tiles
-    (3, 2, 32, 44, 11, 9, 13),        # tiny: one partial tile per image
-    (1, 4, 64, 1800, 150, 17, 19),    # ADE bank: several panels per scale
-]
-
-
 @pytest.mark.parametrize("shape", PUSH_FUSED_SHAPES)
 @pytest.mark.parametrize("x_dtype", [torch.float32, torch.bfloat16])
 def test_fused_push_minimum_equals_the_two_step_push(shape, x_dtype):
@@ -289,9 +222,9 @@ def test_fused_push_minimum_equals_the_two_step_push(shape, x_dtype):
     and a prototype copied from a pixel (distance 0) are all in."""
     from scaleprotoseg_amd.functional import proto_head_forward, push_masked_argmin, push_min_from_features
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = shape
-    conv, bank, Wl, ident, ranges = _problem(*shape, seed=31)
+    conv, bank, Wl, ident, ranges = problem(*shape, seed=31)
     conv[:, :, 2:4, :] = conv[:, :, 0:2, :]            # repeated rows of pixels: exact ties along a prototype row
     cv = conv[0].view(S, Cs, H, W)
     p_sel = next(p for p in range(P // S) if int(ident[p].argmax()) != 2)
@@ -301,7 +234,7 @@ def test_fused_push_minimum_equals_the_two_step_push(shape, x_dtype):
     target = torch.randint(0, K + 1, (B, H, W), generator=g)
     target[target == 3] = 1                                # class 2 absent everywhere
     target[0, 1, 2] = target[0, 3, 2] = int(ident[p_sel].argmax()) + 1
-    layout = _layout(P, 1, S, Cs, ranges)
+    layout = bank_layout(P, 1, S, Cs, ranges)
     x = conv.to(dev, x_dtype)
     _, dist, _ = proto_head_forward(x, bank.to(dev), None, layout)
     idx2, val2 = push_masked_argmin(dist, target.to(dev), ident, void_class=0)
@@ -323,20 +256,20 @@ def test_fused_push_rejects_a_fractional_identity():
     from scaleprotoseg_amd import SpxError
     from scaleprotoseg_amd.functional import push_min_from_features
 
-    dev = _dev()
+    dev = gpu_device()
     shape = (1, 1, 32, 20, 5, 4, 8)
     B, S, Cs, P, K, H, W = shape
-    conv, bank, Wl, ident, ranges = _problem(*shape, seed=33)
+    conv, bank, Wl, ident, ranges = problem(*shape, seed=33)
     ident = ident.clone()
     ident[0, 0] = 0.5
     with pytest.raises(SpxError):
-        push_min_from_features(conv.to(dev), bank.to(dev), _layout(P, 1, S, Cs, ranges), torch.zeros(B, H, W, dtype=torch.long), ident)
+        push_min_from_features(conv.to(dev), bank.to(dev), bank_layout(P, 1, S, Cs, ranges), torch.zeros(B, H, W, dtype=torch.long), ident)
 
 
 def test_argmin_over_images():
     from scaleprotoseg_amd.functional import argmin_over_images
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(5)
     vals = torch.floor(torch.rand(37, 228, generator=g) * 8)  # ties -> lowest image index
     best = argmin_over_images(vals.to(dev))
@@ -347,15 +280,15 @@ def test_prototype_equal_to_pixel():
     """After a push a prototype IS a latent pixel: its distance there must be ~0 and win the argmin."""
     from scaleprotoseg_amd.functional import proto_head_forward, push_masked_argmin
 
-    dev = _dev()
+    dev = gpu_device()
     shape = (1, 4, 64, 228, 19, 12, 16)
     B, S, Cs, P, K, H, W = shape
-    conv, bank, Wl, ident, ranges = _problem(*shape, seed=4)
+    conv, bank, Wl, ident, ranges = problem(*shape, seed=4)
     cv = conv.view(S, Cs, H, W)
     for p in range(0, P, 7):
         s = p // (P // S)
         bank[p, :, 0, 0] = cv[s, :, (p * 5) % H, (p * 3) % W]
-    _, dist, _ = proto_head_forward(conv.to(dev), bank.to(dev), None, _layout(P, 1, S, Cs, ranges))
+    _, dist, _ = proto_head_forward(conv.to(dev), bank.to(dev), None, bank_layout(P, 1, S, Cs, ranges))
     for p in range(0, P, 7):
         assert dist[0, p, (p * 5) % H, (p * 3) % W].item() <= 1e-4
     ref = O.scale_l2_convolution(conv, bank, ranges, S)
@@ -367,13 +300,13 @@ def test_large_shape_properties():
     (a) a pixel's outputs do not depend on where it sits in the grid, (b) logits are linear in the head."""
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     S, Cs, P, K = 1, 256, 190, 19
     H, W = 256, 512
-    conv, bank, Wl, ident, ranges = _problem(1, S, Cs, P, K, 8, 16, seed=6)
+    conv, bank, Wl, ident, ranges = problem(1, S, Cs, P, K, 8, 16, seed=6)
     small = conv.to(dev, torch.bfloat16)
     big = small.repeat(1, 1, H // 8, W // 16).contiguous()
-    lay = _layout(P, K, S, Cs, ranges)
+    lay = bank_layout(P, K, S, Cs, ranges)
     l_s, d_s, _ = proto_head_forward(small, bank.to(dev), Wl.to(dev), lay)
     l_b, d_b, _ = proto_head_forward(big, bank.to(dev), Wl.to(dev), lay)
     torch.cuda.synchronize()
@@ -394,14 +327,6 @@ GATHER_SHAPES = [
 ]
 
 
-def _labels(B, H, W, K, seed):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randint(0, K + 1, (B, H, W), generator=g)      # reference convention: 0 = void, 1..K
-    t[t == K] = 0                                            # last class absent ...
-    t[0, 0, 0] = K                                           # ... but for one pixel
-    return t
-
-
 @pytest.mark.parametrize("shape", GATHER_SHAPES)
 @pytest.mark.parametrize("x_dtype", [torch.float32, torch.bfloat16])
 def test_class_gathered_forward_backward(shape, x_dtype):
@@ -409,12 +334,12 @@ def test_class_gathered_forward_backward(shape, x_dtype):
     and gradients through it equal autograd through the full map with the scattered gradient."""
     from scaleprotoseg_amd.functional import ClassGather, class_gather_table, proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = shape
-    conv, bank, Wl, ident, ranges = _problem(*shape, seed=11)
-    target = _labels(B, H, W, K, seed=5)
+    conv, bank, Wl, ident, ranges = problem(*shape, seed=11)
+    target = gather_labels(B, H, W, K, seed=5)
     lab0 = (target.reshape(B, -1) - 1)
-    lay = _layout(P, K, S, Cs, ranges)
+    lay = bank_layout(P, K, S, Cs, ranges)
     keys, J, table = class_gather_table(lay, ident, dev)
     assert torch.equal(table.cpu(), O.class_slot_table(ident))
     gather = ClassGather(labels=lab0.to(dev, torch.int32).contiguous(), keys=keys, width=J, table=table)
@@ -443,12 +368,12 @@ def test_class_gathered_forward_backward(shape, x_dtype):
     assert (err <= 1e-4 * (1 + ref)).all(), f"class distance err {err.max().item()}"
     # entries no prototype maps to / void pixels are exactly 0
     assert (got[ref == 0] == 0).all()
-    _assert_fwd(logits, None, None, l_ref.detach(), None, None)
+    assert_fwd(logits, None, None, l_ref.detach(), None, None)
     ((logits * g_logits.reshape(-1, K).to(dev)).sum() + (cd * g_cls.permute(0, 2, 1).contiguous().to(dev)).sum()).backward()
     torch.cuda.synchronize()
-    _grad_close(x.grad, c0.grad, "dX", tol=_dx_tol(x_dtype, ranges))
-    _grad_close(pv.grad, p0.grad, "dPrototypes")
-    _grad_close(w.grad, w0.grad, "dLastLayer")
+    grad_close(x.grad, c0.grad, "dX", tol=dx_tolerance(x_dtype, ranges))
+    grad_close(pv.grad, p0.grad, "dPrototypes")
+    grad_close(w.grad, w0.grad, "dLastLayer")
 
 
 def test_kld_through_the_module(golden):
@@ -456,10 +381,10 @@ def test_kld_through_the_module(golden):
     == the oracle's KLD (pinned to the reference's KLDLoss) on the full distance map, value and gradients."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = 2, 4, 16, 40, 5, 9, 11
-    conv, bank, Wl, ident, ranges = _problem(B, S, Cs, P, K, H, W, seed=3)
-    target = _labels(B, H, W, K, seed=2)
+    conv, bank, Wl, ident, ranges = problem(B, S, Cs, P, K, H, W, seed=3)
+    target = gather_labels(B, H, W, K, seed=2)
 
     class _Feat(torch.nn.Module):
         def __init__(self):
@@ -491,8 +416,8 @@ def test_kld_through_the_module(golden):
     k_ref = O.kld_loss(d_ref, target, ident, S, ranges)
     k_ref.backward()
     assert abs(kld.item() - k_ref.item()) <= 1e-4 * max(1.0, abs(k_ref.item())), (kld.item(), k_ref.item())
-    _grad_close(x.grad, c0.grad, "dX via KLD")
-    _grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes via KLD")
+    grad_close(x.grad, c0.grad, "dX via KLD")
+    grad_close(net.prototype_vectors.grad, p0.grad, "dPrototypes via KLD")
     # same module, same loss class, full-map input: identical value
     logits2, dist2 = net.forward_from_conv_features(conv.to(dev))
     k2 = spx.KLDLoss(net.prototype_class_identity, S, net.scale_num_prototypes)(dist2, target.to(dev))
@@ -506,11 +431,11 @@ def test_north_star_size_properties():
     dLastLayer equal (number of periods) x the one-period gradients up to fp32 summation order."""
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     S, Cs, P, K = 1, 256, 190, 19
     H, W, h, w = 1024, 2048, 8, 64
-    conv, bank, Wl, ident, ranges = _problem(1, S, Cs, P, K, h, w, seed=21)
-    lay = _layout(P, K, S, Cs, ranges)
+    conv, bank, Wl, ident, ranges = problem(1, S, Cs, P, K, h, w, seed=21)
+    lay = bank_layout(P, K, S, Cs, ranges)
     g = torch.Generator().manual_seed(3)
     gl_s = (torch.randn(h * w, K, generator=g) * 1e-3).to(dev)
     gd_s = (torch.randn(1, P, h, w, generator=g) * 1e-3).to(dev)
@@ -534,8 +459,8 @@ def test_north_star_size_properties():
     assert torch.equal(d_b, d_s.repeat(1, 1, H // h, W // w))
     assert torch.equal(l_b.view(H, W, K), l_s.view(h, w, K).repeat(H // h, W // w, 1))
     assert torch.equal(dx_b, dx_s.repeat(1, 1, H // h, W // w))
-    _grad_close(dp_b, reps * dp_s, "dPrototypes (full size)")
-    _grad_close(dw_b, reps * dw_s, "dLastLayer (full size)")
+    grad_close(dp_b, reps * dp_s, "dPrototypes (full size)")
+    grad_close(dw_b, reps * dw_s, "dLastLayer (full size)")
 
 
 def test_argument_errors():
@@ -544,8 +469,8 @@ def test_argument_errors():
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
-    lay = _layout(40, 5, 4, 16, O.default_scale_ranges(40, 4))
+    dev = gpu_device()
+    lay = bank_layout(40, 5, 4, 16, O.default_scale_ranges(40, 4))
     bank = torch.rand(40, 16, 1, 1, device=dev)
     head = torch.rand(5, 40, device=dev)
     with pytest.raises(spx.SpxError, match="channels"):
@@ -557,14 +482,14 @@ def test_argument_errors():
     with pytest.raises(spx.SpxError, match="empty input"):
         proto_head_forward(torch.rand(0, 64, 4, 4, device=dev), bank, head, lay)
     # maximum size: P * H * W must stay below 2^29 (32-bit byte offsets inside one image of the distance map)
-    big = _layout(190, 19, 1, 16, {0: (0, 190)})
+    big = bank_layout(190, 19, 1, 16, {0: (0, 190)})
     with pytest.raises(spx.SpxError, match="too large"):
         proto_head_forward(torch.zeros(1, 16, 1700, 1700, device=dev, dtype=torch.bfloat16), torch.rand(190, 16, 1, 1, device=dev),
                            torch.rand(19, 190, device=dev), big)
     # P % num_scales != 0 with the reference's own scale table (Ps = P // S: 189 of 190 rows covered,
     # model_multiscale.py:146-149): its forward raises at F.linear, the plan is rejected here
     with pytest.raises(spx.SpxError):
-        _layout(190, 19, 3, 16, {0: (0, 63), 1: (63, 126), 2: (126, 189)}).plan()
+        bank_layout(190, 19, 3, 16, {0: (0, 63), 1: (63, 126), 2: (126, 189)}).plan()
 
 
 @pytest.mark.parametrize("shape", [(2, 4, 64, 228, 19, 9, 13, 3), (1, 1, 64, 210, 21, 8, 16, 3), (1, 4, 16, 40, 5, 9, 11, 3)])
@@ -574,9 +499,9 @@ def test_fused_group_tail(shape, x_dtype):
     the oracle's compute_group + last_layer_group (model_multiscale_group.py:283-308) and its autograd."""
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W, G = shape
-    conv, bank, _, ident, ranges = _problem(B, S, Cs, P, K, H, W, seed=31)
+    conv, bank, _, ident, ranges = problem(B, S, Cs, P, K, H, W, seed=31)
     g = torch.Generator().manual_seed(17)
     idx = O.class_prototype_index(ident)
     idx = [i for i in idx if len(i) > 0]
@@ -606,7 +531,7 @@ def test_fused_group_tail(shape, x_dtype):
     pv = bank.to(dev).requires_grad_(True)
     wdd = wd.to(dev).requires_grad_(True)
     wgd = wg.to(dev).requires_grad_(True)
-    logits, dist, _, gact = proto_head_forward(x, pv, wdd, _layout(P, U, S, Cs, ranges), group_tail=wgd)
+    logits, dist, _, gact = proto_head_forward(x, pv, wdd, bank_layout(P, U, S, Cs, ranges), group_tail=wgd)
     torch.cuda.synchronize()
     rl = l_ref.detach()
     err = (logits.detach().cpu() - rl).abs().max().item()
@@ -615,16 +540,16 @@ def test_fused_group_tail(shape, x_dtype):
     assert ((gact.cpu() - ug).abs() <= 2e-4 * (1 + ug.abs())).all(), "group activations"
     ((logits * g_logits.reshape(-1, K).to(dev)).sum() + (dist * g_dist.to(dev)).sum()).backward()
     torch.cuda.synchronize()
-    _grad_close(x.grad, c0.grad, "dX", tol=_dx_tol(x_dtype, ranges))
-    _grad_close(pv.grad, p0.grad, "dPrototypes")
-    _grad_close(wgd.grad, wg0.grad, "dLastLayerGroup")
+    grad_close(x.grad, c0.grad, "dX", tol=dx_tolerance(x_dtype, ranges))
+    grad_close(pv.grad, p0.grad, "dPrototypes")
+    grad_close(wgd.grad, wg0.grad, "dLastLayerGroup")
     dwd_ref = torch.zeros(U, P)
     for k, i in enumerate(idx):
         dwd_ref[k * G:(k + 1) * G, i] = gw0[k].grad
     mask = torch.zeros(U, P, dtype=torch.bool)
     for k, i in enumerate(idx):
         mask[k * G:(k + 1) * G, i] = True
-    _grad_close(wdd.grad.cpu() * mask, dwd_ref, "dGroupProjection")
+    grad_close(wdd.grad.cpu() * mask, dwd_ref, "dGroupProjection")
 
 
 # the reference's own evaluation shapes (eval_valid_multiscale.py:229-234: latent 129 x 257 -> 1024 x 2048 for Cityscapes, 65 x 65
@@ -642,7 +567,7 @@ def test_upsample_argext(case):
     wherever the runner-up is not within that tolerance."""
     from scaleprotoseg_amd.functional import upsample_argext
 
-    dev = _dev()
+    dev = gpu_device()
     N, C, h, w, H, W, largest = case
     g = torch.Generator().manual_seed(77)
     src = torch.rand(N, C, h, w, generator=g) * 10
@@ -667,143 +592,16 @@ def test_upsample_argext(case):
     assert clear.float().mean() > 0.99
 
 
-def _random_case(rng):
-    S = int(rng.choice([1, 2, 3, 4]))
-    Cs = int(rng.choice([16, 32, 48, 64, 80, 128]))
-    K = int(rng.choice([2, 3, 5, 19, 21, 40, 64, 70]))
-    per_scale = [int(rng.integers(1, 7)) * max(1, K // int(rng.choice([1, 2, 4]))) for _ in range(S)]
-    per_scale = [min(p, 230) for p in per_scale]
-    if rng.random() < 0.4:                       # unequal scales, as after the push's de-duplication
-        per_scale = [max(1, p - int(rng.integers(0, 5))) for p in per_scale]
-    B = int(rng.integers(1, 4))
-    H, W = int(rng.integers(1, 24)), int(rng.integers(1, 40))
-    if rng.random() < 0.3:
-        W = 8 * int(rng.integers(1, 12))         # aligned rows: vector staging path
-    if rng.random() < 0.2:                       # (drawn last: the other seeds keep their round-3 configurations)
-        # H*W a multiple of 64 and scales wider than 64 channels: the LDS-DMA parameter kernel (bf16 features, K <= 32)
-        H, W, Cs = 8 * int(rng.integers(1, 4)), 8 * int(rng.integers(1, 6)), int(rng.choice([80, 96, 128]))
-    return B, S, Cs, per_scale, K, H, W
-
-
 @pytest.mark.parametrize("seed", list(range(24)))
 def test_random_configurations(seed):
-    """Randomised shapes (scale counts, unequal per-scale banks, channel widths with 16-channel tails, 1/2/5-block
-    heads, odd and aligned grids, partial tiles, both feature dtypes): forward outputs and all gradients against the
-    oracle, with the stated tolerances."""
-    from scaleprotoseg_amd.functional import BankLayout, proto_head_forward
-
-    dev = _dev()
-    rng = np.random.default_rng(1000 + seed)
-    B, S, Cs, per_scale, K, H, W = _random_case(rng)
-    P = sum(per_scale)
-    ranges, lo = {}, 0
-    for s, n in enumerate(per_scale):
-        ranges[s] = (lo, lo + n)
-        lo += n
-    g = torch.Generator().manual_seed(seed)
-    conv = O.bf16_representable(torch.sigmoid(torch.randn(B, S * Cs, H, W, generator=g)))
-    bank = O.bf16_representable(torch.rand(P, Cs, 1, 1, generator=g))
-    Wl = torch.randn(K, P, generator=g) * 0.3
-    x_dtype = torch.bfloat16 if seed % 2 else torch.float32
-    g_logits = torch.randn(B, H, W, K, generator=g) * 1e-3
-    g_dist = torch.randn(B, P, H, W, generator=g) * 1e-3
-    g_act = torch.randn(B * H * W, P, generator=g) * 1e-3
-    l_ref, d_ref, a_ref, dx_ref, dp_ref, dw_ref = O.fwd_bwd_reference(conv, bank, ranges, S, Wl, g_logits, g_dist, g_act)
-
-    x = conv.to(dev, x_dtype).requires_grad_(True)
-    pv = bank.to(dev).requires_grad_(True)
-    w = Wl.to(dev).requires_grad_(True)
-    lay = BankLayout(P, K, S, Cs, tuple(ranges[s] for s in range(S)))
-    logits, dist, act = proto_head_forward(x, pv, w, lay, want_distances=True, want_activations=True)
-    torch.cuda.synchronize()
-    _assert_fwd(logits, dist, act, l_ref, d_ref, a_ref)
-    ((logits * g_logits.reshape(-1, K).to(dev)).sum() + (dist * g_dist.to(dev)).sum() + (act * g_act.to(dev)).sum()).backward()
-    torch.cuda.synchronize()
-    tag = f"B{B} S{S} Cs{Cs} P{per_scale} K{K} {H}x{W} {x_dtype}"
-    _grad_close(x.grad, dx_ref, "dX " + tag, tol=_dx_tol(x_dtype, ranges))
-    # G enters dX and dPrototypes as ONE fp16 plane scaled per tile by a power of two (11 significant bits per element)
-    _grad_close(pv.grad, dp_ref, "dPrototypes " + tag)
-    # d_W = dLogits^T . a: the activations cross HBM as block-scaled int16 codes and enter the MFMA as an exact bf16 hi + lo
-    # pair, dLogits as split bf16
-    _grad_close(w.grad, dw_ref, "dLastLayer " + tag)
+    check_random_configuration(seed)
 
 
 # (40, 48, 84: the configurations that missed a 0.1 max|l| per-element floor in the round-2 fuzz run; 378: the worst of the
-# round-3 run, 1.002e-4 of the per-element measure - all fixed regression cases of the bound stated in _assert_fwd)
+# round-3 run, 1.002e-4 of the per-element measure - all fixed regression cases of the bound stated in parity_cases.assert_fwd)
 @pytest.mark.parametrize("seed", list(range(12)) + [40, 48, 84, 378])
 def test_random_gather_and_tail(seed):
-    """Randomised shapes for the two extended modes: class-gathered distances (even seeds) and the fused grouping
-    tail (odd seeds), forward + all gradients against the oracle."""
-    from scaleprotoseg_amd.functional import BankLayout, ClassGather, class_gather_table, proto_head_forward
-
-    dev = _dev()
-    rng = np.random.default_rng(5000 + seed)
-    S = int(rng.choice([1, 2, 4]))
-    Cs = int(rng.choice([16, 32, 64]))
-    K = int(rng.choice([2, 3, 5, 7, 19]))
-    r = int(rng.integers(1, 4))
-    P = K * S * r
-    B, H, W = int(rng.integers(1, 3)), int(rng.integers(2, 14)), int(rng.integers(2, 30))
-    x_dtype = torch.bfloat16 if (seed // 2) % 2 else torch.float32
-    conv, bank, Wl, ident, ranges = _problem(B, S, Cs, P, K, H, W, seed=100 + seed)
-    lay_k = BankLayout(P, K, S, Cs, tuple(ranges[s] for s in range(S)))
-    g = torch.Generator().manual_seed(seed)
-    g_logits = torch.randn(B, H, W, K, generator=g) * 1e-3
-    x = conv.to(dev, x_dtype).requires_grad_(True)
-    pv = bank.to(dev).requires_grad_(True)
-    c0 = conv.clone().requires_grad_(True)
-    p0 = bank.clone().requires_grad_(True)
-    # tiny banks (P as small as 4): dX is a sum of a handful of signed terms G_p (x - p), each carrying G's bf16
-    # rounding (2^-8); with cancellation between them the error relative to max|dX| can pass the 4e-3 of the
-    # realistic shapes, so these toy cases get 6e-3
-    dx_tol = _dx_tol(x_dtype, ranges)
-    if seed % 2 == 0:
-        target = _labels(B, H, W, K, seed=seed)
-        lab0 = target.reshape(B, -1) - 1
-        keys, J, table = class_gather_table(lay_k, ident, dev)
-        gather = ClassGather(labels=lab0.to(dev, torch.int32).contiguous(), keys=keys, width=J, table=table)
-        g_cls = torch.randn(B, H * W, J, generator=g) * 1e-3
-        w0 = Wl.clone().requires_grad_(True)
-        l_ref, d_ref, _ = O.forward_from_conv_features(c0, p0, ranges, S, w0)
-        cd_ref = O.gather_class_distances(d_ref, lab0, ident)
-        ((l_ref * g_logits).sum() + (cd_ref * g_cls).sum()).backward()
-        w = Wl.to(dev).requires_grad_(True)
-        logits, cd, _ = proto_head_forward(x, pv, w, lay_k, class_gather=gather)
-        got = cd.detach().cpu().permute(0, 2, 1)
-        assert ((got - cd_ref.detach()).abs() <= 1e-4 * (1 + cd_ref.detach())).all()
-        _assert_fwd(logits, None, None, l_ref.detach(), None, None)
-        ((logits * g_logits.reshape(-1, K).to(dev)).sum() + (cd * g_cls.permute(0, 2, 1).contiguous().to(dev)).sum()).backward()
-        torch.cuda.synchronize()
-        _grad_close(w.grad, w0.grad, "dLastLayer")
-    else:
-        G = int(rng.integers(2, 4))
-        idx = [i for i in O.class_prototype_index(ident) if len(i) > 0]
-        gw = [O.projection_simplex_sort(torch.rand(G, len(i), generator=g)) for i in idx]
-        U = G * len(idx)
-        wg = torch.randn(K, U, generator=g) * 0.5
-        gw0 = [t.clone().requires_grad_(True) for t in gw]
-        wg0 = wg.clone().requires_grad_(True)
-        d_ref = O.scale_l2_convolution(c0, p0, ranges, S)
-        act_ref = O.distance_2_similarity(d_ref).permute(0, 2, 3, 1).reshape(-1, P)
-        units = torch.cat(O.compute_group(act_ref, ident, gw0), dim=-1)
-        l_ref = torch.nn.functional.linear(units, wg0)
-        (l_ref * g_logits.reshape(-1, K)).sum().backward()
-        wd = torch.zeros(U, P)
-        for k, i in enumerate(idx):
-            wd[k * G:(k + 1) * G, i] = gw[k]
-        wdd = wd.to(dev).requires_grad_(True)
-        wgd = wg.to(dev).requires_grad_(True)
-        logits, _, _, gact = proto_head_forward(x, pv, wdd, BankLayout(P, U, S, Cs, tuple(ranges[s] for s in range(S))),
-                                                want_distances=False, group_tail=wgd)
-        rl = l_ref.detach()
-        err = (logits.detach().cpu() - rl).abs().max().item()
-        assert err <= 1e-4 * max(1.0, rl.abs().max().item()), f"group logits err {err}"
-        (logits * g_logits.reshape(-1, K).to(dev)).sum().backward()
-        torch.cuda.synchronize()
-        _grad_close(wgd.grad, wg0.grad, "dLastLayerGroup")
-    _grad_close(x.grad, c0.grad, "dX", tol=dx_tol)
-    _grad_close(pv.grad, p0.grad, "dPrototypes")
-
+    check_random_gather_and_tail(seed)
 
 
 @pytest.mark.parametrize("tag", ["a", "b", "c"])
@@ -813,7 +611,7 @@ def test_kld_kernels_match_reference_golden(golden, tag):
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.loss import class_slot_table, gather_class_distances
 
-    dev = _dev()
+    dev = gpu_device()
     g = golden("kld_loss")
     t = torch.from_numpy(g[f"{tag}_target"])
     ident = torch.from_numpy(g[f"{tag}_ident"])
@@ -851,10 +649,10 @@ def test_kld_kernels_large_random():
     independent slot planes (loss about 1e-8: the value assertion cannot fail there) and on tests/kld_cases.py's correlated ones."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     P, K, S, H, W = 190, 19, 1, 512, 1024
     ident = O.default_class_identity(P, K, S)
-    lay = _layout(P, K, S, 16, O.default_scale_ranges(P, S))
+    lay = bank_layout(P, K, S, 16, O.default_scale_ranges(P, S))
     keys, J, table = spx.class_gather_table(lay, ident, dev)
     for planes in ("independent", "correlated"):
         gen = torch.Generator(device=dev).manual_seed(5)
@@ -888,11 +686,11 @@ def test_kld_kernels_with_the_ade_and_coco_class_counts(K, per):
     backend there).  Value and gradient against the oracle's torch restatement in fp64, on the crops those configs train on."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     P, S, B, H, W = K * per, 4, 2, 33, 65
     ident = O.default_class_identity(P, K, S)
     ranges = O.default_scale_ranges(P, S)
-    lay = _layout(P, K if K <= 160 else 1, S, 16, ranges)       # (more than 160 classes: the head is not in the plan, as in the module)
+    lay = bank_layout(P, K if K <= 160 else 1, S, 16, ranges)       # (more than 160 classes: the head is not in the plan, as in the module)
     keys, J, table = spx.class_gather_table(lay, ident, dev)
     assert J == per
     gen = torch.Generator(device=dev).manual_seed(11)
@@ -923,7 +721,7 @@ def test_kld_group_kernels_match_reference_golden(golden):
     KLDLossGroup value and gradients (segmentation/model/loss.py:461-545), run-to-run bit-identical."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = golden("kld_loss")
     n = int(g["grp_n"])
     t = torch.from_numpy(g["grp_target"]).to(dev)
@@ -952,10 +750,10 @@ def test_kld_kernels_ragged_grids(H, W):
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd import loss as L
 
-    dev = _dev()
+    dev = gpu_device()
     P, K, S = 60, 6, 1
     ident = O.default_class_identity(P, K, S)
-    lay = _layout(P, K, S, 16, O.default_scale_ranges(P, S))
+    lay = bank_layout(P, K, S, 16, O.default_scale_ranges(P, S))
     keys, J, table = spx.class_gather_table(lay, ident, dev)
     gen = torch.Generator(device=dev).manual_seed(H * 1000 + W)
     t = torch.randint(0, K + 1, (2, (H + 7) // 8, (W + 15) // 16), device=dev, generator=gen).repeat_interleave(8, 1).repeat_interleave(16, 2)[:, :H, :W].contiguous()
@@ -989,7 +787,7 @@ def test_push_argmin_vector_path_edges(B, P, K, H, W, void):
     workgroup's span, no void class, a void class in the middle, exact ties - bit-exact against the oracle."""
     from scaleprotoseg_amd.functional import push_masked_argmin
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(B * 1000 + P)
     dist = torch.floor(torch.rand(B, P, H, W, generator=g) * 64) / 8          # many exact ties
     nlab = K if void is None else K + 1
@@ -1008,7 +806,7 @@ def test_push_argmin_full_size_against_torch():
     """North-star map size (190 x 1024 x 2048): the kernel against torch's masked min on the GPU (same fp32 arithmetic)."""
     from scaleprotoseg_amd.functional import push_masked_argmin
 
-    dev = _dev()
+    dev = gpu_device()
     P, K, H, W = 190, 19, 1024, 2048
     gen = torch.Generator(device=dev).manual_seed(3)
     dist = torch.rand(1, P, H, W, device=dev, generator=gen) * 40
@@ -1029,26 +827,6 @@ def test_push_argmin_full_size_against_torch():
         assert torch.equal(idx[:, sl], first)
 
 
-class _Guarded:
-    """A device buffer with guard bands on both sides: kernels get a pointer into the middle, the bands must stay intact."""
-    GUARD = 64 * 1024          # bytes each side
-
-    def __init__(self, nbytes, dev):
-        self.n = int(nbytes)
-        self.buf = torch.full((self.n + 2 * self.GUARD,), 0xA5, dtype=torch.uint8, device=dev)
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.GUARD
-
-    def body(self, dtype):
-        return self.buf[self.GUARD:self.GUARD + self.n].view(dtype)
-
-    def intact(self):
-        g = self.GUARD
-        return bool((self.buf[:g] == 0xA5).all()) and bool((self.buf[g + self.n:] == 0xA5).all())
-
-
 @pytest.mark.parametrize("seed", list(range(16)))
 def test_no_write_outside_the_output_buffers(seed):
     """Every output of the forward / pixel-side / bank-side backward / push through the C ABI, placed between guard
@@ -1058,10 +836,10 @@ def test_no_write_outside_the_output_buffers(seed):
     from scaleprotoseg_amd import _lib
     from scaleprotoseg_amd.functional import _Packs, BankLayout
 
-    dev = _dev()
+    dev = gpu_device()
     lib = _lib.load()
     rng = np.random.default_rng(3000 + seed)
-    B, S, Cs, per_scale, K, H, W = _random_case(rng)
+    B, S, Cs, per_scale, K, H, W = random_case(rng)
     P, HW, C = sum(per_scale), H * W, S * Cs
     ranges, lo = [], 0
     for n in per_scale:
@@ -1079,24 +857,24 @@ def test_no_write_outside_the_output_buffers(seed):
     head = torch.randn(K, P, device=dev, generator=g) * 0.1
     packs = _Packs(plan, bank, head, True)
     s = _lib.stream_ptr()
-    dist, act, logits = _Guarded(B * P * HW * 4, dev), _Guarded(B * HW * P * 4, dev), _Guarded(B * HW * K * 4, dev)
+    dist, act, logits = Guarded(B * P * HW * 4, dev), Guarded(B * HW * P * 4, dev), Guarded(B * HW * K * 4, dev)
     _lib.check(lib.spx_dist_fwd(pp, _lib.ptr(x), 1 if xf32 else 0, B, HW, _lib.ptr(packs.bank), _lib.ptr(packs.p2), _lib.ptr(packs.head),
                                 dist.ptr, act.ptr, logits.ptr, 1e-4, 0, s))
     scr = lib.spx_bwd_scratch_bytes(pp, B, HW)
-    dx, gs, as_ = _Guarded(B * C * HW * esz, dev), _Guarded(scr, dev), _Guarded(lib.spx_bwd_head_scratch_bytes(pp, B, HW), dev)
+    dx, gs, as_ = Guarded(B * C * HW * esz, dev), Guarded(scr, dev), Guarded(lib.spx_bwd_head_scratch_bytes(pp, B, HW), dev)
     n_acc = lib.spx_bwd_dx_scratch_bytes(pp, 1 if xf32 else 0, B, HW)
-    dacc = _Guarded(n_acc, dev) if n_acc else None
+    dacc = Guarded(n_acc, dev) if n_acc else None
     gd = torch.randn(B, P, HW, device=dev, generator=g) * 1e-3
     ga = torch.randn(B * HW, P, device=dev, generator=g) * 1e-3
     gl = torch.randn(B * HW, K, device=dev, generator=g) * 1e-3
     _lib.check(lib.spx_dist_bwd(pp, _lib.ptr(x), 1 if xf32 else 0, B, HW, _lib.ptr(packs.bank), _lib.ptr(packs.bankT), _lib.ptr(packs.p2),
                                 _lib.ptr(packs.headT), _lib.ptr(gd), _lib.ptr(ga), _lib.ptr(gl), dx.ptr, dacc.ptr if dacc else None, gs.ptr,
                                 as_.ptr, 1e-4, 0, s))
-    ws = _Guarded(lib.spx_bank_bwd_workspace_bytes(pp, B, HW), dev)
-    d_bank, d_head = _Guarded(P * Cs * 4, dev), _Guarded(K * P * 4, dev)
+    ws = Guarded(lib.spx_bank_bwd_workspace_bytes(pp, B, HW), dev)
+    d_bank, d_head = Guarded(P * Cs * 4, dev), Guarded(K * P * 4, dev)
     _lib.check(lib.spx_bank_bwd(pp, _lib.ptr(x), 1 if xf32 else 0, B, HW, _lib.ptr(bank), gs.ptr, as_.ptr, _lib.ptr(gl), d_bank.ptr,
                                 d_head.ptr, ws.ptr, s))
-    idx, val, scratch = _Guarded(B * P * 8, dev), _Guarded(B * P * 4, dev), _Guarded(B * P * 8, dev)
+    idx, val, scratch = Guarded(B * P * 8, dev), Guarded(B * P * 4, dev), Guarded(B * P * 8, dev)
     labels = torch.randint(0, K + 1, (B, HW), device=dev, generator=g, dtype=torch.int32)
     ident = torch.zeros(P, K, device=dev)
     ident[torch.arange(P), torch.arange(P) % K] = 1
@@ -1120,7 +898,7 @@ def test_no_write_outside_the_output_buffers_extended_ops(seed):
     from scaleprotoseg_amd import _lib
     from scaleprotoseg_amd.functional import _Packs, BankLayout, class_gather_table
 
-    dev = _dev()
+    dev = gpu_device()
     lib = _lib.load()
     rng = np.random.default_rng(4000 + seed)
     S = int(rng.choice([1, 2, 4]))
@@ -1143,40 +921,40 @@ def test_no_write_outside_the_output_buffers_extended_ops(seed):
     packs = _Packs(plan, bank, head, True)
     labels = torch.randint(-1, K, (B, HW), device=dev, generator=g, dtype=torch.int32)
     s = _lib.stream_ptr()
-    cd, logits = _Guarded(B * J * HW * 4, dev), _Guarded(B * HW * K * 4, dev)
+    cd, logits = Guarded(B * J * HW * 4, dev), Guarded(B * HW * K * 4, dev)
     cd.body(torch.float32).zero_()
     _lib.check(lib.spx_dist_fwd_cls(pp, _lib.ptr(x), 0, B, HW, _lib.ptr(packs.bank), _lib.ptr(packs.p2), _lib.ptr(packs.head),
                                     _lib.ptr(labels), _lib.ptr(keys), J, cd.ptr, None, logits.ptr, 1e-4, 0, s))
     scr = lib.spx_bwd_scratch_bytes(pp, B, HW)
-    dx, gs, as_ = _Guarded(B * C * HW * 2, dev), _Guarded(scr, dev), _Guarded(lib.spx_bwd_head_scratch_bytes(pp, B, HW), dev)
+    dx, gs, as_ = Guarded(B * C * HW * 2, dev), Guarded(scr, dev), Guarded(lib.spx_bwd_head_scratch_bytes(pp, B, HW), dev)
     n_acc = lib.spx_bwd_dx_scratch_bytes(pp, 0, B, HW)
-    dacc = _Guarded(n_acc, dev) if n_acc else None
+    dacc = Guarded(n_acc, dev) if n_acc else None
     gcd = torch.randn(B, J, HW, device=dev, generator=g) * 1e-3
     gl = torch.randn(B * HW, K, device=dev, generator=g) * 1e-3
     _lib.check(lib.spx_dist_bwd_cls(pp, _lib.ptr(x), 0, B, HW, _lib.ptr(packs.bank), _lib.ptr(packs.bankT), _lib.ptr(packs.p2),
                                     _lib.ptr(packs.headT), _lib.ptr(labels), _lib.ptr(keys), J, _lib.ptr(gcd), None, _lib.ptr(gl),
                                     dx.ptr, dacc.ptr if dacc else None, gs.ptr, as_.ptr, 1e-4, 0, s))
     # KLD passes on the gathered planes
-    kk, cnt, ssum = _Guarded(B * K * J * 4, dev), _Guarded(B * K * 4, dev), _Guarded(B * K * J * 8, dev)
-    lse, afx, grad = _Guarded(B * K * J * 4, dev), _Guarded(B * K * J * J * 8, dev), _Guarded(B * J * HW * 4, dev)
+    kk, cnt, ssum = Guarded(B * K * J * 4, dev), Guarded(B * K * 4, dev), Guarded(B * K * J * 8, dev)
+    lse, afx, grad = Guarded(B * K * J * 4, dev), Guarded(B * K * J * J * 8, dev), Guarded(B * J * HW * 4, dev)
     for z in (kk, cnt, ssum, afx):
         z.body(torch.uint8).zero_()
     Wk = W if seed % 2 else 0
-    rngk, scale = _Guarded(8, dev), _Guarded(8, dev)
+    rngk, scale = Guarded(8, dev), Guarded(8, dev)
     rngk.body(torch.uint8).zero_()
     _lib.check(lib.spx_kld_segment_max(cd.ptr, _lib.ptr(labels), B, J, HW, Wk, K, kk.ptr, cnt.ptr, rngk.ptr, s))
     _lib.check(lib.spx_kld_segment_sumexp(cd.ptr, _lib.ptr(labels), B, J, HW, Wk, K, kk.ptr, ssum.ptr, s))
     _lib.check(lib.spx_kld_segment_lse(kk.ptr, ssum.ptr, B * K * J, lse.ptr, rngk.ptr, HW, scale.ptr, s))
     _lib.check(lib.spx_kld_pair_sums(cd.ptr, _lib.ptr(labels), B, J, HW, Wk, K, lse.ptr, scale.ptr, afx.ptr, s))
-    A, E, Cf, kloss = (_Guarded(B * K * J * J * 4, dev), _Guarded(B * K * 2 * 8, dev), _Guarded(B * K * J * J * 4, dev),
-                       _Guarded(8, dev))
+    A, E, Cf, kloss = (Guarded(B * K * J * J * 4, dev), Guarded(B * K * 2 * 8, dev), Guarded(B * K * J * J * 4, dev),
+                       Guarded(8, dev))
     pair_ok = torch.triu(torch.ones(J, J, dtype=torch.uint8, device=dev), diagonal=1).repeat(K, 1, 1).contiguous()
     _lib.check(lib.spx_kld_gram_loss(afx.ptr, scale.ptr, cnt.ptr, _lib.ptr(pair_ok), B * K, K, J, A.ptr, Cf.ptr, E.ptr, kloss.ptr, s))
     _lib.check(lib.spx_kld_backward(cd.ptr, _lib.ptr(labels), B, J, HW, K, lse.ptr, A.ptr, Cf.ptr, kloss.ptr + 4, grad.ptr, s))
     # evaluation map: upsample the small map by a non-integer factor
     Ho, Wo = int(rng.integers(H, 5 * H + 3)), int(rng.integers(W, 5 * W + 3))
     src = torch.rand(B, P, H, W, device=dev, generator=g)
-    eidx, eval_ = _Guarded(B * Ho * Wo * 8, dev), _Guarded(B * Ho * Wo * 4, dev)
+    eidx, eval_ = Guarded(B * Ho * Wo * 8, dev), Guarded(B * Ho * Wo * 4, dev)
     _lib.check(lib.spx_upsample_argext(_lib.ptr(src), B, P, H, W, Ho, Wo, 0, eidx.ptr, eval_.ptr, s))
     torch.cuda.synchronize()
     tag = f"B{B} S{S} Cs{Cs} P{P} K{K} J{J} {H}x{W} -> {Ho}x{Wo}"
@@ -1211,7 +989,7 @@ def test_hip_graph_capture_replay():
     from scaleprotoseg_amd.functional import proto_head_forward
     from scaleprotoseg_amd.graphs import capture_step
 
-    dev = _dev()
+    dev = gpu_device()
     x, bank, head, lay, gl, gd = _graph_problem(dev)
     leaves = (x, bank, head)
 
@@ -1256,16 +1034,16 @@ def test_features_beyond_the_fp16_range_give_finite_prototype_gradients(hw):
     in every prototype gradient)."""
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K = 1, 1, 128, 40, 5
     H, W = hw
-    conv, bank, Wl, ident, ranges = _problem(B, S, Cs, P, K, H, W, seed=4)
+    conv, bank, Wl, ident, ranges = problem(B, S, Cs, P, K, H, W, seed=4)
     conv[0, 3, 1, 2] = 1.0e5
     conv[0, 70, 0, 0] = -3.0e5
     x = conv.to(dev, torch.bfloat16)
     pv = bank.to(dev).requires_grad_(True)
     w = Wl.to(dev).requires_grad_(True)
-    logits, dist, _ = proto_head_forward(x, pv, w, _layout(P, K, S, Cs, ranges), want_distances=True)
+    logits, dist, _ = proto_head_forward(x, pv, w, bank_layout(P, K, S, Cs, ranges), want_distances=True)
     g = torch.Generator().manual_seed(3)
     ((logits * (torch.randn(B * H * W, K, generator=g) * 1e-3).to(dev)).sum() + (dist * 1e-9).sum()).backward()
     assert torch.isfinite(pv.grad).all() and torch.isfinite(w.grad).all()
@@ -1277,10 +1055,10 @@ def test_eager_forward_after_graph_replays_sees_the_updated_parameters():
     from scaleprotoseg_amd.functional import proto_head_forward
     from scaleprotoseg_amd.graphs import capture_step
 
-    dev = _dev()
+    dev = gpu_device()
     B, S, Cs, P, K, H, W = 1, 1, 32, 40, 5, 8, 16
-    conv, bank, Wl, ident, ranges = _problem(B, S, Cs, P, K, H, W, seed=9)
-    lay = _layout(P, K, S, Cs, ranges)
+    conv, bank, Wl, ident, ranges = problem(B, S, Cs, P, K, H, W, seed=9)
+    lay = bank_layout(P, K, S, Cs, ranges)
     x = conv.to(dev)
     pv = bank.to(dev).requires_grad_(True)
     w = Wl.to(dev).requires_grad_(True)
@@ -1316,7 +1094,7 @@ def test_capture_step_refuses_a_stale_default_stream_graph():
     from scaleprotoseg_amd.functional import proto_head_forward
     from scaleprotoseg_amd.graphs import capture_step
 
-    dev = _dev()
+    dev = gpu_device()
     x, bank, head, lay, gl, gd = _graph_problem(dev)
 
     def step():
@@ -1345,7 +1123,7 @@ def test_pixel_outer_kernel(M, n1, n2):
     """spx_pixel_outer (d W_g = d_logits^T . g of the grouping tail) against an fp64 product; run-to-run identical."""
     from scaleprotoseg_amd.functional import _pixel_outer
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(M + n1)
     a = torch.randn(M, n1, generator=g).to(dev)
     b = torch.rand(M, n2, generator=g).to(dev) * 3
@@ -1362,10 +1140,10 @@ def test_tiny_and_ragged_grids(H, W, x_dtype):
     """Images of fewer than 8 pixels (element-wise staging), exactly one piece, and ragged ends below one tile."""
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     shape = (2, 4, 16, 40, 5, H, W)
     B, S, Cs, P, K, _, _ = shape
-    conv, bank, Wl, ident, ranges = _problem(*shape, seed=5)
+    conv, bank, Wl, ident, ranges = problem(*shape, seed=5)
     g = torch.Generator().manual_seed(9)
     g_logits = torch.randn(B, H, W, K, generator=g) * 1e-3
     g_dist = torch.randn(B, P, H, W, generator=g) * 1e-3
@@ -1373,12 +1151,12 @@ def test_tiny_and_ragged_grids(H, W, x_dtype):
     x = conv.to(dev, x_dtype).requires_grad_(True)
     pv = bank.to(dev).requires_grad_(True)
     w = Wl.to(dev).requires_grad_(True)
-    logits, dist, _ = proto_head_forward(x, pv, w, _layout(P, K, S, Cs, ranges))
-    _assert_fwd(logits, dist, None, rl, rd, None)
+    logits, dist, _ = proto_head_forward(x, pv, w, bank_layout(P, K, S, Cs, ranges))
+    assert_fwd(logits, dist, None, rl, rd, None)
     torch.autograd.backward([logits, dist], [g_logits.reshape(-1, K).to(dev), g_dist.to(dev)])
-    _grad_close(x.grad, dx_ref, "dX", tol=_dx_tol(x_dtype, ranges))
-    _grad_close(pv.grad, dp_ref, "dPrototypes")
-    _grad_close(w.grad, dw_ref, "dLastLayer")
+    grad_close(x.grad, dx_ref, "dX", tol=dx_tolerance(x_dtype, ranges))
+    grad_close(pv.grad, dp_ref, "dPrototypes")
+    grad_close(w.grad, dw_ref, "dLastLayer")
 
 
 @pytest.mark.parametrize("B,H,W", [(300, 3, 5), (140, 9, 11), (37, 13, 21)])
@@ -1387,10 +1165,10 @@ def test_many_small_images(B, H, W):
     image; the position advances incrementally, spx_bank.hip) and every slab sums chunks of several images."""
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     shape = (B, 2, 16, 12, 3, H, W)
     _, S, Cs, P, K, _, _ = shape
-    conv, bank, Wl, ident, ranges = _problem(*shape, seed=8)
+    conv, bank, Wl, ident, ranges = problem(*shape, seed=8)
     g = torch.Generator().manual_seed(10)
     g_logits = torch.randn(B, H, W, K, generator=g) * 1e-3
     g_dist = torch.randn(B, P, H, W, generator=g) * 1e-3
@@ -1398,12 +1176,12 @@ def test_many_small_images(B, H, W):
     x = conv.to(dev, torch.bfloat16).requires_grad_(True)
     pv = bank.to(dev).requires_grad_(True)
     w = Wl.to(dev).requires_grad_(True)
-    logits, dist, _ = proto_head_forward(x, pv, w, _layout(P, K, S, Cs, ranges))
-    _assert_fwd(logits, dist, None, rl, rd, None)
+    logits, dist, _ = proto_head_forward(x, pv, w, bank_layout(P, K, S, Cs, ranges))
+    assert_fwd(logits, dist, None, rl, rd, None)
     torch.autograd.backward([logits, dist], [g_logits.reshape(-1, K).to(dev), g_dist.to(dev)])
-    _grad_close(x.grad, dx_ref, "dX", tol=_dx_tol(torch.bfloat16, ranges))
-    _grad_close(pv.grad, dp_ref, "dPrototypes")
-    _grad_close(w.grad, dw_ref, "dLastLayer")
+    grad_close(x.grad, dx_ref, "dX", tol=dx_tolerance(torch.bfloat16, ranges))
+    grad_close(pv.grad, dp_ref, "dPrototypes")
+    grad_close(w.grad, dw_ref, "dLastLayer")
 
 
 @pytest.mark.parametrize("x_dtype,offset", [(torch.bfloat16, 1), (torch.bfloat16, 3), (torch.float32, 1)])
@@ -1412,10 +1190,10 @@ def test_features_at_an_unaligned_address(x_dtype, offset):
     takes any alignment (gfx950 serves misaligned 16-B buffer accesses)."""
     from scaleprotoseg_amd.functional import proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     shape = (1, 1, 64, 210, 21, 8, 16)
     B, S, Cs, P, K, H, W = shape
-    conv, bank, Wl, ident, ranges = _problem(*shape, seed=6)
+    conv, bank, Wl, ident, ranges = problem(*shape, seed=6)
     g = torch.Generator().manual_seed(4)
     g_logits = torch.randn(B, H, W, K, generator=g) * 1e-3
     g_dist = torch.randn(B, P, H, W, generator=g) * 1e-3
@@ -1426,12 +1204,12 @@ def test_features_at_an_unaligned_address(x_dtype, offset):
     assert x.data_ptr() % 16 != 0
     pv = bank.to(dev).requires_grad_(True)
     w = Wl.to(dev).requires_grad_(True)
-    logits, dist, _ = proto_head_forward(x, pv, w, _layout(P, K, S, Cs, ranges))
-    _assert_fwd(logits, dist, None, rl, rd, None)
+    logits, dist, _ = proto_head_forward(x, pv, w, bank_layout(P, K, S, Cs, ranges))
+    assert_fwd(logits, dist, None, rl, rd, None)
     gx, gp, gw = torch.autograd.grad([logits, dist], [x, pv, w], [g_logits.reshape(-1, K).to(dev), g_dist.to(dev)])
-    _grad_close(gx, dx_ref, "dX", tol=_dx_tol(x_dtype, ranges))
-    _grad_close(gp, dp_ref, "dPrototypes")
-    _grad_close(gw, dw_ref, "dLastLayer")
+    grad_close(gx, dx_ref, "dX", tol=dx_tolerance(x_dtype, ranges))
+    grad_close(gp, dp_ref, "dPrototypes")
+    grad_close(gw, dw_ref, "dLastLayer")
 
 
 @pytest.mark.parametrize("P,K,S,Cs,K2", [(190, 19, 1, 256, 0), (228, 57, 4, 64, 19), (1800, 150, 4, 64, 0), (37, 9, 2, 48, 5), (64, 0, 1, 64, 0)])
@@ -1442,7 +1220,7 @@ def test_pack_all_equals_the_single_pack_calls(P, K, S, Cs, K2):
     from scaleprotoseg_amd import _lib
     from scaleprotoseg_amd.functional import BankLayout
 
-    dev = _dev()
+    dev = gpu_device()
     lib = _lib.load()
     g = torch.Generator().manual_seed(P + K)
     per = P // S
@@ -1497,7 +1275,7 @@ def test_gathered_forward_writes_every_slot_of_uninitialised_planes(S, H, W):
     from scaleprotoseg_amd import _lib
     from scaleprotoseg_amd.functional import BankLayout, _Packs, class_gather_table
 
-    dev = _dev()
+    dev = gpu_device()
     lib = _lib.load()
     K, Cs, B = 4, 32, 2
     per_scale = [0, 0, 0, 1, 1, 2]                       # classes of a scale's 6 prototypes: class 3 has none
@@ -1521,8 +1299,9 @@ def test_gathered_forward_writes_every_slot_of_uninitialised_planes(S, H, W):
     packs = _Packs(plan, bank.to(dev), head.to(dev), False)
     cd = torch.full((B, J, HW), float("nan"), device=dev)
     logits = torch.empty(B * HW, K, device=dev)
-    _lib.check(lib.spx_dist_fwd_cls(pp, _lib.ptr(x.to(dev)), 0, B, HW, _lib.ptr(packs.bank), _lib.ptr(packs.p2), _lib.ptr(packs.head),
-                                    _lib.ptr(labels.to(dev)), _lib.ptr(keys), J, _lib.ptr(cd), None, _lib.ptr(logits), 1e-4, 0,
+    x_dev, labels_dev = x.to(dev), labels.to(dev)          # alive until the kernel is done: the call takes bare addresses
+    _lib.check(lib.spx_dist_fwd_cls(pp, _lib.ptr(x_dev), 0, B, HW, _lib.ptr(packs.bank), _lib.ptr(packs.p2), _lib.ptr(packs.head),
+                                    _lib.ptr(labels_dev), _lib.ptr(keys), J, _lib.ptr(cd), None, _lib.ptr(logits), 1e-4, 0,
                                     _lib.stream_ptr()))
     torch.cuda.synchronize()
     _, d_ref, _ = O.forward_from_conv_features(x.float().reshape(B, S * Cs, H, W), bank.reshape(P, Cs, 1, 1), ranges, S, head)
@@ -1545,7 +1324,7 @@ def test_group_tail_with_cross_entropy_at_the_widest_heads(P, S, Cs, U, K2, B, H
     model_multiscale_group.py:303-308 + loss.py:9-48 on the same bf16-representable inputs; every gradient finite."""
     from scaleprotoseg_amd.functional import BankLayout, proto_head_forward
 
-    dev = _dev()
+    dev = gpu_device()
     torch.manual_seed(P + U)
     x = torch.sigmoid(torch.randn(B, S * Cs, H, W, device=dev)).bfloat16().requires_grad_(True)
     bank = torch.rand(P, Cs, 1, 1, device=dev).bfloat16().float().requires_grad_(True)

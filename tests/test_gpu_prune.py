@@ -18,48 +18,15 @@ import pytest
 import torch
 import torch.nn as nn
 
+from support import Backbone, ListData, proto_net
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 
 
-class _Identity(nn.Module):
-    """Backbone stand-in: the dataset's 'images' are the features ([S*Cs, H, W]); ``str()`` starts with MSC as
-    model_multiscale.py:153-171 expects."""
-
-    def __init__(self, ch):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return x
-
-
-class _Data:
-    convert_targets = None
-
-    def __init__(self, items):
-        self.items = items
-
-    def __len__(self):
-        return len(self.items)
-
-    def __getitem__(self, i):
-        return self.items[i]
-
-
 def _net(S, K, per, Cs, seed=0):
-    import scaleprotoseg_amd as spx
-
-    torch.manual_seed(seed)
-    P = S * K * per
-    net = spx.PPNetMultiScale(_Identity(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S)
-    net.add_on_layers = nn.Sequential(nn.Sigmoid())
-    return net.to(DEV).eval()
+    return proto_net(S * K * per, K, S, Cs, seed=seed, add_on=nn.Sequential(nn.Sigmoid()), device=DEV).eval()
 
 
 def _targets(gen, Hf, Wf, K, block, void_frac=0.25):
@@ -77,7 +44,7 @@ def _dataset(n, C, H, W, Hf, Wf, K, seed, block=8, void_frac=0.25):
     for _ in range(n):
         x = torch.randn(C, H, W, generator=gen) * 2.0
         items.append((x, _targets(gen, Hf, Wf, K, block, void_frac)))
-    return _Data(items)
+    return ListData(items)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -461,7 +428,7 @@ def test_pruning_search_runs_on_ppnet_single_scale():
 
     torch.manual_seed(121)
     K, per, Cs = 4, 3, 16
-    net = spx.PPNet(_Identity(Cs), 64, (K * per, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple")
+    net = spx.PPNet(Backbone(Cs), 64, (K * per, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple")
     net.add_on_layers = nn.Sequential(nn.Sigmoid())
     net = net.to(DEV).eval()
     data = _dataset(5, Cs, 8, 8, 64, 64, K, seed=122)

@@ -21,23 +21,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import push_boxes_restatement as PB  # noqa: E402
-from test_push_boxes_cpu import CASES, classes_of, planes_of  # noqa: E402
+from map_cases import PUSH_BOX_CASES as CASES, classes_of, planes_of  # noqa: E402
+from support import gpu_device, ListData, proto_net  # noqa: E402
+from support import release_cached_blocks  # noqa: E402,F401  (a module-scoped autouse fixture, taken by importing its name)
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _release_cached_blocks():
-    yield
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-        torch.cuda.empty_cache()
 
 
 def _gpu(planes, labels, rows, dev, **kw):
@@ -62,7 +50,7 @@ def _compare(tag, rf, box, want_rf, want_box, robust, exact=False):
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_fixture_parity(name):
-    dev = _dev()
+    dev = gpu_device()
     c = CASES[name]
     planes, cls = planes_of(c), classes_of(c)
     P = planes.shape[1]
@@ -134,7 +122,7 @@ def _shape_case(name):
 
 @pytest.mark.parametrize("name", sorted(_SHAPES))
 def test_against_the_restatement(name):
-    dev = _dev()
+    dev = gpu_device()
     planes, labels, rows, want_rf, want_box, robust = _shape_case(name)
     H, W = labels.shape[1:]
     rf, box = _gpu(planes, labels, rows, dev)
@@ -150,7 +138,7 @@ def test_against_the_restatement(name):
 def test_strided_pixel_major_and_label_types_and_repeats():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     planes, labels, rows, _, _, _ = _shape_case("300_rows_3_images_repeated_channels")
     N, C, h, w = planes.shape
     p, l, r = torch.from_numpy(planes).to(dev), torch.from_numpy(labels).to(dev), torch.from_numpy(rows)
@@ -196,7 +184,7 @@ def test_inside_a_captured_step():
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd import graphs
 
-    dev = _dev()
+    dev = gpu_device()
     planes, labels, rows, _, _, _ = _shape_case("w50_shorter_than_a_wave")
     p, l, r = torch.from_numpy(planes).to(dev), torch.from_numpy(labels).to(dev), torch.from_numpy(rows).to(torch.int32).to(dev)
     thr = spx.high_activation_threshold(p, labels.shape[1:], 0.95)
@@ -211,37 +199,17 @@ def test_inside_a_captured_step():
 
 
 # ---- the module, end to end ---------------------------------------------------------------------------------------------
-class _Backbone(nn.Module):
-    def __init__(self, ch, stride=4):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-        self.pool = nn.AvgPool2d(stride)
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return self.base(self.pool(x))
-
-
-class _Data(list):
-    convert_targets = None
 
 
 def test_push_prototypes_multiscale_with_boxes(tmp_path):
-    import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.push import push_prototypes_multiscale
 
-    dev = _dev()
+    dev = gpu_device()
     S, Cs, K, per = 2, 16, 3, 2
     P = S * K * per
-    torch.manual_seed(11)
-    net = spx.PPNetMultiScale(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S)
-    net.add_on_layers = nn.Sequential(nn.Sigmoid())
-    net = net.to(dev).eval()
+    net = proto_net(P, K, S, Cs, seed=11, backbone="pool", add_on=nn.Sequential(nn.Sigmoid()), device=dev).eval()
     gen = torch.Generator().manual_seed(12)
-    data = _Data()
+    data = ListData()
     H, W = 40, 56
     for _ in range(3):
         t = torch.randint(0, K + 1, (5, 7), generator=gen).repeat_interleave(8, 0).repeat_interleave(8, 1)

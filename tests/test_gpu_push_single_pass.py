@@ -1,7 +1,6 @@
 """The single-pass batched push on the GPU: spx_push_merge against its restatement (tests/push_merge_restatement.py), and the
 pipeline push_prototypes_multiscale(batch_size=...) against the two-pass push (batch_size=None, the path this change leaves as
 it was), in one process and sharded over two ranks.  Everything is an equality of bits."""
-import json
 import os
 import sys
 
@@ -16,6 +15,8 @@ if HERE not in sys.path:
 import push_merge_restatement as R  # noqa: E402
 from scaleprotoseg_amd import PushTable, push_single_pass  # noqa: E402,F401  (the feature under test: no test here runs without it)
 from scaleprotoseg_amd import push as push_mod  # noqa: E402
+from push_cases import bf16_bank_with_a_duplicate, push_problem, push_state, same_push_state  # noqa: E402
+from support import RoundBf16, gpu_device, proto_net, run_gloo  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -28,12 +29,6 @@ _TWO_PASS_STEPS = dict(compute_distances=push_mod.compute_distances, argmin_over
 def _product_steps(monkeypatch):
     for name, fn in _TWO_PASS_STEPS.items():
         monkeypatch.setattr(push_mod, name, fn)
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
 
 
 # ---- the kernel against the restatement --------------------------------------------------------------------------------
@@ -59,6 +54,7 @@ def _batch(g, B, P, S, Cs, H, W, dtype):
     return idx, val, x
 
 
+# (local: the bits of a float32 tensor, integer tensors as they are - not support.bits_equal, which takes two floats)
 def _bits(t):
     return t.view(torch.int32) if t.dtype == torch.float32 else t
 
@@ -73,7 +69,7 @@ def _same_table(table, state, tag):
 def test_kernel_equals_the_restatement(name):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, P, S, Cs, H, W, dtype, image0 = CASES[name]
     g = torch.Generator().manual_seed(sorted(CASES).index(name))
     if name == "ragged":
@@ -97,7 +93,7 @@ def test_kernel_equals_the_restatement(name):
 def test_a_batch_that_improves_nothing_writes_nothing():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     B, P, S, Cs, H, W = 6, 37, 2, 24, 4, 5
     g = torch.Generator().manual_seed(9)
     table = spx.PushTable(P, Cs, dev)
@@ -146,39 +142,16 @@ class _FeatureData:
         return self.items[i]
 
 
+# (local: a module and a data set, not the operator inputs of parity_cases.problem)
 def _problem(dev, sizes, seed=3, fractional=False):
-    """A net built like tests/test_gpu_modules.py::_push_problem (forced duplicate, absent class), identity backbone."""
-    import scaleprotoseg_amd as spx
-    from oracle import ppnet_oracle as O
-    from test_gpu_modules import _Backbone, _RoundBf16
-
-    torch.manual_seed(seed)
-    net = spx.PPNetMultiScale(_Backbone(S_ * CS_, mode="identity"), 64, (P_, CS_, 1, 1), [], K_,
-                              add_on_layers_type="deeplab_simple", patch_classification=True, num_scales=S_)
-    net.add_on_layers = nn.Sequential(nn.Sigmoid(), _RoundBf16())
-    with torch.no_grad():
-        net.prototype_vectors.copy_(O.bf16_representable(net.prototype_vectors.data))
-        net.prototype_vectors[1].copy_(net.prototype_vectors[0])          # forced duplicate
+    """A net built like push_cases.push_problem (forced duplicate, absent class), identity backbone."""
+    net = proto_net(P_, K_, S_, CS_, seed=seed, add_on=nn.Sequential(nn.Sigmoid(), RoundBf16()), init=bf16_bank_with_a_duplicate)
     if fractional:                                                          # not one-hot: the written map + push_masked_argmin
         ident = net.prototype_class_identity.clone()
         ident[4] = 0.0
         ident[4, 0] = ident[4, 1] = 0.5
         net.prototype_class_identity = ident
     return net.to(dev), _FeatureData(sizes, seed + 1)
-
-
-def _state(net, root=None):
-    out = dict(bank=net.prototype_vectors.detach().cpu(), ranges={s: tuple(net.scale_num_prototypes[s]) for s in range(S_)},
-               last=net.last_layer.weight.detach().cpu(), ident=net.prototype_class_identity.cpu().clone())
-    if root is not None:
-        out["json"] = json.load(open(os.path.join(root, "unique_prototypes.json")))
-    return out
-
-
-def _same_state(a, b):
-    for k in ("bank", "last", "ident"):
-        assert a[k].shape == b[k].shape and torch.equal(a[k], b[k]), k
-    assert a["ranges"] == b["ranges"] and a.get("json") == b.get("json")
 
 
 _two_pass_cache = {}
@@ -192,7 +165,7 @@ def _two_pass(dev, key, tmp_root, **kw):
         best, list_idx, dup = push_mod.push_prototypes_multiscale(data, net, root, log=lambda *_: None)
         assert isinstance(list_idx, list)
         flat = torch.cat(list_idx)[best, torch.arange(P_, device=best.device)]
-        _two_pass_cache[key] = (_state(net, root), best.cpu(), flat.cpu(), list(dup))
+        _two_pass_cache[key] = (push_state(net, root), best.cpu(), flat.cpu(), list(dup))
     return _two_pass_cache[key]
 
 
@@ -203,7 +176,7 @@ def shared_tmp(tmp_path_factory):
 
 @pytest.mark.parametrize("batch", [1, 2, 3, 64])
 def test_pipeline_equals_the_two_pass_push(shared_tmp, tmp_path, batch):
-    dev = _dev()
+    dev = gpu_device()
     want, best0, flat0, dup0 = _two_pass(dev, "same", os.path.join(shared_tmp, "same"), sizes=SAME)
     assert 1 in dup0
     net, data = _problem(dev, sizes=SAME)
@@ -211,7 +184,7 @@ def test_pipeline_equals_the_two_pass_push(shared_tmp, tmp_path, batch):
     best, flat, dup = push_mod.push_prototypes_multiscale(data, net, str(tmp_path), log=lambda *_: None, batch_size=batch)
     assert isinstance(flat, torch.Tensor) and flat.dtype == torch.int64 and tuple(flat.shape) == (P_,)
     assert torch.equal(best.cpu(), best0) and torch.equal(flat.cpu(), flat0) and list(dup) == dup0
-    _same_state(_state(net, str(tmp_path)), want)
+    same_push_state(push_state(net, str(tmp_path)), want)
     assert len(absent) == S_ * PER_
     for p in absent:                                                        # value 1e10 in every image: image 0, flat 0
         assert int(best[p]) == 0 and int(flat[p]) == 0
@@ -219,19 +192,19 @@ def test_pipeline_equals_the_two_pass_push(shared_tmp, tmp_path, batch):
 
 @pytest.mark.parametrize("batch", [2, 3])
 def test_pipeline_with_mixed_image_sizes(shared_tmp, tmp_path, batch):
-    dev = _dev()
+    dev = gpu_device()
     want, best0, flat0, dup0 = _two_pass(dev, "mixed", os.path.join(shared_tmp, "mixed"), sizes=MIXED)
     net, data = _problem(dev, sizes=MIXED)
     best, flat, dup = push_mod.push_prototypes_multiscale(data, net, str(tmp_path), log=lambda *_: None, batch_size=batch)
     assert torch.equal(best.cpu(), best0) and torch.equal(flat.cpu(), flat0) and list(dup) == dup0
     assert len(set(best0.tolist())) > 2 and int(best0.max()) >= 2           # winners beyond the first run: global indices
-    _same_state(_state(net, str(tmp_path)), want)
+    same_push_state(push_state(net, str(tmp_path)), want)
 
 
 def test_a_fractional_identity_row_takes_the_map_path(shared_tmp, tmp_path):
     from scaleprotoseg_amd.functional import identity_is_one_hot
 
-    dev = _dev()
+    dev = gpu_device()
     want, best0, flat0, dup0 = _two_pass(dev, "fractional", os.path.join(shared_tmp, "fractional"), sizes=MIXED, fractional=True)
     net, data = _problem(dev, sizes=MIXED, fractional=True)
     assert not identity_is_one_hot(net.prototype_class_identity)
@@ -241,25 +214,23 @@ def test_a_fractional_identity_row_takes_the_map_path(shared_tmp, tmp_path):
     best, flat, dup = push_mod.push_prototypes_multiscale(data, net, str(tmp_path), log=lambda *_: None, batch_size=3)
     assert fused and all(f is None for f in fused)                          # every run went through the written map
     assert torch.equal(best.cpu(), best0) and torch.equal(flat.cpu(), flat0) and list(dup) == dup0
-    _same_state(_state(net, str(tmp_path)), want)
+    same_push_state(push_state(net, str(tmp_path)), want)
 
 
 def test_pool_backbone_at_batch_size_one(tmp_path):
     """The stand-in's 1x1 convolutions may round differently per batch shape, so only batch_size=1 is comparable."""
-    from test_gpu_modules import _push_problem
-
-    dev = _dev()
-    net0, data, P = _push_problem(dev)
+    dev = gpu_device()
+    net0, data, P = push_problem(dev)
     best0, list_idx, dup0 = push_mod.push_prototypes_multiscale(data, net0, str(tmp_path / "two"), log=lambda *_: None)
-    net1, _, _ = _push_problem(dev)
+    net1, _, _ = push_problem(dev)
     best1, flat1, dup1 = push_mod.push_prototypes_multiscale(data, net1, str(tmp_path / "one"), log=lambda *_: None, batch_size=1)
     assert torch.equal(best1, best0) and list(dup1) == list(dup0)
     assert torch.equal(flat1, torch.cat(list_idx)[best0, torch.arange(P, device=best0.device)])
-    _same_state(_state(net1, str(tmp_path / "one")), _state(net0, str(tmp_path / "two")))
+    same_push_state(push_state(net1, str(tmp_path / "one")), push_state(net0, str(tmp_path / "two")))
 
 
 def test_boxes_with_and_without_batching(tmp_path):
-    dev = _dev()
+    dev = gpu_device()
     net0, data = _problem(dev, sizes=MIXED)
     out0 = push_mod.push_prototypes_multiscale(data, net0, str(tmp_path / "two"), log=lambda *_: None, boxes=True,
                                                epoch_number=3, proto_bound_boxes_filename_prefix="bb")
@@ -269,25 +240,24 @@ def test_boxes_with_and_without_batching(tmp_path):
     assert len(out0) == len(out1) == 5 and torch.equal(out1[0], out0[0]) and list(out1[2]) == list(out0[2])
     assert out1[3].dtype == np.int64 and np.array_equal(out1[3], out0[3]) and np.array_equal(out1[4], out0[4])
     assert (out1[3][:, 0] == out0[0].cpu().numpy()).all()
-    _same_state(_state(net1, str(tmp_path / "one")), _state(net0, str(tmp_path / "two")))
+    same_push_state(push_state(net1, str(tmp_path / "one")), push_state(net0, str(tmp_path / "two")))
     for name in ("bb-receptive_field3.npy", "bb3.npy"):
         a, b = (np.load(os.path.join(str(tmp_path / d), "epoch-3", name)) for d in ("one", "two"))
         assert np.array_equal(a, b)
 
 
 # ---- sharded: two ranks on one GPU -------------------------------------------------------------------------------------
+# (what one rank runs in this file's sharded test; support.run_gloo spawns it)
 def _dp_case(rank, world):
     net, data = _problem(torch.device("cuda:0"), sizes=MIXED)
     best, flat, dup = push_mod.push_prototypes_multiscale(data, net, log=lambda *_: None, batch_size=3)
-    return _state(net), best.cpu(), flat.cpu(), list(dup)
+    return push_state(net), best.cpu(), flat.cpu(), list(dup)
 
 
 def test_sharded_single_pass_on_the_kernels(shared_tmp, tmp_path):
-    from test_gpu_dp import _run
-
-    dev = _dev()
+    dev = gpu_device()
     want, best0, flat0, dup0 = _two_pass(dev, "mixed", os.path.join(shared_tmp, "mixed"), sizes=MIXED)
     want = {k: v for k, v in want.items() if k != "json"}
-    for state, best, flat, dup in _run(_dp_case, tmp_path):
-        _same_state(state, want)
+    for state, best, flat, dup in run_gloo(_dp_case, tmp_path, gpu=True):
+        same_push_state(state, want)
         assert torch.equal(best, best0) and torch.equal(flat, flat0) and dup == dup0

@@ -7,56 +7,14 @@ import pytest
 import torch
 import torch.nn as nn
 
-from test_regularizers_cpu import CASES, case_inputs, close, present_blocks, restate
+from regularizer_cases import CASES, case_inputs, check_against_f64, close, flat_grads, flat_weights, restate, zero_grads
+from support import gpu_device, group_net, proto_net
 
 pytestmark = pytest.mark.gpu
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.fail("needs an MI355X")
-    return torch.device("cuda:0")
-
-
-class _Features(nn.Module):
-    def __init__(self, ch):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-
-    def __str__(self):
-        return "MSC(stand-in)"
-
-
-def _group_net(P, K, S, G=3, Cs=16, seed=0):
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet
-
-    torch.manual_seed(seed)
-    net = GroupNet(_Features(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple", patch_classification=True,
-                   num_scales=S, num_groups=G)
-    net.add_on_layers = nn.Sequential()
-    return net
-
-
-def _proto_net(P, K, S, Cs=16):
-    from scaleprotoseg_amd.model_multiscale import PPNetMultiScale
-
-    net = PPNetMultiScale(_Features(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple", patch_classification=True,
-                          num_scales=S)
-    net.add_on_layers = nn.Sequential()
-    return net
-
-
-def _flat_weights(net):
-    return torch.cat([gp.weight.detach().reshape(-1) for gp in net.group_projection])
-
-
-def _flat_grads(net):
-    return torch.cat([gp.weight.grad.reshape(-1) for gp in net.group_projection])
-
-
-def _zero_grads(net):
-    for p in net.parameters():
-        p.grad = None
+def _group_net(P, K, S, G=3, seed=0):
+    return group_net(P, K, S, 16, G, seed=seed, add_on=nn.Sequential())
 
 
 def _net_from_case(z, name, dev):
@@ -75,7 +33,7 @@ def _net_from_case(z, name, dev):
         gp.weight.data.copy_(torch.from_numpy(w[off:off + n]).view_as(gp.weight))
         off += n
     net.last_layer_group.weight.data.copy_(torch.from_numpy(hg))
-    proto = _proto_net(P, K, S)
+    proto = proto_net(P, K, S, 16, add_on=nn.Sequential())
     proto.prototype_class_identity = ident.clone()
     proto.scale_num_prototypes = dict(scales)
     proto = proto.to(dev)
@@ -87,48 +45,24 @@ def _net_from_case(z, name, dev):
 def test_terms_match_reference_fixture(golden, name):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device(required=True)
     z = golden("group_regularizers")
     net, proto, eps = _net_from_case(z, name, dev)
     for key, mod in (("ent", spx.EntropyGroup(net, epsilon=eps)), ("ceg", spx.CrossEntropyGroup(net, epsilon=eps)),
                      ("sm", spx.ScaleMax(net))):
-        _zero_grads(net)
+        zero_grads(net)
         v = mod()
         assert v.shape == () and v.is_cuda
         v.backward()
         assert close(v.cpu(), z[f"{name}__{key}"], 1e-5), (name, key, v.item(), z[f"{name}__{key}"])
-        assert close(_flat_grads(net).cpu(), z[f"{name}__d_{key}"], 1e-5), (name, "d_" + key)
+        assert close(flat_grads(net).cpu(), z[f"{name}__d_{key}"], 1e-5), (name, "d_" + key)
     for key, m in (("l1_group", net), ("l1_proto", proto)):
-        _zero_grads(m)
+        zero_grads(m)
         v = spx.head_l1(m)
         v.backward()
         W = m.last_layer_group.weight if key == "l1_group" else m.last_layer.weight
         assert close(v.cpu(), z[f"{name}__{key}"], 1e-5), (name, key)
         assert close(W.grad.cpu(), z[f"{name}__d_{key}"], 1e-5), (name, "d_" + key)
-
-
-def _check_against_f64(net, reg, weights, eps):
-    """GroupRegularizers' total, terms and gradients against the float64 restatement: values within 1e-6 max(1, |ref|),
-    gradients within 1e-6 max|g|."""
-    _zero_grads(net)
-    total, terms = reg()
-    total.backward()
-    torch.cuda.synchronize()
-    ident = net.prototype_class_identity.cpu()
-    hg = net.last_layer_group.weight.detach().cpu().numpy()
-    r = restate(ident, net.scale_num_prototypes, net.num_groups, eps, _flat_weights(net).cpu().numpy(), hg,
-                np.zeros((ident.shape[1], ident.shape[0]), np.float32))
-    ref_terms = [r["ent"], r["ceg"], r["sm"], r["l1_group"]]
-    for i in range(4):
-        assert close(terms[i].cpu(), ref_terms[i], 1e-6), (i, terms[i].item(), ref_terms[i].item())
-    ref_total = ((weights[3] * ref_terms[3] + weights[1] * ref_terms[1]) + weights[2] * ref_terms[2]) + weights[0] * ref_terms[0]
-    assert close(total.cpu(), ref_total, 1e-6)
-    d_ref = sum(wt * r["d_" + k] for wt, k in zip(weights[:3], ("ent", "ceg", "sm")))
-    d_got = _flat_grads(net).cpu().double()
-    assert (d_got - d_ref).abs().max() <= 1e-6 * d_ref.abs().max(), (d_got - d_ref).abs().max()
-    dh_ref = weights[3] * r["d_l1_group"]
-    dh = net.last_layer_group.weight.grad.cpu().double()
-    assert (dh - dh_ref).abs().max() <= 1e-6 * dh_ref.abs().max()
 
 
 @pytest.mark.parametrize("P,K,prune,eps", [(228, 19, (), 1e-5), (252, 21, (), 1e-5), (1800, 150, (), 1e-5), (2054, 182, (), 1e-5),
@@ -137,7 +71,7 @@ def _check_against_f64(net, reg, weights, eps):
 def test_group_regularizers_match_float64(P, K, prune, eps):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device(required=True)
     net = _group_net(P, K, 4, seed=P + K)
     if prune:
         net.prune_prototypes(list(prune))
@@ -152,15 +86,15 @@ def test_group_regularizers_match_float64(P, K, prune, eps):
     net.last_layer_group.weight.data.add_(0.01 * torch.randn(net.last_layer_group.weight.shape, generator=g).to(dev))
     weights = (0.25, 0.1, 0.3, 1e-3)
     reg = spx.GroupRegularizers(net, group_ent=weights[0], crs_ent_group=weights[1], scale_max=weights[2], l1=weights[3], epsilon=eps)
-    _check_against_f64(net, reg, weights, eps)
+    check_against_f64(net, reg, weights, eps)
 
 
 @pytest.mark.parametrize("P,K", [(228, 19), (1800, 150), (2054, 182)])
 def test_prototype_head_l1_matches_float64(P, K):
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
-    net = _proto_net(P, K, 4).to(dev)
+    dev = gpu_device(required=True)
+    net = proto_net(P, K, 4, 16, add_on=nn.Sequential(), device=dev)
     g = torch.Generator().manual_seed(K)
     W = torch.randn(K, P, generator=g)
     W[torch.rand(K, P, generator=g) < 0.1] = 0.0
@@ -180,7 +114,7 @@ def test_prototype_head_l1_matches_float64(P, K):
 def test_scale_max_gradient_goes_to_first_maximum_under_ties():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device(required=True)
     net = _group_net(48, 4, 4).to(dev)          # 12 prototypes per class, 3 per scale: spans [0,3) [3,6) [6,9) [9,12)
     for gp in net.group_projection:
         w = torch.zeros(3, 12)
@@ -206,7 +140,7 @@ def test_scale_max_gradient_goes_to_first_maximum_under_ties():
 def test_cross_entropy_clamp_mask_at_epsilon():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device(required=True)
     net = _group_net(48, 4, 4).to(dev)
     eps = float(np.float32(1e-5))
     for gp in net.group_projection:
@@ -218,9 +152,9 @@ def test_cross_entropy_clamp_mask_at_epsilon():
     ceg = spx.CrossEntropyGroup(net, epsilon=1e-5)
     v = ceg()
     v.backward()
-    r = restate(net.prototype_class_identity.cpu(), net.scale_num_prototypes, 3, 1e-5, _flat_weights(net).cpu().numpy(),
+    r = restate(net.prototype_class_identity.cpu(), net.scale_num_prototypes, 3, 1e-5, flat_weights(net).cpu().numpy(),
                 np.zeros((4, 12), np.float32), np.zeros((4, 48), np.float32), dtype=torch.float32)
-    got = _flat_grads(net).cpu()
+    got = flat_grads(net).cpu()
     assert close(got, r["d_ceg"], 1e-5)
     # the element at eps gets the clamp term (q * w_other / eps, large); the one just below only its row-i terms
     assert got[12 + 0].abs() > 100 * got[12 + 1].abs()
@@ -229,15 +163,15 @@ def test_cross_entropy_clamp_mask_at_epsilon():
 def test_repeated_calls_are_bit_identical():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device(required=True)
     net = _group_net(1800, 150, 4, seed=3).to(dev)
     reg = spx.GroupRegularizers(net, group_ent=0.25, crs_ent_group=0.1, scale_max=0.3, l1=1e-4)
     outs = []
     for _ in range(3):
-        _zero_grads(net)
+        zero_grads(net)
         total, terms = reg()
         total.backward()
-        outs.append((total.clone(), terms.clone(), _flat_grads(net).clone(), net.last_layer_group.weight.grad.clone()))
+        outs.append((total.clone(), terms.clone(), flat_grads(net).clone(), net.last_layer_group.weight.grad.clone()))
     for o in outs[1:]:
         for a, b in zip(outs[0], o):
             assert torch.equal(a, b)
@@ -253,7 +187,7 @@ def _group_step_inputs(net, dev, B=2, H=9, W=9, seed=0):
 def test_gradients_through_logits_route_equal_standalone_terms():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device(required=True)
     for P, K in ((228, 19), (1800, 150)):
         net = _group_net(P, K, 4, seed=K).to(dev)
         x, target = _group_step_inputs(net, dev, seed=K)
@@ -261,18 +195,18 @@ def test_gradients_through_logits_route_equal_standalone_terms():
         reg = spx.GroupRegularizers(net, *wts)
         ce = spx.PixelWiseCrossEntropyLoss(ignore_index=-1)
 
-        _zero_grads(net)
+        zero_grads(net)
         logits, _ = net.forward_from_conv_features(x, ce_target=target)
         total, _ = reg(logits)
         (ce(logits, target) + total).backward()
-        fused = (_flat_grads(net).clone(), net.last_layer_group.weight.grad.clone(), net.prototype_vectors.grad.clone())
+        fused = (flat_grads(net).clone(), net.last_layer_group.weight.grad.clone(), net.prototype_vectors.grad.clone())
 
-        _zero_grads(net)
+        zero_grads(net)
         logits, _ = net.forward_from_conv_features(x, ce_target=target)
         terms = (spx.EntropyGroup(net)(), spx.CrossEntropyGroup(net)(), spx.ScaleMax(net)(), spx.head_l1(net))
         loss = ce(logits, target) + wts[3] * terms[3] + wts[1] * terms[1] + wts[2] * terms[2] + wts[0] * terms[0]
         loss.backward()
-        alone = (_flat_grads(net), net.last_layer_group.weight.grad, net.prototype_vectors.grad)
+        alone = (flat_grads(net), net.last_layer_group.weight.grad, net.prototype_vectors.grad)
         for a, b in zip(fused, alone):
             assert (a - b).abs().max() <= 1e-6 * b.abs().max(), (P, (a - b).abs().max())
 
@@ -283,7 +217,7 @@ def test_captured_group_step_replays_eager_bit_for_bit():
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.graphs import capture_step
 
-    dev = _dev()
+    dev = gpu_device(required=True)
     net = _group_net(228, 19, 4, seed=7).to(dev)
     x, target = _group_step_inputs(net, dev, seed=7)
     reg = spx.GroupRegularizers(net, group_ent=0.05, crs_ent_group=0.0, scale_max=0.0, l1=1e-3)
@@ -291,7 +225,7 @@ def test_captured_group_step_replays_eager_bit_for_bit():
     s = torch.cuda.Stream()
 
     def step():
-        _zero_grads(net)
+        zero_grads(net)
         logits, _ = net.forward_from_conv_features(x, ce_target=target)
         total, terms = reg(logits)
         loss = ce(logits, target) + total
@@ -319,7 +253,7 @@ def test_captured_group_step_replays_eager_bit_for_bit():
 def test_regularizers_do_not_synchronise():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device(required=True)
     net = _group_net(228, 19, 4, seed=9).to(dev)
     reg = spx.GroupRegularizers(net, group_ent=0.05, l1=1e-3)
     total, _ = reg()                        # build the caches (host work) first
@@ -333,7 +267,7 @@ def test_regularizers_do_not_synchronise():
             mode_works = False
         except RuntimeError:
             pass
-        _zero_grads(net)
+        zero_grads(net)
         total, terms = reg()
         total.backward()
     finally:

@@ -1,5 +1,5 @@
 """GPU checks of the shared segment walk (csrc/spx_kld_walk.h) under both families that use it: the KLD loss against LO.kld_loss in
-float64 and the activation losses against the float64 restatement of tests/test_activation_losses_cpu.py, with the tolerances of
+float64 and the activation losses against the float64 restatement of tests/activation_loss_cases.py, with the tolerances of
 the existing tests of those kernels.  The planes are random [B, J, HW] tensors (no distance kernel; for the KLD loss both
 independent slots, loss about 0, and tests/kld_cases.py's correlated ones, loss about 0.4); the label map (kld_cases.band_labels)
 is built so that every branch of the walk runs whatever tile height the launcher picks (tiles start at multiples of 16 rows):
@@ -18,20 +18,14 @@ import torch
 from oracle import loss_oracle as LO
 from oracle import ppnet_oracle as O
 from kld_cases import BAND_B, BAND_H, BAND_W, MIN_LOSS, band_classes, band_labels as _labels, correlated_planes
-from test_activation_losses_cpu import log_activation
-from test_gpu_activation_losses import W3, _check_against_reference64, _identity, _reference64
+from activation_loss_cases import W3, check_against_reference64, identity, log_activation, reference64
+from support import gpu_device
 
 pytestmark = pytest.mark.gpu
 
 B, H, W = BAND_B, BAND_H, BAND_W                           # 2 x 37 x 83
 WIDTHS = (3, 7, 11, 16)                                   # one J per JT = 4, 8, 12, 16
 WALKS = ("grid", "linear")
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
 
 
 def _grid(walk):
@@ -45,7 +39,7 @@ def _kld_case(K, J, planes):
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.loss import ClassDistances, class_slot_table
 
-    dev = _dev()
+    dev = gpu_device()
     P = K * J
     ident = O.default_class_identity(P, K, 1)
     lab = _labels(K, band_classes(K)).to(dev)
@@ -108,7 +102,7 @@ def _act_case(J, norm_type):
     from scaleprotoseg_amd.loss import class_slot_table
 
     K = 5
-    ident, rl = _identity(ACT_COUNTS[J])
+    ident, rl = identity(ACT_COUNTS[J])
     P = ident.shape[0]
     table = class_slot_table(ident)
     assert tuple(table.shape) == (K, J)
@@ -123,7 +117,7 @@ def _act_case(J, norm_type):
     bi, pi, ji = torch.nonzero(valid, as_tuple=True)
     d = torch.rand(B, H * W, P, generator=gen) * 2.0
     d[bi, pi, idx[bi, pi, ji]] = planes[bi, ji, pi]
-    vals, counts, total, grad = _reference64(d.reshape(B * H * W, P), target, ident, rl, norm_type, W3, log_activation)
+    vals, counts, total, grad = reference64(d.reshape(B * H * W, P), target, ident, rl, norm_type, W3, log_activation)
     gp = torch.zeros(B, J, H * W, dtype=torch.float64)
     gp[bi, ji, pi] = grad.reshape(B, H * W, P)[bi, pi, idx[bi, pi, ji]]
     return ident, rl, target, lab, table, planes, (vals, counts, total, gp)
@@ -136,7 +130,7 @@ def test_activation_losses_against_float64(J, walk):
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.loss import ClassDistances
 
-    dev = _dev()
+    dev = gpu_device()
     for nt in ("l1", "linf"):
         ident, rl, target, lab, table, planes, ref = _act_case(J, nt)
         x = planes.to(dev).requires_grad_(True)
@@ -146,4 +140,4 @@ def test_activation_losses_against_float64(J, walk):
         ranges = {s: r for s, r in enumerate(rl)}
         tot, terms = spx.ActivationRegularizers(ident, len(rl), ranges, *W3, norm_type=nt)(cd, tgt)
         tot.backward()
-        _check_against_reference64(tot, terms, x.grad, ref, f"J={J} {walk} {nt}")
+        check_against_reference64(tot, terms, x.grad, ref, f"J={J} {walk} {nt}")

@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 
 from simplex_restatement import case_rows
+from support import bits_equal, gpu_device, group_net, run_gloo
 
 pytestmark = pytest.mark.gpu
 
@@ -14,20 +15,10 @@ SIZES = (1, 2, 12, 63, 64, 65, 257, 1024)
 _REF = {}
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    return torch.device("cuda:0")
-
-
 def _formula(v: torch.Tensor, z: float = 1.0) -> torch.Tensor:
     from scaleprotoseg_amd.utils import projection_simplex_sort
 
     return projection_simplex_sort(v.detach().cpu(), z)
-
-
-def _bits_equal(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return torch.equal(a.detach().cpu().contiguous().view(torch.int32), b.detach().cpu().contiguous().view(torch.int32))
 
 
 def _ragged_inputs():
@@ -64,13 +55,13 @@ def test_one_launch_over_a_ragged_list_is_bit_exact(z):
     most n times.  Total <= n 2^-23 max(1, |z|) (which covers n 2^-24 |z| + 2^-24 |z|) + n 2^-23 1.5 |theta|."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     ws = [w.to(dev) for w in _ragged_inputs()]
     assert sorted({w.shape[0] for w in ws}) == [1, 3, 5] and sorted({w.shape[1] for w in ws}) == list(SIZES)
     spx.projection_simplex_sort_(ws, z)
     for w, v, ref in zip(ws, _ragged_inputs(), _ragged_reference(z)):
         got = w.cpu()
-        assert _bits_equal(got, ref), f"[{v.shape[0]}, {v.shape[1]}] z={z}: {(got - ref).abs().max().item()}"
+        assert bits_equal(got, ref), f"[{v.shape[0]}, {v.shape[1]}] z={z}: {(got - ref).abs().max().item()}"
         assert (got >= 0).all()
         n = v.shape[1]
         for g in range(v.shape[0]):
@@ -82,21 +73,21 @@ def test_one_launch_over_a_ragged_list_is_bit_exact(z):
 def test_193_tensors_are_chunked():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(193)
     cpu = [torch.randn(3, 12, generator=g) * (0.1 + 0.05 * i) for i in range(193)]
     ws = [w.to(dev) for w in cpu]
     spx.projection_simplex_sort_(ws)
     ref = _formula(torch.cat(cpu, dim=0)).reshape(193, 3, 12)             # (the formula is row-wise)
     for i in (0, 191, 192):
-        assert _bits_equal(ws[i], ref[i]), i
-    assert _bits_equal(torch.stack([w.cpu() for w in ws]), ref)
+        assert bits_equal(ws[i], ref[i]), i
+    assert bits_equal(torch.stack([w.cpu() for w in ws]), ref)
 
 
 def test_the_edit_is_in_place():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(7)
     before = torch.full((64,), 5.0, device=dev)
     ws = [nn.Parameter(torch.randn(G, n, generator=g).to(dev)) for G, n in ((3, 12), (1, 65), (5, 7), (3, 12))]
@@ -110,7 +101,7 @@ def test_the_edit_is_in_place():
     assert all(w.grad_fn is None and w.requires_grad and w.is_leaf for w in ws)       # no autograd node on the parameters
     assert (canary == 7.0).all() and (before == 5.0).all()
     for w, v in zip(ws, cpu):
-        assert _bits_equal(w, _formula(v))
+        assert bits_equal(w, _formula(v))
     with pytest.raises(spx.SpxError, match="listed twice"):
         spx.projection_simplex_sort_([ws[0], ws[1], ws[0]])
     with pytest.raises(spx.SpxError, match="fp32"):
@@ -121,7 +112,7 @@ def test_rows_longer_than_the_kernel_takes_fall_back_in_place():
     """n > 1024 in any tensor: the whole call is the stock formula on the device, copied back into the same storages."""
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(1025)
     ws = [nn.Parameter(torch.randn(s, generator=g).to(dev)) for s in ((2, 1025), (3, 12))]
     want = [spx.projection_simplex_sort(w.detach().clone()) for w in ws]
@@ -138,7 +129,7 @@ def test_rows_longer_than_the_kernel_takes_fall_back_in_place():
 def test_a_nan_row_comes_back_nan_and_its_neighbours_exact():
     import scaleprotoseg_amd as spx
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(11)
     a, b = torch.randn(3, 12, generator=g), torch.randn(2, 70, generator=g)
     a[1, 5] = float("nan")
@@ -148,19 +139,11 @@ def test_a_nan_row_comes_back_nan_and_its_neighbours_exact():
     spx.projection_simplex_sort_([wa, wb, wc])
     assert torch.isnan(wa[1]).all() and torch.isnan(wb[0]).all()
     assert torch.isnan(_formula(a)[1]).all()                                # ... as the formula has it
-    assert _bits_equal(wa[[0, 2]], _formula(a[[0, 2]])) and _bits_equal(wb[1:], _formula(b[1:])) and _bits_equal(wc, _formula(c))
+    assert bits_equal(wa[[0, 2]], _formula(a[[0, 2]])) and bits_equal(wb[1:], _formula(b[1:])) and bits_equal(wc, _formula(c))
 
 
 def _group_net(dev, seed=1):
-    from test_gpu_modules import _Backbone
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet
-
-    S, Cs, K, G, P = 4, 16, 5, 3, 40
-    torch.manual_seed(seed)
-    net = GroupNet(_Backbone(S * Cs), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                   patch_classification=True, num_scales=S, num_groups=G)
-    net.add_on_layers = nn.Sequential()
-    return net.to(dev)
+    return group_net(40, 5, 4, 16, 3, seed=seed, add_on=nn.Sequential(), device=dev)
 
 
 def _consumers(net, x):
@@ -171,7 +154,7 @@ def _consumers(net, x):
 
 
 def test_the_module_caches_see_the_projection():
-    dev = _dev()
+    dev = gpu_device()
     net = _group_net(dev)
     x = torch.sigmoid(torch.randn(2, 64, 9, 11, generator=torch.Generator().manual_seed(3))).to(dev)
     first = _consumers(net, x)
@@ -204,7 +187,7 @@ def test_the_projection_is_capturable():
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd import graphs
 
-    dev = _dev()
+    dev = gpu_device()
     g = torch.Generator().manual_seed(21)
     shapes = ((3, 12), (3, 5), (2, 65))
     cpu = [spx.projection_simplex_sort(torch.rand(s, generator=g)) for s in shapes]
@@ -226,9 +209,10 @@ def test_the_projection_is_capturable():
         cpu = [_formula(w + d) for w, d in zip(cpu, deltas_cpu)]
     assert [w.data_ptr() for w in ws] == ptrs
     for w, ref in zip(ws, cpu):
-        assert _bits_equal(w, ref)
+        assert bits_equal(w, ref)
 
 
+# (what one rank runs in this file's data-parallel test; support.run_gloo spawns it)
 def _dp_case(rank, world):
     """Two identical group modules through identical steps: the default re-projection (formula per class, rebound) and the fused
     one.  Plain SGD: the update is linear in the gradient, so the two paths stay a rounding error apart."""
@@ -256,10 +240,8 @@ def _dp_case(rank, world):
 
 
 def test_data_parallel_step_with_the_fused_projection(tmp_path):
-    _dev()
-    from test_gpu_dp import _run
-
-    (res,) = _run(_dp_case, tmp_path, world=1)
+    gpu_device()
+    (res,) = run_gloo(_dp_case, tmp_path, world=1, gpu=True)
     (wd, pd), (wf, pf) = res["default"], res["fused"]
     for a, b, w0 in zip(wd, wf, res["initial"]):
         assert (a - b).abs().max().item() <= 1e-6

@@ -3,15 +3,11 @@ of the C entries (no GPU is touched), the refusal of CPU tensors, and the sum of
 import ctypes as C
 import math
 import os
-import socket
-import sys
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import run_gloo
 
 
 @pytest.fixture(scope="module")
@@ -185,29 +181,15 @@ def _counters(rank, K, P):
     return buf
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _worker(rank, world, port, out):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        K, P = 5, 10
-        hm = _HostMetrics(K, torch.eye(K).repeat(2, 1), _counters(rank, K, P))
-        hm.m.all_reduce()
-        torch.save(hm.m._buf, os.path.join(out, f"r{rank}.pt"))
-    finally:
-        dist.destroy_process_group()
+def _all_reduce_case(rank, world):
+    K, P = 5, 10
+    hm = _HostMetrics(K, torch.eye(K).repeat(2, 1), _counters(rank, K, P))
+    hm.m.all_reduce()
+    return hm.m._buf
 
 
 def test_all_reduce_sums_two_ranks(tmp_path):
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
-    bufs = [torch.load(os.path.join(tmp_path, f"r{r}.pt")) for r in range(2)]
+    bufs = run_gloo(_all_reduce_case, tmp_path)
     K, P = 5, 10
     total = _counters(0, K, P) + _counters(1, K, P)
     assert torch.equal(bufs[0], total) and torch.equal(bufs[1], total)

@@ -6,23 +6,11 @@ import torch
 import torch.nn as nn
 
 import scaleprotoseg_amd as spx
-
-
-class _Backbone(nn.Module):
-    def __init__(self, ch):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return x
+from support import group_net, proto_net
 
 
 def _proto(P, Cs, S, K, **kw):
-    return spx.PPNetMultiScale(_Backbone(Cs * S), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                               patch_classification=True, num_scales=S, **kw)
+    return proto_net(P, K, S, Cs, **kw)
 
 
 @pytest.mark.parametrize("name", ["proto_ms_small", "proto_ms_city", "proto_s3", "proto_floor", "proto_s1_wide"])
@@ -52,8 +40,7 @@ def test_state_dict_and_tables_match_reference(golden, name):
 def test_prune_matches_reference(golden):
     g = golden("misc")
     P, S, K = int(g["prune_P"]), int(g["prune_S"]), int(g["prune_K"])
-    net = spx.PPNetMultiScale(_Backbone(8 * S), 64, (P, 8, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S)
+    net = proto_net(P, K, S, 8)
     with torch.no_grad():
         net.prototype_vectors.copy_(torch.from_numpy(g["prune_before_protos"]))
         net.last_layer.weight.copy_(torch.from_numpy(g["prune_before_last"]))
@@ -79,8 +66,7 @@ def test_group_phase_surface(golden):
     P, K = g["class_identity"].shape
     Cs = g["prototype_vectors"].shape[1]
     old = _proto(P, Cs, S, K)
-    net = spx.PPNetMultiScaleGroup(_Backbone(Cs * S), 64, (P, Cs, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                                   patch_classification=True, num_scales=S, num_groups=G)
+    net = group_net(P, K, S, Cs, G)
     sd = {k: v for k, v in net.state_dict().items() if not k.startswith("features.")}
     assert list(sd.keys()) == list(g["state_keys"])
     assert [str(tuple(v.shape)) for v in sd.values()] == list(g["state_shapes"])
@@ -108,7 +94,7 @@ def test_group_phase_surface(golden):
 def test_single_scale_ppnet(golden):
     g = golden("ppnet_single")
     P, K = g["class_identity"].shape
-    net = spx.PPNet(_Backbone(32), 64, (P, 32, 1, 1), [], K, add_on_layers_type="deeplab_simple", patch_classification=True)
+    net = proto_net(P, K, 1, 32, cls=spx.PPNet)
     np.testing.assert_array_equal(net.prototype_class_identity.numpy(), g["class_identity"])
     assert net.num_prototypes_per_class == P // K and net.num_scales == 1
 
@@ -226,7 +212,6 @@ def test_pruned_prototype_checkpoint_loads_into_the_group_module(tmp_path, golde
     pruned class table."""
     import json
     from scaleprotoseg_amd.checkpoint import export_state, import_state, load_reference_state_dict
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet
 
     g = golden("misc")
     P, S, K = int(g["prune_P"]), int(g["prune_S"]), int(g["prune_K"])
@@ -240,8 +225,7 @@ def test_pruned_prototype_checkpoint_loads_into_the_group_module(tmp_path, golde
     path.write_text(json.dumps(keep))
 
     def fresh():
-        return GroupNet(_Backbone(8 * S), 64, (P, 8, 1, 1), [], K, add_on_layers_type="deeplab_simple",
-                        patch_classification=True, num_scales=S, num_groups=3)
+        return group_net(P, K, S, 8, 3)
 
     dst = fresh()
     res = load_reference_state_dict(dst, src.state_dict(), unique_prototypes=str(path))
@@ -265,10 +249,7 @@ def test_pruned_prototype_checkpoint_loads_into_the_group_module(tmp_path, golde
 def test_table_caches_follow_in_place_edits_and_reassignment():
     """The (class, slot) gather table and the dense grouping index are keyed on the identity OBJECT, its in-place
     version and the module's table counter: an in-place edit or a re-assignment invalidates them."""
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet
-
-    net = GroupNet(_Backbone(32), 64, (12, 8, 1, 1), [], 3, add_on_layers_type="deeplab_simple",
-                   patch_classification=True, num_scales=4, num_groups=2)
+    net = group_net(12, 3, 4, 8, 2)
     r0, c0, n0, _ = net._group_index("cpu")
     assert net._group_index("cpu")[0] is r0                      # cached
     v = net._tables_version
@@ -413,10 +394,9 @@ def test_torch_module_edits_the_pack_cache_key_relies_on():
 def test_scale_table_item_edits_reach_the_group_tables():
     """``scale_num_prototypes[s] = ...`` is an item edit of a dict: it passes no ``__setattr__``, so the caches that read the
     scale ranges carry them in their keys (the gather and push tables through the layout, the group tables' ScaleMax spans)."""
-    from scaleprotoseg_amd.model_multiscale_group import PPNetMultiScale as GroupNet, group_scale_spans
+    from scaleprotoseg_amd.model_multiscale_group import group_scale_spans
 
-    net = GroupNet(_Backbone(32), 64, (24, 16, 1, 1), [], 3, add_on_layers_type="deeplab_simple",
-                   patch_classification=True, num_scales=2, num_groups=2)
+    net = group_net(24, 3, 2, 16, 2)
     spans = lambda: group_scale_spans(net.prototype_class_identity, net.scale_num_prototypes, 2, 2)[1]
     before = spans()
     idx = net._group_index("cpu")

@@ -13,29 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import overlap_restatement as R  # noqa: E402
-
-GOLDEN = os.path.join(HERE, "golden", "activation_overlap.npz")
-EPS = 1e-4
-
-
-def load_cases():
-    z = np.load(GOLDEN)
-    cases = {}
-    for key in z.files:
-        name, field = key.split("__")
-        cases.setdefault(name, {})[field] = z[key]
-    return cases
-
-
-def planes_of(case):
-    """The float32 activation planes [N, C, h, w] the reference upsampled."""
-    if str(case["kind"]) == "proto":
-        d = case["distances"]
-        return np.log((d + 1) / (d + EPS))                   # prototype_overlap.py:60 on float32
-    return case["activations"]
-
-
-CASES = load_cases()
+from map_cases import OVERLAP_CASES as CASES, planes_of  # noqa: E402
 
 
 def test_fixture_holds_the_cases_of_the_issue():

@@ -2,15 +2,13 @@
 prune.py:33-42 restated with collections.Counter, the data-parallel merge at world size 2 over gloo, the ABI version.
 No kernels run here."""
 import os
-import socket
-import sys
 from collections import Counter
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from support import run_gloo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -128,34 +126,21 @@ def test_nearest_table_rejects_k_outside_range():
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# data-parallel merge, world size 2 over gloo (as tests/test_dp_gloo.py)
+# data-parallel merge, world size 2 over gloo (support.run_gloo, as tests/test_dp_gloo.py)
 # ------------------------------------------------------------------------------------------------------------------
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
-def _worker(rank, world, port, out):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from scaleprotoseg_amd import dp
+def _dp_merge_case(rank, world):
+    from scaleprotoseg_amd import dp
 
-        gen = np.random.default_rng(7)
-        rows = [_random_entries(gen, range(0, 11)) for _ in range(5)]
-        shard = dp.shard_range(11, rank, world)
-        local = _table([[e for e in r if e[2] in shard] for r in rows], 4)
-        got = dp.reduce_prune_tables(local, 4)
-        torch.save((got, _table(rows, 4)), os.path.join(out, f"r{rank}.pt"))
-    finally:
-        dist.destroy_process_group()
+    gen = np.random.default_rng(7)
+    rows = [_random_entries(gen, range(0, 11)) for _ in range(5)]
+    shard = dp.shard_range(11, rank, world)
+    local = _table([[e for e in r if e[2] in shard] for r in rows], 4)
+    return dp.reduce_prune_tables(local, 4), _table(rows, 4)
 
 
 def test_dp_merge_gloo_equals_single_rank(tmp_path):
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
-    (g0, single), (g1, _) = [torch.load(os.path.join(tmp_path, f"r{r}.pt")) for r in range(2)]
+    (g0, single), (g1, _) = run_gloo(_dp_merge_case, tmp_path)
     assert torch.equal(g0, g1)
     assert torch.equal(g0, single)

@@ -13,36 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import push_boxes_restatement as PB  # noqa: E402
-
-GOLDEN = os.path.join(HERE, "golden", "push_boxes.npz")
-EPS = 1e-4
-
-
-def load_cases():
-    z = np.load(GOLDEN)
-    cases = {}
-    for key in z.files:
-        name, field = key.split("__")
-        cases.setdefault(name, {})[field] = z[key]
-    return cases
-
-
-def planes_of(case):
-    """The float32 activation planes [N, P, h, w] the reference upsampled."""
-    kind = str(case["kind"])
-    if kind == "log":
-        d = case["distances"]
-        return np.log((d + 1) / (d + EPS))                   # push_multiscale_optimization.py:447 on float32
-    if kind == "linear":
-        return np.float32(4.0) - case["distances"]           # :449 with max_dist = 4
-    return case["activations"]
-
-
-def classes_of(case):
-    return case["ident"].argmax(1)
-
-
-CASES = load_cases()
+from map_cases import PUSH_BOX_CASES as CASES, classes_of, planes_of  # noqa: E402
 
 
 def test_fixture_holds_the_cases_of_the_issue():

@@ -1,6 +1,6 @@
 """The push's one driver and the data-set walk it shares with the pruning search (scaleprotoseg_amd/scan.py), without a GPU:
 ``global_min`` against the oracle's gather, the two-pass push with more ranks than images, what an empty data set raises, and
-the run generator.  Stand-in backbone, data and device-step replacements of tests/test_push_single_pass_cpu.py; every comparison
+the run generator.  Stand-in backbone, data and device-step replacements of tests/push_cases.py; every comparison
 is an equality of bits."""
 import os
 import sys
@@ -13,10 +13,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 from oracle import ppnet_oracle as O  # noqa: E402
-from test_dp_gloo import _patch_kernels_with_oracle, _run  # noqa: E402
-from test_push_single_pass_cpu import K_, MIXED, QUIET, S_, _same_state, _setup, _state, steps  # noqa: E402,F401
+from push_cases import K_, MIXED, QUIET, S_, feature_problem, patch_kernels_with_oracle, push_state  # noqa: E402
+from push_cases import same_push_state, steps  # noqa: E402,F401  (steps: a fixture, taken by importing its name)
+from support import run_gloo  # noqa: E402
 
 
+# (local: a NumPy array's float32 bytes; support.bits_equal compares tensors)
 def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).tobytes()
 
@@ -25,7 +27,7 @@ def _bits(a):
 def test_global_min_equals_the_oracle_gather(steps, rng):  # noqa: F811
     from scaleprotoseg_amd.push import global_min, min_across_dataset
 
-    net, data = _setup(MIXED)
+    net, data = feature_problem(MIXED)
     P = net.num_prototypes
     convs = [net.conv_features(data[i][0].unsqueeze(0)) for i in rng]        # mixed sizes: 6x8, 8x10, 8x6 latent pixels
     assert len({tuple(c.shape[2:]) for c in convs}) >= 2
@@ -40,21 +42,21 @@ def test_global_min_equals_the_oracle_gather(steps, rng):  # noqa: F811
 def _one_image_case(rank, world):
     from scaleprotoseg_amd.push import push_prototypes_multiscale
 
-    net, data = _setup(MIXED[:1])
-    _patch_kernels_with_oracle(S_)
+    net, data = feature_problem(MIXED[:1])
+    patch_kernels_with_oracle(S_)
     best, list_idx, dup = push_prototypes_multiscale(data, net, **QUIET)
-    return _state(net), best.clone(), [t.clone() for t in list_idx], list(dup)
+    return push_state(net), best.clone(), [t.clone() for t in list_idx], list(dup)
 
 
 def test_two_pass_push_with_more_ranks_than_images(steps, tmp_path):  # noqa: F811
     from scaleprotoseg_amd.push import push_prototypes_multiscale
 
-    res = _run(_one_image_case, tmp_path)
-    net0, data = _setup(MIXED[:1])
+    res = run_gloo(_one_image_case, tmp_path)
+    net0, data = feature_problem(MIXED[:1])
     best0, list_idx0, dup0 = push_prototypes_multiscale(data, net0, **QUIET)
     assert (best0 == 0).all() and len(list_idx0) == 1
     for state, best, _, dup in res:
-        _same_state(state, _state(net0))
+        same_push_state(state, push_state(net0))
         assert torch.equal(best, best0) and dup == list(dup0)
     assert len(res[0][2]) == 1 and torch.equal(res[0][2][0], list_idx0[0]) and res[1][2] == []    # rank 1's shard is empty
 
@@ -64,7 +66,7 @@ def test_an_empty_data_set_raises_what_it_always_did(steps):  # noqa: F811
     refused by the driver (SpxError) - the types recorded before the three bodies became one."""
     import scaleprotoseg_amd as spx
 
-    net, data = _setup(MIXED[:1])
+    net, data = feature_problem(MIXED[:1])
     data.items = []
     with pytest.raises(ValueError, match="non-empty list"):
         spx.push_prototypes_multiscale(data, net, **QUIET)

@@ -1,7 +1,6 @@
 """The single-pass batched push without a GPU: the rule of spx_push_merge (tests/push_merge_restatement.py) against the CPU
 oracle, the driver (push_single_pass / push_prototypes_multiscale(batch_size=...)) with its two device steps replaced by
 oracle-based callables against today's two-pass push, argument errors and the ABI.  Everything is an equality of bits."""
-import json
 import os
 import sys
 
@@ -16,9 +15,9 @@ if HERE not in sys.path:
 import push_merge_restatement as R  # noqa: E402
 from oracle import ppnet_oracle as O  # noqa: E402
 from scaleprotoseg_amd import PushTable, push_single_pass  # noqa: E402,F401  (the feature under test: no test here runs without it)
-from test_dp_gloo import _patch_kernels_with_oracle, _run  # noqa: E402
-
-QUIET = dict(log=lambda *_: None, device="cpu")
+from push_cases import MIXED, QUIET, SAME, FeatureData, feature_problem, push_state, replace_device_steps  # noqa: E402
+from push_cases import same_push_state, steps  # noqa: E402,F401  (steps: a fixture, taken by importing its name)
+from support import run_gloo  # noqa: E402
 
 
 # ---- the rule against the oracle ---------------------------------------------------------------------------------------
@@ -58,104 +57,6 @@ def test_restatement_nan_never_wins_and_an_equal_value_does_not_replace():
 
 
 # ---- the driver, device steps replaced ---------------------------------------------------------------------------------
-class _Identity(torch.nn.Module):
-    """Stand-in backbone: the data set's "images" ARE the features [S * Cs, h, w], so an image's features do not depend on its
-    batch mates (a CPU convolution may round differently per batch shape).  ``str()`` starts with MSC and ``.base`` holds two
-    Conv2d, which is all the model's constructor asks of a backbone."""
-
-    def __init__(self, ch):
-        super().__init__()
-        self.base = torch.nn.Sequential(torch.nn.Conv2d(3, ch, 1), torch.nn.Conv2d(ch, ch, 1))
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return x
-
-
-class _Data:
-    """Feature "images" of the given latent (h, w) sizes in order; targets at four times that size, one label per latent
-    pixel, class ``absent`` never appears."""
-
-    convert_targets = None
-
-    def __init__(self, sizes, K, absent, seed, channels=None):
-        g = torch.Generator().manual_seed(seed)
-        self.items = []
-        for h, w in sizes:
-            img = torch.rand(channels or S_ * CS_, h, w, generator=g)
-            t = torch.randint(0, K + 1, (h, w), generator=g).repeat_interleave(4, 0).repeat_interleave(4, 1)
-            t[t == absent + 1] = 0
-            self.items.append((img, t.numpy()))
-
-    def __len__(self):
-        return len(self.items)
-
-    def __getitem__(self, i):
-        return self.items[i]
-
-
-S_, CS_, K_, PER_ = 2, 16, 3, 2
-SAME = [(6, 8)] * 7
-MIXED = [(6, 8)] * 2 + [(8, 10)] * 3 + [(6, 8)] + [(8, 6)]                # runs break at 2, 5 and 6
-
-
-def _setup(sizes):
-    import scaleprotoseg_amd as spx
-
-    P = S_ * K_ * PER_
-    torch.manual_seed(11)
-    net = spx.PPNetMultiScale(_Identity(S_ * CS_), 64, (P, CS_, 1, 1), [], K_, add_on_layers_type="deeplab_simple",
-                              patch_classification=True, num_scales=S_)
-    net.add_on_layers = torch.nn.Identity()
-    with torch.no_grad():
-        net.prototype_vectors[1].copy_(net.prototype_vectors[0])          # forced duplicate
-    return net, _Data(sizes, K_, absent=2, seed=12)
-
-
-def _replace_device_steps():
-    """push_run_minima / push_run_merge on the oracle and the restatement (tests only; the product path never does)."""
-    from scaleprotoseg_amd import push as push_mod
-
-    def minima(net, conv, labels, void_class, max_dist=1e10):
-        ranges = {s: tuple(net.scale_num_prototypes[s]) for s in range(net.num_scales)}
-        d = O.scale_l2_convolution(conv, net.prototype_vectors.detach(), ranges, net.num_scales)
-        return O.push_masked_argmin(d, labels, net.prototype_class_identity, net.num_classes, max_dist, void_class)
-
-    def merge(table, idx, val, conv, proto_scale, image0):
-        B = table.check(idx, val, conv, proto_scale, image0)
-        R.merge(dict(best_value=table.best_value, best_image=table.best_image, best_flat=table.best_flat,
-                     best_patch=table.best_patch), idx, val, conv, proto_scale, image0)
-        table.next_image = int(image0) + B
-
-    push_mod.push_run_minima = minima
-    push_mod.push_run_merge = merge
-
-
-@pytest.fixture
-def steps(monkeypatch):
-    """Both paths on the CPU for one test: today's compute_distances / argmin_over_images as tests/test_dp_gloo.py replaces
-    them, and the single pass's two device steps; everything is put back afterwards."""
-    from scaleprotoseg_amd import push as push_mod
-
-    for name in ("compute_distances", "argmin_over_images", "push_run_minima", "push_run_merge"):
-        monkeypatch.setattr(push_mod, name, getattr(push_mod, name))        # registers the restore
-    _patch_kernels_with_oracle(S_)
-    _replace_device_steps()
-
-
-def _state(net, root=None):
-    out = dict(bank=net.prototype_vectors.detach().clone(), ranges={s: tuple(net.scale_num_prototypes[s]) for s in range(S_)},
-               last=net.last_layer.weight.detach().clone(), ident=net.prototype_class_identity.clone())
-    if root is not None:
-        out["json"] = json.load(open(os.path.join(root, "unique_prototypes.json")))
-    return out
-
-
-def _same_state(a, b):
-    assert torch.equal(a["bank"], b["bank"]) and torch.equal(a["last"], b["last"]) and torch.equal(a["ident"], b["ident"])
-    assert a["ranges"] == b["ranges"] and a.get("json") == b.get("json")
 
 
 def _spy(net):
@@ -175,18 +76,18 @@ def _spy(net):
 def test_driver_equals_the_two_pass_push(steps, tmp_path, sizes, batch):
     from scaleprotoseg_amd.push import push_prototypes_multiscale
 
-    net0, data = _setup(sizes)
+    net0, data = feature_problem(sizes)
     calls0 = _spy(net0)
     best0, list_idx, dup0 = push_prototypes_multiscale(data, net0, str(tmp_path / "two"), **QUIET)
     assert isinstance(list_idx, list) and 1 in dup0 and len(dup0) >= 2
     flat0 = torch.cat(list_idx)[best0, torch.arange(len(best0))]
 
-    net1, _ = _setup(sizes)
+    net1, _ = feature_problem(sizes)
     calls1 = _spy(net1)
     best1, flat1, dup1 = push_prototypes_multiscale(data, net1, str(tmp_path / "one"), batch_size=batch, **QUIET)
     assert isinstance(flat1, torch.Tensor) and flat1.dtype == torch.int64
     assert torch.equal(best1, best0) and torch.equal(flat1, flat0) and list(dup1) == list(dup0)      # GLOBAL image indices
-    _same_state(_state(net1, tmp_path / "one"), _state(net0, tmp_path / "two"))
+    same_push_state(push_state(net1, tmp_path / "one"), push_state(net0, tmp_path / "two"))
 
     # one encoding per run of equally sized images, against N + one per distinct winner
     runs, last = [], None
@@ -200,25 +101,26 @@ def test_driver_equals_the_two_pass_push(steps, tmp_path, sizes, batch):
     assert len(calls0) == len(sizes) + len(set(best0.tolist())) and set(calls0) == {1}
 
 
+# (what one rank runs in this file's sharded test; support.run_gloo spawns it)
 def _dp_case(rank, world):
     from scaleprotoseg_amd.push import push_prototypes_multiscale
 
-    net, data = _setup(MIXED)
-    _replace_device_steps()
+    net, data = feature_problem(MIXED)
+    replace_device_steps()
     calls = _spy(net)
     best, flat, dup = push_prototypes_multiscale(data, net, batch_size=3, **QUIET)
-    return _state(net), best.clone(), flat.clone(), list(dup), sum(calls)
+    return push_state(net), best.clone(), flat.clone(), list(dup), sum(calls)
 
 
 def test_sharded_driver_equals_the_two_pass_push(steps, tmp_path):
     from scaleprotoseg_amd.push import push_prototypes_multiscale
 
-    res = _run(_dp_case, tmp_path)
-    net0, data = _setup(MIXED)
+    res = run_gloo(_dp_case, tmp_path)
+    net0, data = feature_problem(MIXED)
     best0, list_idx, dup0 = push_prototypes_multiscale(data, net0, **QUIET)
     flat0 = torch.cat(list_idx)[best0, torch.arange(len(best0))]
     for state, best, flat, dup, images in res:
-        _same_state(state, _state(net0))
+        same_push_state(state, push_state(net0))
         assert torch.equal(best, best0) and torch.equal(flat, flat0) and dup == list(dup0)
     assert sum(r[4] for r in res) == len(MIXED)                              # every image encoded once, on one rank
 
@@ -226,7 +128,7 @@ def test_sharded_driver_equals_the_two_pass_push(steps, tmp_path):
 def test_a_rank_with_an_empty_shard_never_wins(steps):
     from scaleprotoseg_amd.push import push_single_pass
 
-    net, data = _setup(SAME)
+    net, data = feature_problem(SAME)
     table = push_single_pass(data, net, batch_size=3, image_range=range(4, 4), device="cpu")
     assert torch.isinf(table.best_value).all() and (table.best_image == -1).all() and table.next_image == 0
     part = push_single_pass(data, net, batch_size=3, image_range=range(4, 7), device="cpu")
@@ -238,7 +140,7 @@ def test_argument_errors(steps):
     import scaleprotoseg_amd as spx
     from scaleprotoseg_amd.push import proto_scale_table, push_single_pass
 
-    net, data = _setup(SAME)
+    net, data = feature_problem(SAME)
     with pytest.raises(spx.SpxError, match="batch_size"):
         push_single_pass(data, net, batch_size=0, device="cpu")
     with pytest.raises(spx.SpxError, match="batch_size"):
@@ -287,7 +189,7 @@ def test_a_scale_block_past_the_features_is_refused_before_any_image_is_encoded(
             raise AssertionError("encoded an image")
 
     with pytest.raises(spx.SpxError, match="channel block"):
-        spx.push_single_pass(_Data(SAME, 3, 2, 1), Net(), batch_size=2, device="cpu")
+        spx.push_single_pass(FeatureData(SAME, 3, 2, 1), Net(), batch_size=2, device="cpu")
 
 
 # ---- ABI ---------------------------------------------------------------------------------------------------------------

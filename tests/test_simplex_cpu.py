@@ -12,11 +12,13 @@ import torch
 import torch.nn as nn
 
 from simplex_restatement import case_rows, projection_simplex_rows
+from support import group_net
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = (1, 2, 12, 63, 64, 65, 257, 1024)
 
 
+# (local: a NumPy array's float32 bits as int32, compared with np.array_equal; support.bits_equal compares tensors)
 def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
 
@@ -107,29 +109,16 @@ def test_in_place_projection_refuses_what_it_cannot_edit_in_place():
     spx.projection_simplex_sort_([])                                       # nothing to do
 
 
-class _Backbone(nn.Module):
-    def __init__(self, ch):
-        super().__init__()
-        self.base = nn.Sequential(nn.Conv2d(3, ch, 1), nn.Conv2d(ch, ch, 1))
-
-    def __repr__(self):
-        return "MSC(standin)"
-
-    def forward(self, x):
-        return x
-
-
 def _group_net(seed=3):
     import scaleprotoseg_amd as spx
 
-    torch.manual_seed(seed)
-    net = spx.PPNetMultiScaleGroup(_Backbone(32), 64, (24, 8, 1, 1), [], 3, add_on_layers_type="deeplab_simple",
-                                   patch_classification=True, num_scales=4, num_groups=2)
     g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
+
+    def simplex_rows(net):
         for gp in net.group_projection:
             gp.weight.copy_(spx.projection_simplex_sort(torch.rand(gp.weight.shape, generator=g) * 3))
-    return net
+
+    return group_net(24, 3, 4, 8, 2, seed=seed, init=simplex_rows)
 
 
 def _reference_non_zero_proto(model):
