@@ -591,6 +591,51 @@ int spx_push_boxes(const float* planes, const int64_t* host_strides, const void*
                    const int32_t* host_rows, const float* thresholds, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
                    int32_t W, int32_t add_margin, int32_t* rf_boxes, int32_t* crops, void* stream);
 
+/* Per-row thresholds for the push boxes (additive to ABI 17): spx_push_boxes with T = row_thresholds[r], fp32 [R], in place of
+ * thresholds[n, c] - the same rows, walk and outputs.  A host row may name class -1, which masks on label 0: what the reference
+ * does for a patch whose majority label is void (nearest_img.py:283, patch_class + 1 == 0).  T = +inf or NaN hits nowhere: the crop
+ * is the patch box plus the margin. */
+int spx_push_boxes_rows(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                        const int32_t* host_rows, const float* row_thresholds, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w,
+                        int32_t H, int32_t W, int32_t add_margin, int32_t* rf_boxes, int32_t* crops, void* stream);
+
+/* Class-restricted thresholds (additive to ABI 17; segmentation/analysis/nearest_img.py:292-300, push_multiscale_optimization.py:
+ * 476-484, the reference's threshold_gt): T[r] = np.percentile(u[n, c][labels[n] == L], 100 q) with u as spx_overlap_thresholds
+ * defines it.
+ *   rows      int32 [R, 3] on the device = (n, c, label value L).  host_rows: the same table in host memory, or NULL.  Given,
+ *             every row is checked on the host (0 <= n < N, 0 <= c < C, L >= 0) and a bad one refuses the call; with NULL such a
+ *             row gets NaN and nothing is read for it.
+ *   rank      on the device, in float64 as numpy forms it: count = |{labels[n] == L}|, virtual = q (count - 1), k = floor(virtual),
+ *             gamma = (float)(virtual - k) clamped below 1, k1 = min(k + 1, count - 1);  T = numpy's _lerp(v[k], v[k1], gamma) in
+ *             fp32 over the sorted fp32 values v of the class's pixels.  count == 0: T = +inf (the reference's np.inf).
+ * The select is spx_overlap_thresholds' (three histogram rounds over values recomputed by the same function, integer
+ * histograms: exact and run-to-run identical), so with every pixel in the class T equals spx_overlap_thresholds' bit for bit.
+ * No host read, no synchronisation; every launch goes to `stream`.  workspace: spx_masked_workspace_bytes(R) bytes (0 and
+ * spx_last_error for a bad R), no initialisation needed, one call at a time per workspace.  Limits: those of
+ * spx_overlap_thresholds, R <= 4096, 0 < q < 1. */
+size_t spx_masked_workspace_bytes(int32_t R);
+int spx_masked_thresholds(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                          const int32_t* host_rows, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W, double q,
+                          void* workspace, float* thresholds, void* stream);
+
+/* Majority label of a patch box (additive to ABI 17; nearest_img.py:258-264, nearest_proto.py:242-244):
+ * majority[r] = np.bincount(labels[n][h0:h1, w0:w1].ravel()).argmax() for row (n, flat latent index f) of rows int32 [R, 2], with
+ * (h0, h1, w0, w1) the rf box of spx_push_boxes for a latent grid h x w, clipped to the image as a NumPy slice clips it; the smallest
+ * label on a tie.  Labels [N, H, W] hold 0 .. num_labels - 1 (num_labels <= 1024: the histogram lives in LDS); a value outside is
+ * not counted.  host_rows as above (0 <= n < N, 0 <= f < h*w), or NULL: such a row gets -1.  majority int32 [R]. */
+int spx_patch_majority(const void* labels, int32_t label_bytes, const int32_t* rows, const int32_t* host_rows, int32_t R, int32_t N,
+                       int32_t h, int32_t w, int32_t H, int32_t W, int32_t num_labels, int32_t* majority, void* stream);
+
+/* Nearest prototypes of chosen pixels (additive to ABI 17; segmentation/analysis/nearest_proto.py:54-66).  distances fp32
+ * [B, P, h, w] contiguous; queries int32 [Q, 3] on the device = (n, y, x), host_queries the same in host memory (every query
+ * checked, a bad one refuses the call) or NULL (a bad query gets no entry).  Per query the k <= 64 smallest distances[n, :, y, x]
+ * in ascending (distance, prototype) order under the total order of the fp32 bits (-0 below +0, NaN last): index int64 [Q, k],
+ * value fp32 [Q, k], missing entries -1 / +inf.  include: uint8 [P] or NULL; a prototype with a zero byte is no candidate.
+ * window = 0: the k nearest candidates.  window > 0, the reference's rule: the `window` nearest of ALL prototypes, of which the
+ * included ones are kept, k at the most.  One wave per query, no atomics: run-to-run identical. */
+int spx_nearest_protos(const float* distances, const int32_t* queries, const int32_t* host_queries, const uint8_t* include, int32_t Q,
+                       int32_t B, int32_t P, int32_t h, int32_t w, int32_t k, int32_t window, int64_t* index, float* value, void* stream);
+
 /* Single-pass push (additive to ABI 17; segmentation/push_multiscale_optimization.py:135-137, :162-188): merge the per-image
  * minima of B consecutive images (global indices image0 .. image0 + B - 1, later than every image already merged - the
  * precondition of spx_prune_merge) into the running winner of every prototype, and gather the winner's feature vector while the

@@ -37,6 +37,10 @@ Public surface mirrors the reference's module/function names for this path:
                                                     (segmentation/analysis/sample_activations_prototype.py:71-133,
                                                      sample_activations_group.py:72-131: per-slot uint8 heat maps over a
                                                      class and the map of the dominant slot, one byte per pixel)
+    nearest_images_to_prototypes, nearest_prototypes, high_activation_threshold_masked, patch_majority
+                                                    (segmentation/analysis/nearest_img.py, nearest_proto.py: the n nearest
+                                                     images of every prototype with the class-restricted threshold_gt and
+                                                     both crops, and the n nearest prototypes of chosen pixels)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -87,6 +91,13 @@ from .push import (  # noqa: F401
     push_prototypes_multiscale,
 )
 from .pushbox import push_bounding_boxes  # noqa: F401
+from .nearest import (  # noqa: F401
+    NearestImages,
+    high_activation_threshold_masked,
+    nearest_images_to_prototypes,
+    nearest_prototypes,
+    patch_majority,
+)
 from .explain import ExplanationMaps, activation_heat_maps, dominant_slot_maps  # noqa: F401
 from .prune import NearestPatches, find_k_nearest_patches_to_prototypes, prune_prototypes  # noqa: F401
 from .utils import (  # noqa: F401

@@ -188,6 +188,11 @@ SIGNATURES = {
     "spx_overlap_thresholds": (C.c_int, [_V, _PL, _I, _I, _I, _I, _I, _I, C.c_int64, _F, _V, _V, _V]),
     "spx_overlap_accumulate": (C.c_int, [_V, _PL, _V, _V, _I, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V]),
     "spx_push_boxes": (C.c_int, [_V, _PL, _V, _I, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "spx_push_boxes_rows": (C.c_int, [_V, _PL, _V, _I, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "spx_masked_workspace_bytes": (C.c_size_t, [_I]),
+    "spx_masked_thresholds": (C.c_int, [_V, _PL, _V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, C.c_double, _V, _V, _V]),
+    "spx_patch_majority": (C.c_int, [_V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V]),
+    "spx_nearest_protos": (C.c_int, [_V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
     "spx_explain_range": (C.c_int, [_V, _PL, _V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V]),
     "spx_explain_heat": (C.c_int, [_V, _PL, _V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V, _V]),
     "spx_explain_dominant": (C.c_int, [_V, _PL, _V, _I, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V]),

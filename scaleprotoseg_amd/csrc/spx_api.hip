@@ -875,10 +875,11 @@ int spx_overlap_accumulate(const float* planes, const int64_t* host_strides, con
                                                     (unsigned long long*)images, workspace, (hipStream_t)stream), who);
 }
 
-int spx_push_boxes(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
-                   const int32_t* host_rows, const float* thresholds, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
-                   int32_t W, int32_t add_margin, int32_t* rf_boxes, int32_t* crops, void* stream) {
-    static const char* who = "spx_push_boxes";
+// what spx_push_boxes and spx_push_boxes_rows check alike; min_class: the lowest class a host row may name
+static int push_boxes_check(const char* who, const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes,
+                            const int32_t* rows, const int32_t* host_rows, const float* thresholds, int32_t R, int32_t N, int32_t C,
+                            int32_t h, int32_t w, int32_t H, int32_t W, int32_t add_margin, const int32_t* rf_boxes, const int32_t* crops,
+                            int32_t min_class) {
     if (!labels || !rows || !thresholds || !rf_boxes || !crops) return fail("%s: NULL labels / rows / thresholds / boxes", who);
     if (int e = check_label_bytes(who, label_bytes)) return e;
     if (R < 1 || R > SPX_PBX_MAX_ROWS) return fail("%s: %d rows (1..%d)", who, R, SPX_PBX_MAX_ROWS);
@@ -887,12 +888,101 @@ int spx_push_boxes(const float* planes, const int64_t* host_strides, const void*
     if (host_rows)
         for (int r = 0; r < R; ++r) {
             const int32_t* q = host_rows + 4 * (size_t)r;
-            if (q[0] < 0 || q[0] >= N || q[1] < 0 || q[1] >= C || q[2] < 0 || q[3] < 0 || q[3] >= h * w)
-                return fail("%s: row %d = (n %d, c %d, class %d, flat index %d) out of range (N=%d C=%d, class >= 0, h*w=%d)", who, r,
-                            q[0], q[1], q[2], q[3], N, C, h * w);
+            if (q[0] < 0 || q[0] >= N || q[1] < 0 || q[1] >= C || q[2] < min_class || q[3] < 0 || q[3] >= h * w)
+                return fail("%s: row %d = (n %d, c %d, class %d, flat index %d) out of range (N=%d C=%d, class >= %d, h*w=%d)", who, r,
+                            q[0], q[1], q[2], q[3], N, C, min_class, h * w);
         }
-    return hip_status(spx_launch_push_boxes(planes, (const long long*)host_strides, labels, label_bytes, rows, thresholds, R, N, C, h, w,
-                                            H, W, add_margin, rf_boxes, crops, (hipStream_t)stream), who);
+    return 0;
+}
+
+int spx_push_boxes(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                   const int32_t* host_rows, const float* thresholds, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H,
+                   int32_t W, int32_t add_margin, int32_t* rf_boxes, int32_t* crops, void* stream) {
+    static const char* who = "spx_push_boxes";
+    if (int e = push_boxes_check(who, planes, host_strides, labels, label_bytes, rows, host_rows, thresholds, R, N, C, h, w, H, W,
+                                 add_margin, rf_boxes, crops, 0))
+        return e;
+    return hip_status(spx_launch_push_boxes(planes, (const long long*)host_strides, labels, label_bytes, rows, thresholds, 0, R, N, C, h,
+                                            w, H, W, add_margin, rf_boxes, crops, (hipStream_t)stream), who);
+}
+
+int spx_push_boxes_rows(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                        const int32_t* host_rows, const float* row_thresholds, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w,
+                        int32_t H, int32_t W, int32_t add_margin, int32_t* rf_boxes, int32_t* crops, void* stream) {
+    static const char* who = "spx_push_boxes_rows";
+    if (int e = push_boxes_check(who, planes, host_strides, labels, label_bytes, rows, host_rows, row_thresholds, R, N, C, h, w, H, W,
+                                 add_margin, rf_boxes, crops, -1))
+        return e;
+    return hip_status(spx_launch_push_boxes(planes, (const long long*)host_strides, labels, label_bytes, rows, row_thresholds, 1, R, N, C,
+                                            h, w, H, W, add_margin, rf_boxes, crops, (hipStream_t)stream), who);
+}
+
+#define SPX_MSK_MAX_ROWS 4096
+size_t spx_masked_workspace_bytes(int32_t R) {
+    if (R < 1 || R > SPX_MSK_MAX_ROWS) {
+        fail("spx_masked_workspace_bytes: %d rows (1..%d)", R, SPX_MSK_MAX_ROWS);
+        return 0;
+    }
+    return spx_masked_ws_bytes(R);
+}
+
+int spx_masked_thresholds(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                          const int32_t* host_rows, int32_t R, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W, double q,
+                          void* workspace, float* thresholds, void* stream) {
+    static const char* who = "spx_masked_thresholds";
+    if (!labels || !rows || !thresholds) return fail("%s: NULL labels / rows / thresholds", who);
+    if (int e = check_label_bytes(who, label_bytes)) return e;
+    if (R < 1 || R > SPX_MSK_MAX_ROWS) return fail("%s: %d rows (1..%d)", who, R, SPX_MSK_MAX_ROWS);
+    if (!(q > 0.0 && q < 1.0)) return fail("%s: quantile %g outside 0 < q < 1", who, q);
+    if (int e = overlap_check(who, planes, host_strides, N, C, h, w, H, W, workspace)) return e;
+    if (host_rows)
+        for (int r = 0; r < R; ++r) {
+            const int32_t* p = host_rows + 3 * (size_t)r;
+            if (p[0] < 0 || p[0] >= N || p[1] < 0 || p[1] >= C || p[2] < 0)
+                return fail("%s: row %d = (n %d, c %d, label %d) out of range (N=%d C=%d, label >= 0)", who, r, p[0], p[1], p[2], N, C);
+        }
+    return hip_status(spx_launch_masked_thresholds(planes, (const long long*)host_strides, labels, label_bytes, rows, R, N, C, h, w, H, W,
+                                                   q, workspace, thresholds, (hipStream_t)stream), who);
+}
+
+#define SPX_NEAR_MAX_K 64
+int spx_patch_majority(const void* labels, int32_t label_bytes, const int32_t* rows, const int32_t* host_rows, int32_t R, int32_t N,
+                       int32_t h, int32_t w, int32_t H, int32_t W, int32_t num_labels, int32_t* majority, void* stream) {
+    static const char* who = "spx_patch_majority";
+    if (!labels || !rows || !majority) return fail("%s: NULL labels / rows / output", who);
+    if (int e = check_label_bytes(who, label_bytes)) return e;
+    if (R < 1 || R > SPX_PBX_MAX_ROWS) return fail("%s: %d rows (1..%d)", who, R, SPX_PBX_MAX_ROWS);
+    if (N < 1 || h < 1 || w < 1 || H < 1 || W < 1) return fail("%s: empty input (N=%d h=%d w=%d H=%d W=%d)", who, N, h, w, H, W);
+    if ((long long)H * W >= (1LL << 31) || (long long)h * w >= (1LL << 31) || H > SPX_OVL_MAX_OUT || W > SPX_OVL_MAX_OUT)
+        return fail("%s: maps too large (H*W, h*w < 2^31, H and W <= %d)", who, SPX_OVL_MAX_OUT);
+    if (num_labels < 1 || num_labels > SPX_EVAL_MAX_CLASSES)
+        return fail("%s: %d label values 0..K (K + 1 <= %d: the histogram lives in LDS)", who, num_labels, SPX_EVAL_MAX_CLASSES);
+    if (host_rows)
+        for (int r = 0; r < R; ++r) {
+            const int32_t* p = host_rows + 2 * (size_t)r;
+            if (p[0] < 0 || p[0] >= N || p[1] < 0 || p[1] >= h * w)
+                return fail("%s: row %d = (n %d, flat index %d) out of range (N=%d h*w=%d)", who, r, p[0], p[1], N, h * w);
+        }
+    return hip_status(spx_launch_patch_majority(labels, label_bytes, rows, R, N, h, w, H, W, num_labels, majority, (hipStream_t)stream), who);
+}
+
+int spx_nearest_protos(const float* distances, const int32_t* queries, const int32_t* host_queries, const uint8_t* include, int32_t Q,
+                       int32_t B, int32_t P, int32_t h, int32_t w, int32_t k, int32_t window, int64_t* index, float* value, void* stream) {
+    static const char* who = "spx_nearest_protos";
+    if (!distances || !queries || !index || !value) return fail("%s: NULL distances / queries / outputs", who);
+    if (Q < 1 || Q > SPX_PBX_MAX_ROWS) return fail("%s: %d queries (1..%d)", who, Q, SPX_PBX_MAX_ROWS);
+    if (B < 1 || P < 1 || h < 1 || w < 1) return fail("%s: empty input (B=%d P=%d h=%d w=%d)", who, B, P, h, w);
+    if ((long long)P * h * w >= (1LL << 31)) return fail("%s: one image's map spans more than 2^31 elements", who);
+    if (k < 1 || k > SPX_NEAR_MAX_K) return fail("%s: k %d outside 1..%d", who, k, SPX_NEAR_MAX_K);
+    if (window < 0) return fail("%s: negative window", who);
+    if (host_queries)
+        for (int r = 0; r < Q; ++r) {
+            const int32_t* p = host_queries + 3 * (size_t)r;
+            if (p[0] < 0 || p[0] >= B || p[1] < 0 || p[1] >= h || p[2] < 0 || p[2] >= w)
+                return fail("%s: query %d = (n %d, y %d, x %d) out of range (B=%d h=%d w=%d)", who, r, p[0], p[1], p[2], B, h, w);
+        }
+    return hip_status(spx_launch_nearest_protos(distances, queries, include, Q, B, P, h, w, k, window, (long long*)index, value,
+                                                (hipStream_t)stream), who);
 }
 
 // what the three explanation-map entry points check alike

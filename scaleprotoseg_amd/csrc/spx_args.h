@@ -230,8 +230,18 @@ hipError_t spx_launch_overlap_accumulate(const float* planes, const long long* s
                                          void* workspace, hipStream_t s);
 // push bounding boxes (spx_pushbox.hip)
 hipError_t spx_launch_push_boxes(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
-                                 const float* thresholds, int R, int N, int C, int h, int w, int H, int W, int add_margin,
+                                 const float* thresholds, int per_row, int R, int N, int C, int h, int w, int H, int W, int add_margin,
                                  int32_t* rf_boxes, int32_t* crops, hipStream_t s);
+// class-restricted thresholds (spx_masked_select.hip)
+size_t spx_masked_ws_bytes(int R);
+hipError_t spx_launch_masked_thresholds(const float* planes, const long long* st, const void* labels, int label_bytes,
+                                        const int32_t* rows, int R, int N, int C, int h, int w, int H, int W, double q, void* workspace,
+                                        float* thresholds, hipStream_t s);
+// nearest-image / nearest-prototype analysis (spx_nearest.hip)
+hipError_t spx_launch_patch_majority(const void* labels, int label_bytes, const int32_t* rows, int R, int N, int h, int w, int H, int W,
+                                     int bins, int32_t* majority, hipStream_t s);
+hipError_t spx_launch_nearest_protos(const float* distances, const int32_t* queries, const uint8_t* include, int Q, int B, int P, int h,
+                                     int w, int k, int window, long long* index, float* value, hipStream_t s);
 // explanation maps (spx_explain.hip)
 hipError_t spx_launch_explain_range(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
                                     int R, int N, int C, int h, int w, int H, int W, void* workspace, hipStream_t s);

@@ -12,21 +12,10 @@
 //                            slot, popcount(b_j & b_j') per slot pair (j == j': the mask's area), 64-bit integer atomics.
 #include "spx_overlap_sample.h"
 
-#define OVL_THREADS 256
-#define OVL_BINS 2048             // bins of a histogram round (the last round uses 1024)
 #define OVL_MAX_J 32
 #define OVL_MAX_PAIRS (OVL_MAX_J * (OVL_MAX_J + 1) / 2)
 #define OVL_PAIR_REGS ((OVL_MAX_PAIRS + 63) / 64)
 #define OVL_CNT_ROWS 64           // output rows of a counting tile (64 columns wide): 16 per wave
-
-// order-preserving key of an fp32 value (-0.0 sorts directly below +0.0, NaNs at the two ends) and its inverse
-__device__ __forceinline__ uint32_t ovl_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ovl_unkey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // ---- selection -------------------------------------------------------------------------------------------------------
 // Workspace: state uint32 [N*C][4] = (prefix, rank) of the two order statistics; hist uint32 [N*C][2][OVL_BINS]; presence
@@ -45,16 +34,6 @@ __global__ __launch_bounds__(OVL_THREADS) void spx_overlap_init_kernel(uint32_t*
         state[plane * 4 + 2] = 0u;
         state[plane * 4 + 3] = k1;
     }
-}
-
-// one run of equal bins per thread: consecutive rows of a column mostly fall into one bin of the coarse rounds
-__device__ __forceinline__ void ovl_count(uint32_t* hist, int& cur, uint32_t& run, int bin) {
-    if (bin != cur) {
-        if (run) atomicAdd(&hist[cur], run);
-        cur = bin;
-        run = 0u;
-    }
-    ++run;
 }
 
 // Histogram round `round` (0, 1, 2) of the band of output rows blockIdx.x of plane (blockIdx.z, blockIdx.y).  The band's

@@ -1,7 +1,8 @@
-// What the activation-overlap metrics (spx_overlap.hip), the push bounding boxes (spx_pushbox.hip) and the explanation maps
-// (spx_explain.hip) share: the upsampled value of a pixel recomputed from the latent plane and the bands of output rows that
-// stage their latent rows in LDS (the strided view of the planes and the label read come from spx_planes.h).  ONE function,
-// compiled with -ffp-contract=off, gives a pixel the same bits in every pass of every file.
+// What the activation-overlap metrics (spx_overlap.hip), the class-restricted thresholds (spx_masked_select.hip), the push
+// bounding boxes (spx_pushbox.hip) and the explanation maps (spx_explain.hip) share: the upsampled value of a pixel recomputed
+// from the latent plane, the bands of output rows that stage their latent rows in LDS and the key and run counter of the radix
+// select (the strided view of the planes and the label read come from spx_planes.h).  ONE function, compiled with
+// -ffp-contract=off, gives a pixel the same bits in every pass of every file.
 #ifndef SPX_OVERLAP_SAMPLE_H
 #define SPX_OVERLAP_SAMPLE_H
 #include "spx_planes.h"
@@ -80,6 +81,29 @@ static inline int ovl_max_staged_rows(int h, int H, int band) {
         if (hi - lo + 1 > most) most = hi - lo + 1;
     }
     return most;
+}
+
+// ---- the exact radix select over the upsampled values (spx_overlap.hip, spx_masked_select.hip) ---------------------------
+#define OVL_THREADS 256
+#define OVL_BINS 2048             // bins of a histogram round (the last round uses 1024)
+
+// order-preserving key of an fp32 value (-0.0 sorts directly below +0.0, NaNs at the two ends) and its inverse
+__device__ __forceinline__ uint32_t ovl_key(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ovl_unkey(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// one run of equal bins per thread: consecutive rows of a column mostly fall into one bin of the coarse rounds
+__device__ __forceinline__ void ovl_count(uint32_t* hist, int& cur, uint32_t& run, int bin) {
+    if (bin != cur) {
+        if (run) atomicAdd(&hist[cur], run);
+        cur = bin;
+        run = 0u;
+    }
+    ++run;
 }
 
 #endif  // SPX_OVERLAP_SAMPLE_H

@@ -4,7 +4,9 @@
 // and walks NumPy rows on the host; here the walk runs on values recomputed from the latent plane with ovl_value() (the
 // function the thresholds were selected with: a pixel has the same bits in both), and the [H, W] map is never written.
 //
-//   row r = (n, c, class k, flat latent index f);  T = thresholds[n, c]
+//   row r = (n, c, class k, flat latent index f);  T = thresholds[n, c] (spx_push_boxes) or thresholds[r] (spx_push_boxes_rows:
+//           a threshold of the row's own, such as the class-restricted one of spx_masked_select.hip; k = -1 then masks on label 0,
+//           what the reference does for a patch whose majority label is void, and T = +inf hits nowhere)
 //   rf    = [int(i ph), int(i ph + ph) + 1, int(j pw), int(j pw + pw) + 1] with ph = H / h, pw = W / w, i = f / w, j = f % w,
 //           in double as Python computes it (the ends may exceed H, W and are stored as they are)
 //   hit(Y, X) = labels[n, Y, X] == k + 1 ? u[n, c, Y, X] >= T : 0 >= T
@@ -59,7 +61,7 @@ __device__ __forceinline__ bool pbx_any(const PbxRow& r, int Y0, int X0, int dY,
 
 __global__ __launch_bounds__(PBX_THREADS) void spx_push_boxes_kernel(SpxPlanes a, const void* __restrict__ labels, int label_bytes,
                                                                      const int32_t* __restrict__ rows, const float* __restrict__ thresholds,
-                                                                     int N, int C, int h, int w, int H, int W, int add_margin,
+                                                                     int per_row, int N, int C, int h, int w, int H, int W, int add_margin,
                                                                      int32_t* __restrict__ rf_boxes, int32_t* __restrict__ crops) {
     __shared__ int s_any[3];
     const int tid = threadIdx.x;
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(PBX_THREADS) void spx_push_boxes_kernel(SpxPlanes a
     r.labels = labels;
     r.label0 = (size_t)n * H * W;
     r.want = (long long)k + 1;
-    r.T = thresholds[(size_t)n * C + c];
+    r.T = thresholds[per_row ? row : (size_t)n * C + c];
     r.label_bytes = label_bytes;
     r.h = h;
     r.w = w;
@@ -120,9 +122,9 @@ __global__ __launch_bounds__(PBX_THREADS) void spx_push_boxes_kernel(SpxPlanes a
 }
 
 hipError_t spx_launch_push_boxes(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
-                                 const float* thresholds, int R, int N, int C, int h, int w, int H, int W, int add_margin,
+                                 const float* thresholds, int per_row, int R, int N, int C, int h, int w, int H, int W, int add_margin,
                                  int32_t* rf_boxes, int32_t* crops, hipStream_t s) {
     hipLaunchKernelGGL(spx_push_boxes_kernel, dim3((unsigned)R), dim3(PBX_THREADS), 0, s, spx_planes(planes, st), labels, label_bytes,
-                       rows, thresholds, N, C, h, w, H, W, add_margin, rf_boxes, crops);
+                       rows, thresholds, per_row, N, C, h, w, H, W, add_margin, rf_boxes, crops);
     return hipGetLastError();
 }

@@ -3,8 +3,9 @@
 Mirrors the numerical part of segmentation/push_multiscale_optimization.py (lines 34-190 and 323-335):
 ``compute_distances`` -> ``min_across_dataset`` -> ``global_min`` -> commit + de-dup.  Of the plotting half
 (``update_prototypes_on_image``, :341-685) the two integer tables ``proto_rf_boxes`` / ``proto_bound_boxes`` are computed
-(``push_box_tables``, the kernel behind ``pushbox.push_bounding_boxes``); every image and plot dump and the class-restricted
-threshold ``threshold_gt`` (used for a PNG crop only, never stored) are visualisation and are not part of this package.
+(``push_box_tables``, the kernel behind ``pushbox.push_bounding_boxes``), and on request the crop from the class-restricted
+threshold ``threshold_gt`` (:476-484, which the reference cuts a PNG from and never stores); every image and plot dump is
+visualisation and is not part of this package.
 
 ``push_prototypes_multiscale(batch_size=...)`` runs the same push in ONE pass over the data set (``push_single_pass``): images
 are encoded in batches and a ``PushTable`` on the device keeps every prototype's running winner and its feature vector
@@ -284,7 +285,7 @@ def push_single_pass(dataset, ppnet, batch_size: int = 8, void_class: Optional[i
 @torch.no_grad()
 def push_box_tables(best: torch.Tensor, list_min_patch: Optional[Sequence[torch.Tensor]], dataset, ppnet,
                     device: Optional[str] = None, q: float = 0.95, add_margin: int = 5,
-                    flat: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray]:
+                    flat: Optional[torch.Tensor] = None, gt_boxes: bool = False) -> Tuple[np.ndarray, ...]:
     """(proto_rf_boxes, proto_bound_boxes), int64 [P, 6] = [image index, h0, h1, w0, w1, class] of every prototype's winning
     patch (push_multiscale_optimization.py:254-321, 416-497), on the model as it is BEFORE the bank is overwritten.
 
@@ -293,8 +294,13 @@ def push_box_tables(best: torch.Tensor, list_min_patch: Optional[Sequence[torch.
     that image's winners only; the thresholds and the crops are ``pushbox.push_bounding_boxes``.
 
     ``flat`` (int64 [P], the winners' flat latent indices, as the single-pass push keeps them) replaces the per-image index
-    list ``list_min_patch``, which may then be None."""
+    list ``list_min_patch``, which may then be None.
+
+    ``gt_boxes=True`` appends ``proto_bound_boxes_gt``, the same table with every crop grown from the threshold over the pixels
+    of the prototype's own class only (:476-484; ``nearest.high_activation_threshold_masked`` with ``L = class + 1``), from the
+    activations already at hand."""
     from .metrics import prototype_classes
+    from .nearest import high_activation_threshold_masked
     from .pushbox import push_bounding_boxes
 
     device = device or str(ppnet.prototype_vectors.device)
@@ -315,15 +321,27 @@ def push_box_tables(best: torch.Tensor, list_min_patch: Optional[Sequence[torch.
         if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
             labels = labels.to(torch.int64)
         rows = torch.tensor([[0, j, cls_of[p], int(flat_of[p])] for j, p in enumerate(protos)], dtype=torch.int32)
-        rf, box = push_bounding_boxes(act, labels.unsqueeze(0).to(device), rows, q=q, add_margin=add_margin)
+        labels = labels.unsqueeze(0).to(device)
+        rf, box = push_bounding_boxes(act, labels, rows, q=q, add_margin=add_margin)
         order += protos
-        parts.append(torch.cat([rf, box], dim=1))
-    got = torch.cat(parts, dim=0).cpu().numpy()                              # [P, 8] in `order`
+        if gt_boxes:
+            masked = rows[:, :3].clone()
+            masked[:, 2] += 1
+            thr_gt = high_activation_threshold_masked(act, labels, masked, q)
+            parts.append(torch.cat([rf, box, push_bounding_boxes(act, labels, rows, row_thresholds=thr_gt, add_margin=add_margin)[1]], dim=1))
+        else:
+            parts.append(torch.cat([rf, box], dim=1))
+    got = torch.cat(parts, dim=0).cpu().numpy()                              # [P, 8 or 12] in `order`
     proto_rf_boxes = np.full((P, 6), -1, dtype=np.int64)
     proto_bound_boxes = np.full((P, 6), -1, dtype=np.int64)
     for r, p in enumerate(order):
         proto_rf_boxes[p] = [img_of[p], *got[r, :4], cls_of[p]]
-        proto_bound_boxes[p] = [img_of[p], *got[r, 4:], cls_of[p]]
+        proto_bound_boxes[p] = [img_of[p], *got[r, 4:8], cls_of[p]]
+    if gt_boxes:
+        proto_bound_boxes_gt = np.full((P, 6), -1, dtype=np.int64)
+        for r, p in enumerate(order):
+            proto_bound_boxes_gt[p] = [img_of[p], *got[r, 8:12], cls_of[p]]
+        return proto_rf_boxes, proto_bound_boxes, proto_bound_boxes_gt
     return proto_rf_boxes, proto_bound_boxes
 
 
@@ -363,6 +381,7 @@ def push_prototypes_multiscale(
     epoch_number: Optional[int] = None,
     proto_bound_boxes_filename_prefix: Optional[str] = None,
     batch_size: Optional[int] = None,
+    gt_boxes: bool = False,
     **_ignored,
 ):
     """Numerical part of push_multiscale_optimization.py:193-338 (the image / plot dump arguments are accepted and ignored).
@@ -384,7 +403,9 @@ def push_prototypes_multiscale(
     With ``boxes=True``, or when ``proto_bound_boxes_filename_prefix`` is given, the reference's ``proto_rf_boxes`` and
     ``proto_bound_boxes`` tables (int64 [P, 6], ``push_box_tables``) are computed before the bank is overwritten and appended
     to the result.  With ``root_dir_for_saving_prototypes``, the prefix and ``epoch_number`` all set they are also saved under
-    the reference's names (``save_box_tables``).  Not under a sharded push: with more than one rank this raises ``SpxError``."""
+    the reference's names (``save_box_tables``).  Not under a sharded push: with more than one rank this raises ``SpxError``.
+    ``gt_boxes=True`` (with the boxes) appends a sixth result, ``proto_bound_boxes_gt``: the crops from the threshold over the
+    prototype's own class (``push_box_tables``); nothing is saved for it, the reference stores none."""
     from . import dp
 
     net = unwrap(prototype_network_parallel)
@@ -415,7 +436,8 @@ def push_prototypes_multiscale(
         patch = _winning_patches(winners[0], winners[1], dataset, net, device, image_offset=rng.start, only=winners[2])
     full = dp.gather_push_patches(patch, owner, group=group)                                # [P, Cs], identical on every rank
     best_host, flat_host, patch_host = _winners_to_host(best, flat, full)                  # the single pass's one device-to-host copy
-    tables = push_box_tables(best_host, None, dataset, net, device=device, flat=flat_host) if want_boxes else None
+    tables = push_box_tables(best_host, None, dataset, net, device=device, flat=flat_host,
+                             gt_boxes=bool(gt_boxes)) if want_boxes else None
     dup = commit_push(net, patch_host.numpy().reshape(tuple(net.prototype_shape)), root_dir_for_saving_prototypes if rank == 0 else None,
                       log=log)
     if tables is not None and None not in (root_dir_for_saving_prototypes, proto_bound_boxes_filename_prefix, epoch_number):

@@ -23,8 +23,10 @@ The reference resizes, sorts and walks NumPy rows on the host once per prototype
 steps with one workgroup per row on values recomputed from the latent plane (the function the threshold select uses, so the
 two agree on every pixel); the ``[H, W]`` map is never written.
 
-Not built: the class-restricted threshold ``threshold_gt`` (the reference uses it for a PNG crop only and never stores it; it
-needs a masked select), every image and plot dump, and boxes under a sharded (``torch.distributed``) push.
+The class-restricted crop (the reference's ``threshold_gt`` / ``_gt`` crop, :476-484) is the same walk from a threshold of the
+row's own: ``row_thresholds=`` (``spx_push_boxes_rows``), selected by ``nearest.high_activation_threshold_masked``.
+
+Not built: every image and plot dump, and boxes under a sharded (``torch.distributed``) push.
 """
 from __future__ import annotations
 
@@ -53,7 +55,8 @@ def _select_for(lib, planes: torch.Tensor, pairs: torch.Tensor, size, q: float) 
 
 
 def push_bounding_boxes(activations: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, *, thresholds: Optional[torch.Tensor] = None,
-                        q: float = 0.95, add_margin: int = 5, grid: Optional[Tuple[int, int]] = None):
+                        q: float = 0.95, add_margin: int = 5, grid: Optional[Tuple[int, int]] = None,
+                        row_thresholds: Optional[torch.Tensor] = None):
     """(rf_boxes, bound_boxes), int64 [R, 4] device tensors ``(h0, h1, w0, w1)`` with exclusive ends, as the module's header
     defines them.
 
@@ -61,10 +64,14 @@ def push_bounding_boxes(activations: torch.Tensor, labels: torch.Tensor, rows: t
     uint8 / int32 / int64 on the device; its shape is the image size.  ``rows``: integer [R, 4] = (n, c, class, flat latent
     index).  A host tensor is checked on the host (a row out of range raises) and uploaded; a device tensor is never read by
     the host, and a row out of range comes back as -1.  ``thresholds``: fp32 [N, C] as ``high_activation_threshold`` returns
-    them; None selects them at ``q`` for exactly the planes the rows name.  Enqueues work on the current stream only; never
-    synchronises."""
+    them; None selects them at ``q`` for exactly the planes the rows name.  ``row_thresholds``: fp32 [R], one threshold per row
+    instead (``thresholds`` must then be None); only with it may a row name class -1, which masks on label 0 as the reference
+    does for a patch whose majority label is void, and a ``+inf`` entry leaves the crop at the patch box plus the margin.
+    Enqueues work on the current stream only; never synchronises."""
     lib = _lib.load()
     _rank(q, 2)
+    if thresholds is not None and row_thresholds is not None:
+        raise SpxError("pass thresholds= ([N, C]) or row_thresholds= ([R]), not both")
     planes = _maps.planes(activations, grid, "activations")
     N, Cn, h, w = (int(v) for v in planes.shape)
     H, W = _maps.label_map(labels, N, "activations")
@@ -77,7 +84,9 @@ def push_bounding_boxes(activations: torch.Tensor, labels: torch.Tensor, rows: t
         host_rows = rows.to(torch.int32).contiguous()
         if not torch.equal(host_rows.to(torch.int64), rows):
             raise SpxError("rows do not fit int32")
-        if thresholds is None:                     # the select below reads the planes the rows name
+        if row_thresholds is None:
+            _maps.bad_row(rows, rows[:, 2] < 0, "class -1 (a void patch) needs row_thresholds=")
+        if thresholds is None and row_thresholds is None:      # the select below reads the planes the rows name
             n, c = rows[:, 0], rows[:, 1]
             _maps.bad_row(rows, (n < 0) | (n >= N) | (c < 0) | (c >= Cn), f"no plane of N={N}, C={Cn}")
     R = int(rows.shape[0])
@@ -88,7 +97,12 @@ def push_bounding_boxes(activations: torch.Tensor, labels: torch.Tensor, rows: t
         if rows.device != planes.device:
             raise SpxError(f"rows are on {rows.device}, activations on {planes.device}")
         dev_rows = rows.detach().to(torch.int32).contiguous()
-    if thresholds is None:
+    if row_thresholds is not None:
+        _lib.require_gpu(row_thresholds, "row_thresholds")
+        if row_thresholds.dtype != torch.float32 or tuple(row_thresholds.shape) != (R,) or row_thresholds.device != planes.device:
+            raise SpxError(f"row_thresholds must be fp32 [{R}] on {planes.device}")
+        thresholds = row_thresholds.detach().contiguous()
+    elif thresholds is None:
         if host_rows is not None:
             pairs = torch.unique(rows[:, :2], dim=0).to(planes.device)
         else:                                      # no host read: one select per row, rows out of range fold onto plane (0, 0)
@@ -103,7 +117,8 @@ def push_bounding_boxes(activations: torch.Tensor, labels: torch.Tensor, rows: t
         thresholds = thresholds.detach().contiguous()
     rf = torch.empty(R, 4, dtype=torch.int32, device=planes.device)
     box = torch.empty(R, 4, dtype=torch.int32, device=planes.device)
-    _lib.check(lib.spx_push_boxes(planes.data_ptr(), strides(planes), lab.data_ptr(), LABEL_BYTES[lab.dtype],
-                                  _lib.ptr(dev_rows), None if host_rows is None else host_rows.data_ptr(), _lib.ptr(thresholds), R, N,
-                                  Cn, h, w, H, W, int(add_margin), _lib.ptr(rf), _lib.ptr(box), _lib.stream_ptr()))
+    entry = lib.spx_push_boxes if row_thresholds is None else lib.spx_push_boxes_rows
+    _lib.check(entry(planes.data_ptr(), strides(planes), lab.data_ptr(), LABEL_BYTES[lab.dtype],
+                     _lib.ptr(dev_rows), None if host_rows is None else host_rows.data_ptr(), _lib.ptr(thresholds), R, N,
+                     Cn, h, w, H, W, int(add_margin), _lib.ptr(rf), _lib.ptr(box), _lib.stream_ptr()))
     return rf.to(torch.int64), box.to(torch.int64)
