@@ -9,9 +9,10 @@
 //                                   d = hi - lo;  heat = (uint8) trunc(255 * ((m - lo) / d)) in fp32;  d == 0: all zeros
 //   dominant row r = (n, class k):  dom = labels[n] == k + 1 ? the first argmax over the class's slots j of wgt[k, j] * u_j : 255
 //
-//   spx_explain_range     lo / hi of every heat row: bands of output rows, the band's latent rows staged in LDS, minima and
-//                         maxima of the order-preserving uint32 key folded by wave shuffles, then integer atomics per row
-//                         (min and max do not depend on the order: run-to-run identical, no float atomics).
+//   spx_explain_range     lo / hi of every heat row: the staged bands of output rows and their pixel walk of
+//                         spx_overlap_sample.h (ovl_stage_band, ovl_walk_band), minima and maxima of the order-preserving
+//                         uint32 key folded by wave shuffles, then integer atomics per row (min and max do not depend on the
+//                         order: run-to-run identical, no float atomics).
 //   spx_explain_heat      the bytes of every heat row.
 //   spx_explain_dominant  the bytes of every dominant row: the taps of a pixel are formed once, the slots change the plane only.
 // The two byte kernels share exp_store(): lanes are assigned by the ADDRESS of the output dword, so each lane forms four
@@ -31,7 +32,7 @@ struct ExpLabels {
 
 // ---- range -------------------------------------------------------------------------------------------------------------
 // Band blockIdx.x of heat row blockIdx.y.  keys uint32 [2][R]: running minimum (initialised to all ones) and maximum (zero) of
-// float_key(m).  Wave v takes the band's rows v, v + 4, ..., lane l the columns l, l + 64, ... (the labels are read along X).
+// float_key(m).  The labels are read along X, as the walk goes.
 __global__ __launch_bounds__(EXP_THREADS) void spx_explain_range_kernel(SpxPlanes a, ExpLabels labels, const int32_t* __restrict__ rows,
                                                                         int R, int N, int C, int h, int w, int H, int W, int band_rows,
                                                                         uint32_t* __restrict__ keys) {
@@ -42,37 +43,20 @@ __global__ __launch_bounds__(EXP_THREADS) void spx_explain_range_kernel(SpxPlane
     const int tid = threadIdx.x, r = blockIdx.y;
     const int n = rows[r * 3 + 0], c = rows[r * 3 + 1];
     const long long want = (long long)rows[r * 3 + 2] + 1;
-    if (n < 0 || n >= N || c < 0 || c >= C) return;             // workgroup-uniform; the entry point has refused such a row
-    const int Y0 = blockIdx.x * band_rows, Y1 = min(H, Y0 + band_rows), nrows = Y1 - Y0;
-    int i0, i1;
-    float t;
-    ovl_coord(Y0, h, H, i0, t);
-    ovl_coord(Y1 - 1, h, H, i1, t);
-    const int lo = ovl_clamp(i0 - 1, h - 1), hi = ovl_clamp(i1 + 2, h - 1);
-    const int nstage = (hi - lo + 1) * w;                       // <= OVL_STAGE: checked at the launch
-    for (int i = tid; i < nrows; i += EXP_THREADS) ovl_axis(Y0 + i, h, H, lo, w, &s_oy[4 * i], &s_wy[4 * i]);
-    const float* src = a.p + (long long)n * a.sn + (long long)c * a.sc;
-    for (int i = tid; i < nstage; i += EXP_THREADS) {
-        const int y = i / w, x = i - y * w;
-        s_stage[i] = src[(long long)(lo + y) * a.sy + (long long)x * a.sx];
-    }
-    __syncthreads();
+    if (!ovl_plane_ok(n, c, N, C)) return;                      // workgroup-uniform; the entry point has refused such a row
+    const int Y0 = blockIdx.x * band_rows, nrows = min(H, Y0 + band_rows) - Y0;
+    ovl_stage_band<EXP_THREADS>(a, n, c, h, w, H, Y0, nrows, s_oy, s_wy, s_stage, nullptr, 0);
     const int wave = tid >> 6, lane = tid & 63;
     const size_t label0 = (size_t)n * H * W;
     uint32_t klo = 0xffffffffu, khi = 0u;
-    for (int X = lane; X < W; X += 64) {
-        int ox[4];
-        float wx[4];
-        ovl_axis(X, w, W, 0, 1, ox, wx);
-        for (int i = wave; i < nrows; i += EXP_THREADS / 64) {
-            float m = 0.0f;
-            if (spx_label(labels.p, labels.bytes, label0 + (size_t)(Y0 + i) * W + X) == want)
-                m = ovl_value(s_stage, &s_oy[4 * i], &s_wy[4 * i], ox, wx);
-            const uint32_t key = float_key(m);
-            klo = min(klo, key);
-            khi = max(khi, key);
-        }
-    }
+    ovl_walk_band<EXP_THREADS>(w, W, nrows, [&](int i, int X, const int* ox, const float* wx) {
+        float m = 0.0f;
+        if (spx_label(labels.p, labels.bytes, label0 + (size_t)(Y0 + i) * W + X) == want)
+            m = ovl_value(s_stage, &s_oy[4 * i], &s_wy[4 * i], ox, wx);
+        const uint32_t key = float_key(m);
+        klo = min(klo, key);
+        khi = max(khi, key);
+    });
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         klo = min(klo, (uint32_t)__shfl_xor(klo, off));
@@ -95,9 +79,8 @@ __global__ __launch_bounds__(EXP_THREADS) void spx_explain_range_kernel(SpxPlane
 
 hipError_t spx_launch_explain_range(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
                                     int R, int N, int C, int h, int w, int H, int W, void* workspace, hipStream_t s) {
-    int band = ovl_band_rows(h, w, H);
-    if (band > EXP_BAND) band = EXP_BAND;
-    if (band < 1 || (long long)ovl_max_staged_rows(h, H, band) * w > OVL_STAGE) return hipErrorInvalidValue;
+    const int band = ovl_band_plan(h, w, H, EXP_BAND);
+    if (!band) return hipErrorInvalidValue;
     uint32_t* keys = (uint32_t*)workspace;
     hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)R * 4, s);
     if (e != hipSuccess) return e;
@@ -188,7 +171,7 @@ __global__ __launch_bounds__(EXP_THREADS) void spx_explain_heat_kernel(SpxPlanes
                                                                        float* __restrict__ ranges) {
     const int r = blockIdx.y;
     const int n = rows[r * 3 + 0], c = rows[r * 3 + 1];
-    if (n < 0 || n >= N || c < 0 || c >= C) return;             // workgroup-uniform; the entry point has refused such a row
+    if (!ovl_plane_ok(n, c, N, C)) return;                      // workgroup-uniform; the entry point has refused such a row
     ExpHeatPixel px;
     px.a = a;
     px.labels = labels;

@@ -5,9 +5,8 @@
 // and because that is ONE function compiled with -ffp-contract=off the value of a pixel is the same bits in every pass - the
 // selection that finds the threshold and the comparison that builds the mask agree on every pixel.
 //
-//   spx_overlap_thresholds   radix select of the order statistics v[k], v[k1] of each plane over the order-preserving uint32
-//                            key of the fp32 value: three histogram rounds of 11 / 11 / 10 key bits, a one-workgroup scan per
-//                            plane between them; T = numpy's _lerp(v[k], v[k1], gamma) in fp32.
+//   spx_overlap_thresholds   the radix select of spx_overlap_sample.h for the order statistics v[k], v[k1] of every plane over
+//                            all its pixels, the ranks given by the host; T = numpy's _lerp(v[k], v[k1], gamma) in fp32.
 //   spx_overlap_accumulate   class presence from the labels, then per (image, present class, pixel tile): one ballot per
 //                            slot, popcount(b_j & b_j') per slot pair (j == j': the mask's area), 64-bit integer atomics.
 #include "spx_overlap_sample.h"
@@ -18,16 +17,15 @@
 #define OVL_CNT_ROWS 64           // output rows of a counting tile (64 columns wide): 16 per wave
 
 // ---- selection -------------------------------------------------------------------------------------------------------
-// Workspace: state uint32 [N*C][4] = (prefix, rank) of the two order statistics; hist uint32 [N*C][2][OVL_BINS]; presence
-// int32 [N][K].  Nothing depends on H or W.
+// Workspace: state uint32 [N*C][4], hist uint32 [N*C][2][OVL_BINS] (the select's, per plane); presence int32 [N][K].  Nothing
+// depends on H or W.
 static inline size_t ovl_state_bytes(long long planes) { return (size_t)planes * 16; }
 static inline size_t ovl_hist_bytes(long long planes) { return (size_t)planes * 2 * OVL_BINS * 4; }
 
 __global__ __launch_bounds__(OVL_THREADS) void spx_overlap_init_kernel(uint32_t* __restrict__ state, uint32_t* __restrict__ hist,
                                                                        uint32_t k0, uint32_t k1) {
     const size_t plane = blockIdx.x;
-    uint32_t* hq = hist + plane * 2 * OVL_BINS;
-    for (int i = threadIdx.x; i < 2 * OVL_BINS; i += OVL_THREADS) hq[i] = 0u;
+    ovl_clear_hist(hist + plane * 2 * OVL_BINS);
     if (threadIdx.x == 0) {
         state[plane * 4 + 0] = 0u;
         state[plane * 4 + 1] = k0;
@@ -36,107 +34,22 @@ __global__ __launch_bounds__(OVL_THREADS) void spx_overlap_init_kernel(uint32_t*
     }
 }
 
-// Histogram round `round` (0, 1, 2) of the band of output rows blockIdx.x of plane (blockIdx.z, blockIdx.y).  The band's
-// latent rows plus the halo of the cubic taps are staged in LDS; wave v takes the band's rows v, v + 4, ..., lane l the
-// columns l, l + 64, ...
+// band blockIdx.x of plane (blockIdx.z, blockIdx.y), every pixel
 __global__ __launch_bounds__(OVL_THREADS) void spx_overlap_hist_kernel(SpxPlanes a, int C, int h, int w, int H, int W, int band_rows,
                                                                        int round, const uint32_t* __restrict__ state,
                                                                        uint32_t* __restrict__ hist) {
-    __shared__ float s_stage[OVL_STAGE];
-    __shared__ uint32_t s_hist[2 * OVL_BINS];
-    __shared__ int s_oy[OVL_BAND * 4];
-    __shared__ float s_wy[OVL_BAND * 4];
-    const int tid = threadIdx.x, c = blockIdx.y, n = blockIdx.z;
+    const int c = blockIdx.y, n = blockIdx.z;
     const size_t plane = (size_t)n * C + c;
-    const int Y0 = blockIdx.x * band_rows, Y1 = min(H, Y0 + band_rows), rows = Y1 - Y0;
-    int i0, i1;
-    float t;
-    ovl_coord(Y0, h, H, i0, t);
-    ovl_coord(Y1 - 1, h, H, i1, t);
-    const int lo = ovl_clamp(i0 - 1, h - 1), hi = ovl_clamp(i1 + 2, h - 1);
-    const int nstage = (hi - lo + 1) * w;                       // <= OVL_STAGE: ovl_band_rows, checked again at the launch
-    for (int i = tid; i < 2 * OVL_BINS; i += OVL_THREADS) s_hist[i] = 0u;
-    for (int r = tid; r < rows; r += OVL_THREADS) ovl_axis(Y0 + r, h, H, lo, w, &s_oy[4 * r], &s_wy[4 * r]);
-    const float* src = a.p + (long long)n * a.sn + (long long)c * a.sc;
-    for (int i = tid; i < nstage; i += OVL_THREADS) {
-        const int y = i / w, x = i - y * w;
-        s_stage[i] = src[(long long)(lo + y) * a.sy + (long long)x * a.sx];
-    }
-    __syncthreads();
-    const uint32_t p0 = state[plane * 4 + 0], p1 = state[plane * 4 + 2];
-    const int wave = tid >> 6, lane = tid & 63;
-    int cur0 = 0, cur1 = 0;
-    uint32_t run0 = 0u, run1 = 0u;
-    for (int X = lane; X < W; X += 64) {
-        int ox[4];
-        float wx[4];
-        ovl_axis(X, w, W, 0, 1, ox, wx);
-        for (int r = wave; r < rows; r += 4) {
-            const uint32_t key = ovl_key(ovl_value(s_stage, &s_oy[4 * r], &s_wy[4 * r], ox, wx));
-            if (round == 0) {
-                ovl_count(s_hist, cur0, run0, (int)(key >> 21));
-            } else if (round == 1) {
-                if ((key >> 21) == p0) ovl_count(s_hist, cur0, run0, (int)((key >> 10) & 2047u));
-                if ((key >> 21) == p1) ovl_count(s_hist + OVL_BINS, cur1, run1, (int)((key >> 10) & 2047u));
-            } else {
-                if ((key >> 10) == p0) ovl_count(s_hist, cur0, run0, (int)(key & 1023u));
-                if ((key >> 10) == p1) ovl_count(s_hist + OVL_BINS, cur1, run1, (int)(key & 1023u));
-            }
-        }
-    }
-    if (run0) atomicAdd(&s_hist[cur0], run0);
-    if (run1) atomicAdd(&s_hist[OVL_BINS + cur1], run1);
-    __syncthreads();
-    uint32_t* hq = hist + plane * 2 * OVL_BINS;
-    for (int i = tid; i < 2 * OVL_BINS; i += OVL_THREADS) {
-        const uint32_t v = s_hist[i];
-        if (v) atomicAdd(&hq[i], v);
-    }
+    ovl_hist_round<false>(a, n, c, h, w, H, W, band_rows, round, state + plane * 4, hist + plane * 2 * OVL_BINS, OvlClass{});
 }
 
-// Between the rounds, one workgroup per plane: for each of the two ranks the bin that holds it (the first bin whose running
-// count exceeds the rank), the rank inside that bin, the key prefix extended by the bin; the histograms zeroed for the next
-// round.  After the last round the keys are complete: T = numpy's _lerp of the two values, in fp32.
+// plane blockIdx.x; the ranks are in the state from the start
 __global__ __launch_bounds__(OVL_THREADS) void spx_overlap_scan_kernel(int round, uint32_t* __restrict__ state, uint32_t* __restrict__ hist,
                                                                        float gamma, float* __restrict__ thresholds) {
-    __shared__ uint32_t s_sum[OVL_THREADS];
-    const int tid = threadIdx.x;
     const size_t plane = blockIdx.x;
-    const int bits = round == 2 ? 10 : 11, per = (1 << bits) / OVL_THREADS;     // 8 or 4 consecutive bins per thread
-    uint32_t* hq = hist + plane * 2 * OVL_BINS;
-    for (int r = 0; r < 2; ++r) {
-        const uint32_t* hr = hq + (round == 0 ? 0 : r * OVL_BINS);              // round 0: one histogram serves both ranks
-        uint32_t mine = 0u;
-        for (int i = 0; i < per; ++i) mine += hr[tid * per + i];
-        s_sum[tid] = mine;
-        __syncthreads();
-        for (int off = 1; off < OVL_THREADS; off <<= 1) {
-            const uint32_t add = tid >= off ? s_sum[tid - off] : 0u;
-            __syncthreads();
-            s_sum[tid] += add;
-            __syncthreads();
-        }
-        const uint32_t rank = state[plane * 4 + 2 * r + 1];
-        uint32_t below = s_sum[tid] - mine;
-        __syncthreads();                                                         // every thread has read its rank and sums
-        if (rank >= below && rank < below + mine) {                              // exactly one thread
-            int b = tid * per;
-            for (;; ++b) {
-                const uint32_t cnt = hr[b];
-                if (rank < below + cnt) break;
-                below += cnt;
-            }
-            state[plane * 4 + 2 * r] = (state[plane * 4 + 2 * r] << bits) | (uint32_t)b;
-            state[plane * 4 + 2 * r + 1] = rank - below;
-        }
-        __syncthreads();
-    }
-    for (int i = tid; i < 2 * OVL_BINS; i += OVL_THREADS) hq[i] = 0u;
-    if (round == 2 && tid == 0) {
-        const float lo = ovl_unkey(state[plane * 4 + 0]), hi = ovl_unkey(state[plane * 4 + 2]);
-        const float d = hi - lo;
-        thresholds[plane] = gamma >= 0.5f ? hi - d * (1.0f - gamma) : lo + d * gamma;
-    }
+    uint32_t* st = state + plane * 4;
+    ovl_scan_round(round, st, hist + plane * 2 * OVL_BINS, [&](int r) { return st[2 * r + 1]; });
+    if (round == 2 && threadIdx.x == 0) thresholds[plane] = ovl_lerp(ovl_unkey(st[0]), ovl_unkey(st[2]), gamma);
 }
 
 size_t spx_overlap_ws_bytes(int N, int C, int K) {
@@ -150,8 +63,8 @@ hipError_t spx_launch_overlap_thresholds(const float* planes, const long long* s
     uint32_t* state = (uint32_t*)workspace;
     uint32_t* hist = (uint32_t*)((char*)workspace + ovl_state_bytes(np));
     const long long k1 = k + 1 < HW ? k + 1 : HW - 1;
-    const int band = ovl_band_rows(h, w, H);
-    if (band < 1 || (long long)ovl_max_staged_rows(h, H, band) * w > OVL_STAGE) return hipErrorInvalidValue;
+    const int band = ovl_band_plan(h, w, H);
+    if (!band) return hipErrorInvalidValue;
     hipLaunchKernelGGL(spx_overlap_init_kernel, dim3((unsigned)np), dim3(OVL_THREADS), 0, s, state, hist, (uint32_t)k, (uint32_t)k1);
     const dim3 grid((unsigned)((H + band - 1) / band), (unsigned)C, (unsigned)N);
     const SpxPlanes a = spx_planes(planes, st);

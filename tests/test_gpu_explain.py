@@ -20,8 +20,8 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import explain_restatement as E  # noqa: E402
 import overlap_restatement as OR  # noqa: E402
-from map_cases import EXPLAIN_CASES as CASES, class_planes, planes_of, weights_of  # noqa: E402
-from support import gpu_device, group_net  # noqa: E402
+from map_cases import BAND_EDGE_WIDE, EXPLAIN_CASES as CASES, band_edge_case, class_planes, planes_of, weights_of  # noqa: E402
+from support import bits_equal, gpu_device, group_net  # noqa: E402
 from support import release_cached_blocks  # noqa: E402,F401  (a module-scoped autouse fixture, taken by importing its name)
 
 pytestmark = pytest.mark.gpu
@@ -214,6 +214,28 @@ def test_513_against_the_restatement_and_itself():
     heat2, ranges2 = spx.activation_heat_maps(act, lab, rows, table)
     assert torch.equal(heat2, heat) and torch.equal(ranges2.view(torch.int32), ranges.view(torch.int32))
     assert torch.equal(spx.dominant_slot_maps(act, lab, rows2, table, weights=wgt), dom)
+
+
+# ---- 129 x 65 -> 140 x 70: five bands over a plane that no band stages whole, tied to the masked select ----------------------
+def test_ranges_of_a_partially_staged_plane_hold_the_selects_own_pixels():
+    """A class of one pixel has the range (min(0, v), max(0, v)), and v is the class's masked threshold: the range pass and the
+    select recompute that pixel from their own staged rows, and the bits are the same.  A class across the edge of a band
+    against the restatement."""
+    import scaleprotoseg_amd as spx
+
+    dev = gpu_device()
+    c = band_edge_case("partially_staged_129x65")
+    act, lab = torch.from_numpy(c["planes"]).to(dev), torch.from_numpy(c["labels"]).to(dev)
+    table = torch.tensor([[0, 1]] * BAND_EDGE_WIDE)
+    lone = [(L, j) for L in c["lone"] for j in range(2)]
+    rows = torch.tensor([(0, L - 1, j) for L, j in lone] + [(0, BAND_EDGE_WIDE - 1, 0)])
+    _, ranges = spx.activation_heat_maps(act, lab, rows, table)
+    v = spx.high_activation_threshold_masked(act, lab, torch.tensor([(0, j, L) for L, j in lone]))
+    assert torch.isfinite(v).all()
+    zero = torch.zeros_like(v)
+    assert bits_equal(ranges[:len(lone)], torch.stack([torch.minimum(v, zero), torch.maximum(v, zero)], dim=1))
+    _, lo, hi = E.heat_map(c["planes"][0, 0], c["labels"][0], BAND_EDGE_WIDE - 1)
+    assert lo < 0 < hi and np.abs(ranges[-1].cpu().numpy() - np.array([lo, hi])).max() <= OR.margin(c["planes"][0, 0])
 
 
 # ---- the module ------------------------------------------------------------------------------------------------------------

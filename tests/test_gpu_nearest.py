@@ -22,6 +22,7 @@ if HERE not in sys.path:
 import nearest_restatement as NR  # noqa: E402
 import overlap_restatement as R  # noqa: E402
 import push_boxes_restatement as PB  # noqa: E402
+from map_cases import BAND_EDGES, band_edge_case  # noqa: E402
 from nearest_cases import CROP_CASES, NEAREST, crop_case  # noqa: E402
 from support import bits_equal, gpu_device, ListData, proto_net  # noqa: E402
 from support import release_cached_blocks  # noqa: E402,F401  (a module-scoped autouse fixture, taken by importing its name)
@@ -115,6 +116,24 @@ def test_counts_of_one_and_two_dtypes_views_and_repeats():
     keep = torch.ones(len(rows), dtype=torch.bool)
     keep[[1, 4]] = False
     assert torch.isnan(got[~keep.to(dev)]).all() and bits_equal(got[keep.to(dev)], T[keep.to(dev)])
+
+
+@pytest.mark.parametrize("name", sorted(BAND_EDGES))
+def test_classes_at_the_edges_of_the_bands(name):
+    """A class whose rows lie in two bands, and classes of one pixel in the last band and on the first and the last row of a
+    band: the threshold of a lone pixel is that pixel's value."""
+    import scaleprotoseg_amd as spx
+
+    dev = gpu_device()
+    c = band_edge_case(name)
+    planes, labels = c["planes"], c["labels"]
+    rows = np.array([[0, ch, L] for ch in range(2) for L in [1] + c["lone"]], np.int64)
+    up = [R.upsample(planes[0, ch], labels.shape[1:]).astype(np.float32) for ch in range(2)]
+    want = np.array([NR.masked_threshold(up[ch], labels[0] == L) for _, ch, L in rows])
+    assert all((labels[0] == L).sum() == 1 for L in c["lone"]) and np.isfinite(want).all()
+    T = spx.high_activation_threshold_masked(torch.from_numpy(planes).to(dev), torch.from_numpy(labels).to(dev), torch.from_numpy(rows))
+    assert torch.isfinite(T).all()
+    _within(name, T.cpu().numpy(), want, [planes[0, ch] for _, ch, _ in rows])
 
 
 # ---- patch majority ---------------------------------------------------------------------------------------------------
