@@ -15,6 +15,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from ._gathered import row_class_slots
 from ._lib import SpxError, SpxPlan
 
 ACT_FN = {"log": 0, "linear": 1}
@@ -148,34 +149,24 @@ class ClassGather:
 
 def class_gather_table(layout: BankLayout, prototype_class_identity: torch.Tensor, device) -> Tuple[torch.Tensor, int, torch.Tensor]:
     """(keys, J, table) for ClassGather from the module's prototype_class_identity [P, K]
-    (segmentation/model/model_multiscale.py:132-141: one-hot rows, possibly all-zero rows)."""
+    (segmentation/model/model_multiscale.py:132-141: one-hot rows, possibly all-zero rows), by the row-wise slot rule of
+    ``_gathered.row_class_slots``."""
     ident = prototype_class_identity.detach().cpu()
     P, K = ident.shape
     if P != layout.num_prototypes:
         raise SpxError(f"class identity has {P} rows, bank has {layout.num_prototypes}")
-    has = ident.sum(dim=1) > 0
-    cls = torch.where(has, ident.argmax(dim=1), torch.full((P,), -1, dtype=torch.long))
-    slot = torch.zeros(P, dtype=torch.long)
-    counts = [0] * K
-    for p in range(P):
-        c = int(cls[p])
-        if c >= 0:
-            slot[p] = counts[c]
-            counts[c] += 1
-    J = max(1, max(counts) if counts else 1)
+    cls, slot = row_class_slots(ident)
+    own = cls >= 0
+    J = max(1, int(slot.max()) + 1 if bool(own.any()) else 1)
     table = torch.full((K, J), -1, dtype=torch.long)
-    for p in range(P):
-        if int(cls[p]) >= 0:
-            table[int(cls[p]), int(slot[p])] = p
+    table[cls[own], slot[own]] = torch.arange(P)[own]
+    key = torch.where(own, (cls << 16) | slot, torch.full_like(cls, -1))
     plan = layout.plan()
     rows = plan.npb * 32
     keys = torch.full((plan.npanels * rows,), -1, dtype=torch.int64)
     for q in range(plan.npanels):
         p0, n = plan.panel_p0[q], plan.panel_np[q]
-        for r_ in range(n):
-            p = p0 + r_
-            if int(cls[p]) >= 0:
-                keys[q * rows + r_] = (int(cls[p]) << 16) | int(slot[p])
+        keys[q * rows:q * rows + n] = key[p0:p0 + n]
     keys = torch.where(keys < 0, torch.full_like(keys, 0xFFFFFFFF), keys)
     keys32 = (keys & 0xFFFFFFFF).to(torch.int64)
     keys32 = torch.where(keys32 >= 2**31, keys32 - 2**32, keys32).to(torch.int32)   # same bits as uint32

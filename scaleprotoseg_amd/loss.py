@@ -12,81 +12,16 @@ algebra that the tests hold the kernels against is test infrastructure and lives
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
 from typing import Dict, Optional, Tuple, Union
 
 import torch
 from torch import nn
 
-from . import _lib
+from . import _gathered, _lib
 from ._cache import cached
+from ._gathered import ClassDistances, Gathered, class_slot_table, gather_class_distances, slot_scale_table  # noqa: F401
 from ._lib import SpxError
 from .functional import cross_entropy_from_logits
-
-
-@dataclass
-class ClassDistances:
-    """values [B, J, H*W] (slot planes: entry (j, px) = distance to prototype j of the pixel's class), labels [B, H*W] int
-    (class 0..K-1, anything else = no class), table [K, J] prototype index of (class, slot) or -1.
-
-    The planes belong to the labels they were gathered under.  ``KLDLoss`` and ``ActivationRegularizers`` take the label
-    map they are called with: handed ``target`` itself, unedited, they use ``labels`` as they are (no further launch); handed any
-    other tensor (or ``target`` after an in-place edit) they shift that map and compare it with ``labels`` on the device.  Equal
-    classes at every pixel (a clone, a reloaded batch) give the same value.  If a single pixel has another class the planes
-    hold the wrong prototypes' distances for it and cannot be gathered again from here, so the loss - and with it every
-    gradient - is NaN instead of a finite number that belongs to neither label map (no host synchronisation: the NaN is
-    made on the device).  Run the forward again with the new labels."""
-
-    values: torch.Tensor
-    labels: torch.Tensor
-    table: torch.Tensor
-    grid: Tuple[int, int]
-    # the target map ``labels`` was derived from (labels = target - 1) and its version then: a loss that is handed this very
-    # tensor takes ``labels`` as they are instead of shifting and converting the map a second time
-    target: Optional[torch.Tensor] = None
-    target_version: int = -1
-
-
-def class_slot_table(prototype_class_identity: torch.Tensor) -> torch.Tensor:
-    """[K, J] prototype index of (class, slot); slot = rank among the class's prototypes (ascending index)."""
-    ident = prototype_class_identity.detach().cpu()
-    P, K = ident.shape
-    per = [torch.nonzero(ident[:, c]).flatten().tolist() for c in range(K)]
-    J = max(1, max(len(x) for x in per))
-    table = torch.full((K, J), -1, dtype=torch.long)
-    for c in range(K):
-        for j, p in enumerate(per[c]):
-            table[c, j] = p
-    return table
-
-
-def gather_class_distances(prototype_distances: torch.Tensor, labels0: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
-    """torch gather of the P-wide map into the class-gathered form (used when KLDLoss is given the full map)."""
-    B, P = prototype_distances.shape[:2]
-    K, J = table.shape
-    d = prototype_distances.reshape(B, P, -1).permute(0, 2, 1)
-    lab = labels0.reshape(B, -1).long()
-    ok = (lab >= 0) & (lab < K)
-    idx = table.to(d.device)[lab.clamp(0, K - 1)]
-    valid = ok.unsqueeze(-1) & (idx >= 0)
-    out = torch.gather(d, 2, idx.clamp(min=0))
-    return torch.where(valid, out, torch.zeros_like(out))
-
-
-def _labels_of(cd: ClassDistances, target_labels: torch.Tensor):
-    """(labels0 [B, H*W], poison or None) for a loss that is handed ``cd`` and ``target_labels``: ``cd.labels`` when the map is
-    the very tensor the planes were gathered under; else the shifted map and a device scalar that is 1 where it names the same
-    class at every pixel (out-of-range values are all "no class") and NaN otherwise - see ``ClassDistances``."""
-    if cd.target is target_labels and cd.target_version == target_labels._version:
-        return cd.labels, None                                                    # already target - 1 (int32)
-    labels0 = target_labels.reshape(target_labels.shape[0], -1).long() - 1      # loss.py:73
-    K = int(cd.table.shape[0])
-    cls = lambda t: torch.where((t >= 0) & (t < K), t, torch.full_like(t, -1))
-    mine = cd.labels.reshape(cd.labels.shape[0], -1).long()
-    if labels0.shape != mine.shape:
-        raise SpxError(f"labels {tuple(target_labels.shape)} do not match the ClassDistances' {tuple(mine.shape)} pixels")
-    differ = (cls(labels0.to(mine.device)) != cls(mine)).any()
-    return labels0, torch.where(differ, float("nan"), 1.0)
 
 
 class PixelWiseCrossEntropyLoss(nn.Module):
@@ -123,13 +58,6 @@ class PixelWiseCrossEntropyLoss(nn.Module):
         return fused.loss, correct[mask]
 
 
-def _kld_kernels_usable(vals: torch.Tensor, K: int, J: int) -> bool:
-    # fp32 planes on the GPU, at most 16 slots per class; the [K, J] segment tables of the reduction passes must fit the LDS
-    # (K*J*12 + K*4 bytes <= 60 KiB: 150 x 12 and 182 x 12 of the reference's ADE / COCO configs take 22 / 27 KiB); the
-    # [K, J, J] tables of the pair and gradient passes are tiled over class blocks and set no limit
-    return vals.is_cuda and vals.dtype == torch.float32 and J <= 16 and K * J * 12 + K * 4 + 8 <= 60 * 1024
-
-
 def _kld_segment_passes(lib, v, lab, K, Wk, s):
     """The three reduction passes over the gathered planes (csrc/spx_kld.hip): (a_fx int64 [B,K,J,J], counts [B,K], lse [B,K,J],
     scale double [1]).  One zero-filled workspace holds the integer tables: [a_fx | ssum_fx | scale | keys | counts | range keys];
@@ -157,14 +85,13 @@ class _KLDFusedLoss(torch.autograd.Function):
     gradient with respect to the pair sums, loss.py:113-142); backward: one scalar multiply + the per-pixel gradient pass."""
 
     @staticmethod
-    def forward(ctx, vals, labels, K, W, pair_ok):
+    def forward(ctx, planes, g, pair_ok):
         lib = _lib.load()
-        B, J, HW = vals.shape
-        v = vals.detach().contiguous()
-        lab = labels.to(device=v.device, dtype=torch.int32).contiguous()
+        v, lab = _gathered.launch_operands(g)                                   # g.planes is ``planes``
+        B, J, HW = v.shape
+        K = g.table.shape[0]
         s = _lib.stream_ptr()
-        Wk = int(W) if W and HW % int(W) == 0 else 0
-        a_fx, counts, lse, scale = _kld_segment_passes(lib, v, lab, K, Wk, s)
+        a_fx, counts, lse, scale = _kld_segment_passes(lib, v, lab, K, g.walk_w, s)
         n = B * K * J * J
         out = torch.empty((2 * n + 2,), dtype=torch.float32, device=v.device)
         A, cf, loss = out[:n], out[n:2 * n], out[2 * n:]                       # loss = (value, 1 / number of valid pairs)
@@ -184,7 +111,7 @@ class _KLDFusedLoss(torch.autograd.Function):
         coef = (g.reshape(()).float() * loss[1]).reshape(1).contiguous()       # dLoss_total/dloss x 1/n, on the device
         _lib.check(lib.spx_kld_backward(_lib.ptr(v), _lib.ptr(lab), B, J, HW, ctx.K, _lib.ptr(lse), _lib.ptr(A), _lib.ptr(cf), _lib.ptr(coef),
                                         _lib.ptr(grad), _lib.stream_ptr()))
-        return grad, None, None, None, None
+        return grad, None, None
 
 
 def segment_pair_sums(planes: torch.Tensor, labels0: torch.Tensor, K: int, W: int = 0) -> torch.Tensor:
@@ -192,13 +119,9 @@ def segment_pair_sums(planes: torch.Tensor, labels0: torch.Tensor, K: int, W: in
     [B, J, H*W] through the three reduction passes of csrc/spx_kld.hip - what ``KLDLoss`` builds its value from (no autograd;
     diagnostics and tests).  ``W``: row length of the pixel grid (0 = unknown: linear walk)."""
     lib = _lib.load()
-    v = planes.detach().contiguous()
-    B, J, HW = v.shape
-    if not _kld_kernels_usable(v, K, J):
-        raise SpxError(f"segment_pair_sums: input {tuple(v.shape)} {v.dtype} on {v.device} is outside the HIP kernels' domain")
-    lab = labels0.to(device=v.device, dtype=torch.int32).contiguous()
-    Wk = int(W) if W and HW % int(W) == 0 else 0
-    a_fx, _, _, scale = _kld_segment_passes(lib, v, lab, K, Wk, _lib.stream_ptr())
+    _gathered.check_domain(planes, K, "segment_pair_sums")
+    v, lab = _gathered.launch_operands(Gathered(planes, labels0, None, 0))
+    a_fx, _, _, scale = _kld_segment_passes(lib, v, lab, K, _gathered.walk_width(W, v.shape[2]), _lib.stream_ptr())
     return (a_fx.to(torch.float64) / scale).float()
 
 
@@ -244,43 +167,19 @@ class KLDLoss(_SlotTable, nn.Module):
         upper = torch.triu(torch.ones(J, J, dtype=torch.bool), diagonal=1)
         return same & upper
 
-    def forward(self, prototype_distances: Union[torch.Tensor, ClassDistances], target_labels: torch.Tensor) -> torch.Tensor:
-        cd = prototype_distances if isinstance(prototype_distances, ClassDistances) else None
-        poison = None
-        if cd is not None:
-            labels0, poison = _labels_of(cd, target_labels)
-        else:
-            labels0 = target_labels.reshape(target_labels.shape[0], -1).long() - 1      # loss.py:73
+    def _gathered(self, prototype_distances, target_labels: torch.Tensor) -> Gathered:
         if isinstance(prototype_distances, ClassDistances):
-            table = prototype_distances.table
-            vals = prototype_distances.values.permute(0, 2, 1)          # [B, H*W, J] view
-        else:
-            table = self._slot_table()
-            vals = gather_class_distances(prototype_distances, labels0, table)
-        planes = prototype_distances.values if isinstance(prototype_distances, ClassDistances) else None
-        width = prototype_distances.grid[-1] if isinstance(prototype_distances, ClassDistances) else prototype_distances.shape[-1]
-        loss = self._forward_gathered(vals, planes, labels0, table, width)
-        return loss if poison is None else loss * poison.to(loss.device)       # NaN when the planes were gathered under other classes
+            table = self._table_on(prototype_distances.table, prototype_distances.values.device)
+            return _gathered.from_class_distances(prototype_distances, target_labels, table)
+        return _gathered.from_distance_map(prototype_distances, target_labels, self._table_on(self._slot_table(), prototype_distances.device))
 
-    def _forward_gathered(self, vals: torch.Tensor, planes, labels0: torch.Tensor, table: torch.Tensor, width: int = 0) -> torch.Tensor:
-        """Loss from the class-gathered values ``vals`` [B, H*W, J] (``planes``: the same as [B, J, H*W], if the caller
-        already holds that layout; ``width``: W of the pixel grid if known, a traversal hint for the kernels)."""
-        dev = vals.device
-        table = self._table_on(table, dev)
-        K, J = table.shape
-        B = vals.shape[0]
-        lab = labels0.to(dev)
-        nseg = B * K
-        if planes is None and _kld_kernels_usable(vals, K, J):
-            planes = vals.permute(0, 2, 1).contiguous()      # full map given: its gathered entries as [B, J, H*W] planes
-        if planes is not None and _kld_kernels_usable(planes, K, J):
-            # the gathered planes on the GPU: segment statistics and the gradient run in the HIP kernels; nothing on
-            # this path reads a value back to the host (capturable in a HIP graph)
-            return _KLDFusedLoss.apply(planes, lab, K, width, self._pair_mask_u8(table, dev))
-        raise SpxError(
-            f"KLD loss: input {tuple(vals.shape)} {vals.dtype} on {vals.device} (K={K}, J={J}) is outside the HIP kernels' "
-            "domain (fp32 on the GPU, J <= 16, K*J*12 <= 60 KiB); there is no other backend"
-        )
+    def forward(self, prototype_distances: Union[torch.Tensor, ClassDistances], target_labels: torch.Tensor) -> torch.Tensor:
+        # the gathered planes on the GPU: segment statistics and the gradient run in the HIP kernels; nothing on this path reads
+        # a value back to the host (capturable in a HIP graph)
+        g = self._gathered(prototype_distances, target_labels)
+        _gathered.check_domain(g.planes, g.table.shape[0], "KLD loss")
+        loss = _KLDFusedLoss.apply(g.planes, g, self._pair_mask_u8(g.table, g.planes.device))
+        return loss if g.poison is None else loss * g.poison                   # NaN when the planes were gathered under other classes
 
     def _pair_mask_u8(self, table: torch.Tensor, dev) -> torch.Tensor:
         """The [K, J, J] pair mask as uint8 on ``dev`` (cached with the mask it is made from)."""
@@ -303,44 +202,23 @@ class KLDLossGroup(KLDLoss):
         self.num_groups = num_groups
 
     def _class_tables(self):
-        """(projection of class c or -1 [K], stand-in slot table [K, G]: slot ids where the class has a projection), rebuilt when
-        either identity is edited in place or re-assigned (finetune_wandb_group.py:77-78)."""
+        """``_gathered.group_class_tables`` of the two identities, rebuilt when either is edited in place or re-assigned
+        (finetune_wandb_group.py:77-78)."""
         ident, gci, G = self.prototype_class_identity, self.group_class_identity, self.num_groups
-        return cached(self, "_class_tables_cache", (ident, gci), (G,), lambda: self._class_tables_build(ident, gci, G))
-
-    @staticmethod
-    def _class_tables_build(ident, gci, G):
-        K = ident.shape[1]
-        has = ident.sum(dim=0) > 0                                              # loss.py:504
-        proj = torch.where(has, gci.argmax(dim=0) // G, torch.full((K,), -1, dtype=torch.long)).cpu()   # :507
-        table = torch.where(has.cpu().unsqueeze(1), torch.arange(G).unsqueeze(0).expand(K, G), torch.full((K, G), -1, dtype=torch.long))
-        return proj, table.contiguous()
+        return cached(self, "_class_tables_cache", (ident, gci), (G,), lambda: _gathered.group_class_tables(ident, gci, G))
 
     def _pair_mask_build(self, table: torch.Tensor) -> torch.Tensor:
         K, J = table.shape
         upper = torch.triu(torch.ones(J, J, dtype=torch.bool), diagonal=1)
         return upper.unsqueeze(0) & (table.cpu()[:, :1] >= 0).unsqueeze(2)
 
-    def _gather_groups(self, list_group_activation, target_labels: torch.Tensor):
-        """(vals [B, HW, G]: the group activations of the pixel's class, labels0 [B, HW], stand-in slot table [K, G])."""
-        G = self.num_groups
-        labels0 = target_labels.reshape(target_labels.shape[0], -1).long() - 1          # loss.py:493
-        B, HW = labels0.shape
+    def _gathered(self, list_group_activation, target_labels: torch.Tensor) -> Gathered:
         proj, table = self._class_tables()
-        K = table.shape[0]
-        if isinstance(list_group_activation, torch.Tensor):
-            ga = list_group_activation.reshape(B, HW, -1, G)
-        else:
-            ga = torch.stack([a.reshape(B, HW, G) for a in list_group_activation], dim=2)
-        dev = ga.device
-        lab = labels0.to(dev)
-        pix_proj = proj.to(dev)[lab.clamp(0, K - 1)].clamp_min(0)                       # [B, HW]; unused where no class
-        vals = torch.gather(ga, 2, pix_proj.view(B, HW, 1, 1).expand(B, HW, 1, G)).squeeze(2)      # [B, HW, G]
-        return vals, labels0, table
+        dev = (list_group_activation if isinstance(list_group_activation, torch.Tensor) else list_group_activation[0]).device
+        return _gathered.from_groups(list_group_activation, target_labels, proj, self._table_on(table, dev))
 
-    def forward(self, list_group_activation, target_labels: torch.Tensor) -> torch.Tensor:
-        vals, labels0, table = self._gather_groups(list_group_activation, target_labels)
-        return self._forward_gathered(vals, None, labels0, table, target_labels.shape[-1] if target_labels.dim() >= 3 else 0)
+    def forward(self, list_group_activation, target_labels: torch.Tensor) -> torch.Tensor:       # the reference's argument names
+        return super().forward(list_group_activation, target_labels)
 
 
 # ---- weight-side regularisers (segmentation/model/loss.py:351-464, module_multiscale*.py L1) ----------------------------
@@ -553,22 +431,11 @@ _ACT_MODES = {"log": 1, "linear": 2}
 _NORM_TYPES = {"l1": 0, "linf": 1}
 
 
-def slot_scale_table(table: torch.Tensor, num_scales: int, scale_num_prototypes) -> torch.Tensor:
-    """[K, J] int32 scale id of (class, slot) for a ``class_slot_table``: -1 = the class has no such slot, -2 = a prototype
-    that lies in no scale's range (it counts for the spatial entropy and the norm, not for the sample entropy)."""
-    t = table.detach().cpu().long()
-    sid = torch.where(t >= 0, torch.full_like(t, -2), torch.full_like(t, -1))
-    for s in range(int(num_scales)):
-        lo, hi = scale_num_prototypes[s]
-        sid[(t >= int(lo)) & (t < int(hi))] = s
-    return sid.to(torch.int32).contiguous()
-
-
-def _act_desc(v, lab, sid, cfg):
+def _act_desc(v, lab, sid, W, K, cfg):
     B, J, HW = v.shape
     d = _lib.SpxActLoss()
     d.vals, d.labels, d.slot_scale = _lib.ptr(v), _lib.ptr(lab), _lib.ptr(sid)
-    d.B, d.J, d.HW, d.W, d.K = B, J, HW, cfg["W"], cfg["K"]
+    d.B, d.J, d.HW, d.W, d.K = B, J, HW, W, K
     d.mode, d.terms, d.norm_type = cfg["mode"], cfg["terms"], cfg["norm_type"]
     d.epsilon = cfg["epsilon"]
     d.weights = (C.c_float * 3)(*cfg["weights"])
@@ -580,18 +447,18 @@ class _ActLossFn(torch.autograd.Function):
     csrc/spx_actloss.hip); backward ONE launch, scaled by the upstream gradients read on the device."""
 
     @staticmethod
-    def forward(ctx, vals, labels, sid, cfg):
+    def forward(ctx, planes, g, sid, cfg):
         lib = _lib.load()
-        v = vals.detach().contiguous()
-        lab = labels.to(device=v.device, dtype=torch.int32).contiguous()
+        v, lab = _gathered.launch_operands(g)                                   # g.planes is ``planes``
         B, J, HW = v.shape
         s = _lib.stream_ptr()
-        d = _act_desc(v, lab, sid, cfg)
+        ctx.WK = W, K = g.walk_w, g.table.shape[0]
+        d = _act_desc(v, lab, sid, W, K, cfg)
         nbytes = lib.spx_actloss_workspace_bytes(C.byref(d))
         if nbytes == 0:
             raise SpxError(lib.spx_last_error().decode("utf-8", "replace"))
         ws = torch.zeros((nbytes // 8,), dtype=torch.int64, device=v.device)
-        coef = torch.empty((B * cfg["K"], 6, J), dtype=torch.float32, device=v.device)
+        coef = torch.empty((B * K, 6, J), dtype=torch.float32, device=v.device)
         out = torch.empty((7,), dtype=torch.float32, device=v.device)
         _lib.check(lib.spx_actloss_segment_max(C.byref(d), _lib.ptr(ws), s))
         _lib.check(lib.spx_actloss_segment_sums(C.byref(d), _lib.ptr(ws), s))
@@ -609,7 +476,7 @@ class _ActLossFn(torch.autograd.Function):
         gt = g_total.float().reshape(1).contiguous() if g_total is not None else None
         gs = g_terms.float().contiguous() if g_terms is not None else None
         grad = torch.empty_like(v)
-        d = _act_desc(v, lab, sid, ctx.cfg)
+        d = _act_desc(v, lab, sid, *ctx.WK, ctx.cfg)
         _lib.check(_lib.load().spx_actloss_backward(C.byref(d), _lib.ptr(coef), _lib.ptr(gt), _lib.ptr(gs), _lib.ptr(grad), _lib.stream_ptr()))
         return grad, None, None, None
 
@@ -661,36 +528,18 @@ class ActivationRegularizers(_SlotTable, nn.Module):
         return cached(self, "_act_tables_cache", (table,), (scales, str(dev)), build, ways=4)
 
     def _run(self, prototype_activations, target_labels: torch.Tensor):
-        cd = prototype_activations if isinstance(prototype_activations, ClassDistances) else None
-        src = cd.values if cd is not None else prototype_activations
-        _lib.require_gpu(src, "activation losses: input")
-        if src.dtype != torch.float32:
-            raise SpxError(f"activation losses: input is {src.dtype}; the kernels take fp32")
-        dev = src.device
-        poison = None
-        if cd is not None:
-            labels0, poison = _labels_of(cd, target_labels)
-            table, sid = self._tables_on(cd.table, dev)
-            planes, mode, W = cd.values, _ACT_MODES[self.activation], int(cd.grid[-1])
+        if isinstance(prototype_activations, ClassDistances):                           # the activation is applied in the kernels
+            table, sid = self._tables_on(prototype_activations.table, prototype_activations.values.device)
+            g, mode = _gathered.from_class_distances(prototype_activations, target_labels, table), _ACT_MODES[self.activation]
         else:
-            B = target_labels.shape[0]
-            labels0 = target_labels.reshape(B, -1).long().to(dev) - 1                  # loss.py:167
-            table, sid = self._tables_on(self._slot_table(), dev)
-            K = table.shape[0]
-            act = prototype_activations.reshape(B, -1, self.prototype_class_identity.shape[0])
-            idx = table[labels0.clamp(0, K - 1)].clamp(min=0)                           # [B, HW, J]; unused entries are masked in the kernels
-            planes = torch.gather(act, 2, idx).permute(0, 2, 1).contiguous()
-            mode, W = 0, (int(target_labels.shape[-1]) if target_labels.dim() >= 3 else 0)
-        K, J = table.shape
-        if not _kld_kernels_usable(planes, K, J):
-            raise SpxError(f"activation losses: planes {tuple(planes.shape)} (K={K}, J={J}) are outside the HIP kernels' domain "
-                           "(J <= 16, K*J*12 <= 60 KiB); there is no other backend")
-        HW = planes.shape[2]
-        cfg = {"K": K, "W": W if W and HW % W == 0 else 0, "mode": mode, "terms": self._terms,
-               "norm_type": _NORM_TYPES[self.norm_type], "epsilon": float(self.epsilon), "weights": self._weights}
-        total, terms = _ActLossFn.apply(planes, labels0, sid, cfg)
-        if poison is not None:                                                          # NaN when the planes were gathered under other classes
-            total, terms = total * poison.to(total.device), terms * poison.to(terms.device)
+            table, sid = self._tables_on(self._slot_table(), prototype_activations.device)
+            g, mode = _gathered.from_activations(prototype_activations, target_labels, table), 0
+        _gathered.check_domain(g.planes, table.shape[0], "activation losses")
+        cfg = {"mode": mode, "terms": self._terms, "norm_type": _NORM_TYPES[self.norm_type], "epsilon": float(self.epsilon),
+               "weights": self._weights}
+        total, terms = _ActLossFn.apply(g.planes, g, sid, cfg)
+        if g.poison is not None:                                                        # NaN when the planes were gathered under other classes
+            total, terms = total * g.poison, terms * g.poison
         return total, terms
 
     def forward(self, prototype_activations: Union[torch.Tensor, ClassDistances], target_labels: torch.Tensor):

@@ -743,6 +743,51 @@ def test_kld_group_kernels_match_reference_golden(golden):
         assert (a - ref).abs().max().item() <= 2e-5 * ref.abs().max().item() + 1e-9
 
 
+def _concatenated_group_case():
+    """B = 2, grid 7 x 9, K = 4 (class 2 without prototypes), G = 3, one projection per class with prototypes; labels in 2 x 3
+    patches with void, the class without prototypes and 255 among them."""
+    K, G = 4, 3
+    ident = torch.zeros(6, K)
+    for p, c in enumerate([0, 1, 3, 0, 1, 3]):
+        ident[p, c] = 1
+    gci = torch.zeros(3 * G, K)
+    for i, c in enumerate([0, 1, 3]):
+        gci[i * G:(i + 1) * G, c] = 1
+    gen = torch.Generator().manual_seed(21)
+    t = torch.randint(0, K + 1, (2, 4, 3), generator=gen).repeat_interleave(2, 1).repeat_interleave(3, 2)[:, :7, :9].contiguous()
+    t[1, 6, 8] = 255
+    acts = [torch.randn(2 * 63, 1, generator=gen) + 0.5 * torch.randn(2 * 63, G, generator=gen) for _ in range(3)]
+    return ident, gci, G, t, acts
+
+
+def test_kld_group_concatenated_tensor_matches_the_oracle():
+    """KLDLossGroup handed the concatenated [M, n_projections * G] tensor of the grouping head: value and gradient against the
+    float64 loop restatement of the reference (oracle/ppnet_oracle.py::kld_loss_group) within the bounds of the two group tests
+    above (1e-4 relative on the value as in test_kld_through_the_module, 2e-5 of the largest gradient entry), and bit for bit
+    what the list form gives."""
+    import scaleprotoseg_amd as spx
+
+    dev = gpu_device()
+    ident, gci, G, t, acts = _concatenated_group_case()
+    a64 = [a.double().requires_grad_(True) for a in acts]
+    ref = O.kld_loss_group(a64, t, ident, gci, G)
+    ref.backward()
+    assert MIN_LOSS <= ref.item() <= 0.95, ref.item()
+    ref_grad = torch.cat([a.grad for a in a64], dim=1)
+    m = spx.KLDLossGroup(ident, gci, G)
+    cat = torch.cat(acts, dim=1).to(dev).requires_grad_(True)
+    loss = m(cat, t.to(dev))
+    loss.backward()
+    lst = [a.to(dev).requires_grad_(True) for a in acts]
+    loss_list = m(lst, t.to(dev))
+    loss_list.backward()
+    torch.cuda.synchronize()
+    print(f"group KLD of the concatenated tensor {loss.item():.9g}, float64 {ref.item():.9g}")
+    assert abs(loss.item() - ref.item()) <= 1e-4 * max(1.0, abs(ref.item())), (loss.item(), ref.item())
+    assert (cat.grad.cpu().double() - ref_grad).abs().max().item() <= 2e-5 * ref_grad.abs().max().item() + 1e-9
+    assert torch.equal(loss, loss_list) and torch.equal(cat.grad, torch.cat([a.grad for a in lst], dim=1))
+
+
 @pytest.mark.parametrize("H,W", [(67, 333), (5, 64), (130, 257), (1, 1000)])
 def test_kld_kernels_ragged_grids(H, W):
     """Pair-sum kernel on grids that do not fill its 256-column x 16-row strips (and the linear walk, W unknown):

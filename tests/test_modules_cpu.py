@@ -318,7 +318,7 @@ def test_kld_loss_group_tables_follow_edits_of_the_identities():
     swap = [2, 3, 0, 1, 4, 5, 6, 7]                                # the row blocks of classes 0 and 1 change places
     acts = [torch.full((9, G), float(i + 1)) for i in range(K)]
     target = torch.tensor([[[1, 2, 3], [4, 1, 2], [3, 4, 0]]])
-    gather = lambda m: m._gather_groups(acts, target)[0]
+    gather = lambda m: m._gathered(acts, target).planes.permute(0, 2, 1)
     fresh = lambda g: gather(KLDLossGroup(ident, g.clone(), G))
     before, after = fresh(gci), fresh(gci[swap])
     assert not torch.equal(before, after)                          # the edit is visible in what is gathered
