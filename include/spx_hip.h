@@ -690,6 +690,48 @@ int spx_explain_dominant(const float* planes, const int64_t* host_strides, const
                          const int32_t* host_rows, const int32_t* slot_table, const float* weights, int32_t R, int32_t N, int32_t C,
                          int32_t K, int32_t J, int32_t h, int32_t w, int32_t H, int32_t W, uint8_t* dom, void* stream);
 
+/* Failure cases (additive to ABI 17; segmentation/analysis/failure_cases.py, segmentation/eval_test.py:99-111): predicted label
+ * maps as bytes with a confusion matrix per image, the table of failing (image, class) pairs, and the heat maps of two classes'
+ * slots over the failing class.
+ *
+ * spx_predict_accumulate: logits fp32 [N, h, w, K] through host_logit_strides = (n, channel, y, x) as spx_eval_accumulate takes
+ * them, 1 <= K <= 256.  k* = the first argmax over the classes of the bilinear (align_corners = False) upsample to H x W, with the
+ * bits of spx_upsample_argext.  At least one of:
+ *   pred  uint8 [N, H, W], any alignment: id_map[k*] (id_map uint8 [K] on the device), or k* when id_map is NULL; every byte is
+ *         written exactly once, as packed dwords wherever four bytes of a row share an aligned dword.
+ *   conf  int64 [N, K+1, K], ADDED to: conf[n, r, k*] += 1 per pixel with label != 0, r = label - 1 for 1 <= label <= K, else K
+ *         (spx_eval_accumulate's rule, per image).  Needs labels [N, H, W] (label_bytes 1 / 4 / 8); labels may be NULL without it.
+ * One launch; counters privatised per workgroup in LDS and flushed with 64-bit atomics whenever a workgroup's image changes.
+ *
+ * spx_failure_table: one launch over conf int64 [N, K+1, K], no host read.  For image n and class k:
+ *   present = sum_j conf[n, k, j] > 0;  I = conf[n, k, k];  U = sum_j conf[n, k, j] + sum_{r = 0..K} conf[n, r, k] - I
+ *   iou  f64 [N, K]    I / U, the division correctly rounded; NaN for a class that is not present
+ *   fail uint8 [N, K]  iou < threshold (strict, float64); 0 for a class that is not present
+ *   miss int32 [N, K]  argmax over j != k of conf[n, k, j]: the lowest j among equal counts, -1 when all are zero or the class is
+ *                      not present
+ *
+ * spx_paired_range / spx_paired_heat: planes, host_strides, labels, u as spx_explain_range takes them.  rows int32 [R, 4] on the
+ * device = (n, c, class a, range slot q), host_rows the same table in host memory, required and checked before any launch: every
+ * field in range (0 <= q < Q), every slot 0 .. Q-1 named, rows of one slot name one (n, a).
+ *   m      labels[n] == a + 1 ? u[n, c] : 0;   lo_q = min m, hi_q = max m over all pixels of all rows naming slot q
+ *   heat   (uint8) trunc(255 * ((m - lo_q) / hi_q)) in fp32, every operation rounded on its own, the division correctly rounded
+ *          (np.uint8(255 * ((m - min) / max)) on float32); 255 where 255 x >= 256 (possible only when lo_q < 0); a slot with
+ *          hi_q <= 0 gives all-zero rows.
+ * spx_paired_range writes the keys of lo and hi into workspace (8 Q bytes, no initialisation needed); spx_paired_heat, given the
+ * same arguments and that workspace, writes heat uint8 [R, H, W] (any alignment, every byte once) and ranges fp32 [Q, 2].
+ * Integer min / max atomics: run-to-run identical.  Limits: those of spx_explain_range; Q <= R <= 65535. */
+int spx_predict_accumulate(const float* logits, const int64_t* host_logit_strides, const void* labels, int32_t label_bytes,
+                           const uint8_t* id_map, int32_t N, int32_t K, int32_t h, int32_t w, int32_t H, int32_t W, uint8_t* pred,
+                           int64_t* conf, void* stream);
+int spx_failure_table(const int64_t* conf, int32_t N, int32_t K, double threshold, double* iou, int32_t* miss, uint8_t* fail_out,
+                      void* stream);
+int spx_paired_range(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                     const int32_t* host_rows, int32_t R, int32_t Q, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
+                     void* workspace, void* stream);
+int spx_paired_heat(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                    const int32_t* host_rows, int32_t R, int32_t Q, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
+                    const void* workspace, uint8_t* heat, float* ranges, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

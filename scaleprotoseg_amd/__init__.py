@@ -41,6 +41,11 @@ Public surface mirrors the reference's module/function names for this path:
                                                     (segmentation/analysis/nearest_img.py, nearest_proto.py: the n nearest
                                                      images of every prototype with the class-restricted threshold_gt and
                                                      both crops, and the n nearest prototypes of chosen pixels)
+    FailureCases, predict_label_maps, failure_table, paired_heat_maps
+                                                    (segmentation/analysis/failure_cases.py, segmentation/eval_test.py:99-111:
+                                                     predicted label maps as bytes in the data set's ids with a confusion
+                                                     matrix per image, the failing (image, class, mistaken-for) table, and
+                                                     the two classes' heat maps over the failing class on shared ranges)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -99,6 +104,14 @@ from .nearest import (  # noqa: F401
     patch_majority,
 )
 from .explain import ExplanationMaps, activation_heat_maps, dominant_slot_maps  # noqa: F401
+from .failures import (  # noqa: F401
+    BatchFailures,
+    FailureCases,
+    FailureReport,
+    failure_table,
+    paired_heat_maps,
+    predict_label_maps,
+)
 from .prune import NearestPatches, find_k_nearest_patches_to_prototypes, prune_prototypes  # noqa: F401
 from .utils import (  # noqa: F401
     non_zero_proto,

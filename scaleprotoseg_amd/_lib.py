@@ -196,6 +196,10 @@ SIGNATURES = {
     "spx_explain_range": (C.c_int, [_V, _PL, _V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V]),
     "spx_explain_heat": (C.c_int, [_V, _PL, _V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V, _V]),
     "spx_explain_dominant": (C.c_int, [_V, _PL, _V, _I, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V]),
+    "spx_predict_accumulate": (C.c_int, [_V, _PL, _V, _I, _V, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "spx_failure_table": (C.c_int, [_V, _I, _I, C.c_double, _V, _V, _V, _V]),
+    "spx_paired_range": (C.c_int, [_V, _PL, _V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V]),
+    "spx_paired_heat": (C.c_int, [_V, _PL, _V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V, _V]),
     "spx_push_merge": (C.c_int, [_V, _V, _V, _I, _I, _I, _I, _I, _I, _V, C.c_int64, _V, _V, _V, _V, _V]),
 }
 

@@ -107,6 +107,23 @@ def device_labels(maps: torch.Tensor, labels: torch.Tensor, name: str = "activat
     return labels.detach().contiguous()
 
 
+MAX_MAP_ROWS = 65535             # rows of one launch of a byte-map kernel (a grid dimension)
+
+
+def upload(host: torch.Tensor, device) -> torch.Tensor:
+    """Device copy of a small host table through pinned memory: an asynchronous copy that never waits for the device."""
+    return host.pin_memory().to(device, non_blocking=True)
+
+
+def byte_output(out: Optional[torch.Tensor], shape, device) -> torch.Tensor:
+    """The uint8 output of a byte-map operator: ``out`` when it fits (contiguous, any alignment), else a fresh tensor."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
+        raise SpxError(f"out must be a contiguous uint8 {tuple(shape)} tensor on {device}")
+    return out
+
+
 def slot_table(table) -> torch.Tensor:
     """Host int32 [K, J] copy of a slot table (channel of (class, slot) or -1) with ``J <= MAX_SLOTS``."""
     table = torch.as_tensor(table).detach().cpu()

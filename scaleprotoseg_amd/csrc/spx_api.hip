@@ -4,6 +4,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <vector>
+
 #include "spx_args.h"
 
 static thread_local char g_err[512] = "";
@@ -1040,6 +1042,82 @@ int spx_explain_dominant(const float* planes, const int64_t* host_strides, const
     }
     return hip_status(spx_launch_explain_dominant(planes, (const long long*)host_strides, labels, label_bytes, rows, slot_table, weights,
                                                   R, N, C, K, J, h, w, H, W, dom, (hipStream_t)stream), who);
+}
+
+// ---- failure cases: label maps with per-image confusion, the failure table, paired heat maps -------------------------------
+#define SPX_PRED_MAX_CLASSES 256
+
+int spx_predict_accumulate(const float* logits, const int64_t* host_logit_strides, const void* labels, int32_t label_bytes,
+                           const uint8_t* id_map, int32_t N, int32_t K, int32_t h, int32_t w, int32_t H, int32_t W, uint8_t* pred,
+                           int64_t* conf, void* stream) {
+    static const char* who = "spx_predict_accumulate";
+    if (!pred && !conf) return fail("%s: NULL pred and conf: nothing to write", who);
+    if (conf && !labels) return fail("%s: NULL labels with confusion counters", who);
+    if (labels)
+        if (int e = check_label_bytes(who, label_bytes)) return e;
+    if (K > SPX_PRED_MAX_CLASSES) return fail("%s: %d classes (at most %d: a prediction is one byte)", who, K, SPX_PRED_MAX_CLASSES);
+    if (int e = eval_check(who, logits, host_logit_strides, nullptr, nullptr, N, K, 0, h, w, H, W)) return e;
+    return hip_status(spx_launch_predict_accumulate(logits, (const long long*)host_logit_strides, conf ? labels : nullptr, label_bytes,
+                                                    id_map, N, K, h, w, H, W, pred, (unsigned long long*)conf, (hipStream_t)stream), who);
+}
+
+int spx_failure_table(const int64_t* conf, int32_t N, int32_t K, double threshold, double* iou, int32_t* miss, uint8_t* fail_out,
+                      void* stream) {
+    static const char* who = "spx_failure_table";
+    if (!conf || !iou || !miss || !fail_out) return fail("%s: NULL conf / iou / miss / fail", who);
+    if (N < 1 || K < 1) return fail("%s: empty input (N=%d K=%d)", who, N, K);
+    if (K > SPX_EVAL_MAX_CLASSES || (long long)N * K >= (1LL << 31))
+        return fail("%s: bad sizes (N=%d K=%d; K <= %d, N*K < 2^31)", who, N, K, SPX_EVAL_MAX_CLASSES);
+    if (threshold != threshold) return fail("%s: the threshold is NaN", who);
+    return hip_status(spx_launch_failure_table((const long long*)conf, N, K, threshold, iou, miss, fail_out, (hipStream_t)stream), who);
+}
+
+// what the two paired-map entry points check alike: every field of every row, every slot used, one (image, class) per slot
+static int paired_check(const char* who, const float* planes, const int64_t* st, const void* labels, int32_t label_bytes,
+                        const int32_t* rows, const int32_t* host_rows, int32_t R, int32_t Q, int32_t N, int32_t C, int32_t h, int32_t w,
+                        int32_t H, int32_t W, const void* workspace) {
+    if (!workspace) return fail("%s: NULL workspace", who);
+    if (int e = explain_check(who, planes, st, labels, label_bytes, rows, host_rows, R, N, C, h, w, H, W)) return e;
+    if (Q < 1 || Q > R) return fail("%s: %d range slots for %d rows (1..R)", who, Q, R);
+    std::vector<int32_t> first;                                  // host memory, at most 4 Q <= 256 KiB: the first row of each slot
+    try {
+        first.assign((size_t)Q, -1);
+    } catch (...) {
+        return fail("%s: out of host memory for the table of %d range slots", who, Q);
+    }
+    for (int r = 0; r < R; ++r) {
+        const int32_t* p = host_rows + 4 * (size_t)r;
+        if (p[0] < 0 || p[0] >= N || p[1] < 0 || p[1] >= C || p[2] < 0 || p[3] < 0 || p[3] >= Q)
+            return fail("%s: row %d = (n %d, c %d, class %d, slot %d) out of range (N=%d C=%d Q=%d, class >= 0)", who, r, p[0], p[1], p[2],
+                        p[3], N, C, Q);
+        int32_t& f = first[(size_t)p[3]];
+        if (f < 0) f = r;
+        else if (host_rows[4 * (size_t)f] != p[0] || host_rows[4 * (size_t)f + 2] != p[2])
+            return fail("%s: row %d = (n %d, class %d) shares slot %d with row %d = (n %d, class %d)", who, r, p[0], p[2], p[3], f,
+                        host_rows[4 * (size_t)f], host_rows[4 * (size_t)f + 2]);
+    }
+    for (int q = 0; q < Q; ++q)
+        if (first[(size_t)q] < 0) return fail("%s: no row names range slot %d of %d", who, q, Q);
+    return 0;
+}
+
+int spx_paired_range(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                     const int32_t* host_rows, int32_t R, int32_t Q, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
+                     void* workspace, void* stream) {
+    static const char* who = "spx_paired_range";
+    if (int e = paired_check(who, planes, host_strides, labels, label_bytes, rows, host_rows, R, Q, N, C, h, w, H, W, workspace)) return e;
+    return hip_status(spx_launch_paired_range(planes, (const long long*)host_strides, labels, label_bytes, rows, R, Q, N, C, h, w, H, W,
+                                              workspace, (hipStream_t)stream), who);
+}
+
+int spx_paired_heat(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* rows,
+                    const int32_t* host_rows, int32_t R, int32_t Q, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
+                    const void* workspace, uint8_t* heat, float* ranges, void* stream) {
+    static const char* who = "spx_paired_heat";
+    if (!heat || !ranges) return fail("%s: NULL heat / ranges", who);
+    if (int e = paired_check(who, planes, host_strides, labels, label_bytes, rows, host_rows, R, Q, N, C, h, w, H, W, workspace)) return e;
+    return hip_status(spx_launch_paired_heat(planes, (const long long*)host_strides, labels, label_bytes, rows, R, Q, N, C, h, w, H, W,
+                                             workspace, heat, ranges, (hipStream_t)stream), who);
 }
 
 static int kld_check(const char* who, const float* vals, const int32_t* labels, int32_t B, int32_t J, int32_t HW, int32_t K,

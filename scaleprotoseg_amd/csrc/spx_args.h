@@ -251,6 +251,16 @@ hipError_t spx_launch_explain_heat(const float* planes, const long long* st, con
 hipError_t spx_launch_explain_dominant(const float* planes, const long long* st, const void* labels, int label_bytes,
                                        const int32_t* rows, const int32_t* table, const float* weights, int R, int N, int C, int K, int J,
                                        int h, int w, int H, int W, uint8_t* dom, hipStream_t s);
+hipError_t spx_launch_predict_accumulate(const float* logits, const long long* lst, const void* labels, int label_bytes,
+                                         const uint8_t* id_map, int N, int K, int h, int w, int H, int W, uint8_t* pred,
+                                         unsigned long long* conf, hipStream_t s);
+hipError_t spx_launch_failure_table(const long long* conf, int N, int K, double threshold, double* iou, int32_t* miss, uint8_t* fail,
+                                    hipStream_t s);
+hipError_t spx_launch_paired_range(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
+                                   int R, int Q, int N, int C, int h, int w, int H, int W, void* workspace, hipStream_t s);
+hipError_t spx_launch_paired_heat(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
+                                  int R, int Q, int N, int C, int h, int w, int H, int W, const void* workspace, uint8_t* heat,
+                                  float* ranges, hipStream_t s);
 size_t spx_actloss_ws_bytes(int B, int K, int J);
 hipError_t spx_launch_actloss_max(const spx_actloss* p, void* workspace, hipStream_t s);
 hipError_t spx_launch_actloss_sums(const spx_actloss* p, void* workspace, hipStream_t s);

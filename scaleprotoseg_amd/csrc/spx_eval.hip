@@ -386,3 +386,189 @@ hipError_t spx_launch_eval_topk(const float* logits, const long long* lst, const
                        samples, sample_bytes, N, S, K, P, h, w, H, W, sh, sw, topk, seen);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Label maps and per-image confusion (segmentation/eval_test.py:99-111, segmentation/analysis/failure_cases.py:96-141):
+// the pass of spx_eval_accumulate_kernel over the logits (the same tiles, the same staged footprint, the same scan, so
+// pred carries the bits of spx_upsample_argext), with two other outputs:
+//   pred [N, H, W] uint8   id_map[k*], or k* without a map: one byte per pixel
+//   conf [N, K+1, K]       the rule of spx_eval_accumulate per image
+// A wave is one row of a tile.  Its 64 bytes are gathered with lane shuffles into the aligned dwords of memory they fall
+// into (lane l forms the dword 4 l bytes above the row's address rounded down to a dword), whole dwords are stored as
+// such and the ends of the row byte by byte: every byte is written exactly once whatever W and the pointer are.
+// A workgroup walks a contiguous run of tiles (tiles are numbered image by image), so the counters it holds in LDS belong
+// to one image; they are flushed and zeroed when the image changes and at the end.
+
+__device__ __forceinline__ void spx_predict_flush(unsigned int* s_conf, int nconf, int K, int full_conf,
+                                                  unsigned long long* __restrict__ conf_n) {
+    for (int i = threadIdx.x; i < nconf; i += SPX_EVAL_ACC_THREADS) {
+        const unsigned int v = s_conf[i];
+        if (v && conf_n) atomicAdd(&conf_n[full_conf ? (size_t)i : (size_t)i * K + i], (unsigned long long)v);
+        s_conf[i] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(SPX_EVAL_ACC_THREADS) void spx_predict_accumulate_kernel(
+    SpxPlanes lg, const void* __restrict__ labels, int label_bytes, const uint8_t* __restrict__ id_map, int N, int K, int h, int w,
+    int H, int W, float sh, float sw, int tiles_x, int tiles_y, long long chunk, int full_conf, uint8_t* __restrict__ pred_out,
+    unsigned long long* __restrict__ conf) {
+    extern __shared__ unsigned int s_eval[];
+    const int tid = threadIdx.x;
+    const int nconf = conf ? (full_conf ? (K + 1) * K : K) : 0;
+    unsigned int* s_conf = s_eval;
+    float* s_lg = (float*)(s_eval + nconf);
+    const size_t conf_image = (size_t)(K + 1) * K;
+
+    const long long ntiles = (long long)N * tiles_y * tiles_x;
+    const long long t0 = (long long)blockIdx.x * chunk, t1 = min(t0 + chunk, ntiles);
+    int held = -1;                                             // the image whose counters s_conf holds
+    for (long long t = t0; t < t1; ++t) {
+        const int tx = (int)(t % tiles_x);
+        const long long r = t / tiles_x;
+        const int ty = (int)(r % tiles_y), n = (int)(r / tiles_y);
+        if (conf && n != held) {                               // workgroup-uniform
+            __syncthreads();                                   // the previous tile's counts are in
+            spx_predict_flush(s_conf, nconf, K, full_conf, held >= 0 ? conf + (size_t)held * conf_image : nullptr);
+            __syncthreads();
+            held = n;
+        }
+        const int ox = tx * 64 + (tid & 63), oy = ty * SPX_EVAL_TILE_H + (tid >> 6);
+        const bool active = ox < W && oy < H;
+        int y0, y1, x0, x1;
+        float ly0, ly1, lx0, lx1;
+        src_index(active ? oy : ty * SPX_EVAL_TILE_H, sh, h, y0, y1, ly0, ly1);
+        src_index(active ? ox : tx * 64, sw, w, x0, x1, lx0, lx1);
+        // the tile's source footprint (src_index is monotone in dst): workgroup-uniform
+        int ya, yb, xa, xb, d0;
+        float f0, f1;
+        src_index(ty * SPX_EVAL_TILE_H, sh, h, ya, d0, f0, f1);
+        src_index(min(ty * SPX_EVAL_TILE_H + SPX_EVAL_TILE_H - 1, H - 1), sh, h, d0, yb, f0, f1);
+        src_index(tx * 64, sw, w, xa, d0, f0, f1);
+        src_index(min(tx * 64 + 63, W - 1), sw, w, d0, xb, f0, f1);
+        const int nfx = xb - xa + 1, nfy = yb - ya + 1, nf = nfx * nfy;
+        const float* lq = lg.p + (long long)n * lg.sn;
+        int pred;
+        if (nf * K <= SPX_EVAL_STAGE) {
+            __syncthreads();                                   // the previous tile's scan is done with s_lg
+            for (int i = tid; i < nf * K; i += SPX_EVAL_ACC_THREADS) {
+                const int c = i % K, px = i / K, fx = px % nfx, fy = px / nfx;
+                s_lg[c * nf + px] = lq[c * lg.sc + (ya + fy) * lg.sy + (xa + fx) * lg.sx];
+            }
+            __syncthreads();
+            const unsigned r0 = (unsigned)((y0 - ya) * nfx), r1 = (unsigned)((y1 - ya) * nfx);
+            pred = argext_at<true>(s_lg, nf, K, r0 + (x0 - xa), r0 + (x1 - xa), r1 + (x0 - xa), r1 + (x1 - xa), lx0, lx1, ly0, ly1);
+        } else {
+            const unsigned r0 = (unsigned)(y0 * lg.sy), r1 = (unsigned)(y1 * lg.sy), c0 = (unsigned)(x0 * lg.sx),
+                           c1 = (unsigned)(x1 * lg.sx);
+            pred = argext_at<true>(lq, lg.sc, K, r0 + c0, r0 + c1, r1 + c0, r1 + c1, lx0, lx1, ly0, ly1);
+        }
+        if (conf && active) {
+            const long long ann = spx_label(labels, label_bytes, ((size_t)n * H + oy) * W + ox);
+            if (ann != 0) {
+                const int row = (ann >= 1 && ann <= K) ? (int)(ann - 1) : K;
+                if (full_conf) atomicAdd(&s_conf[row * K + pred], 1u);
+                else if (row == pred) atomicAdd(&s_conf[pred], 1u);
+                else atomicAdd(&conf[(size_t)n * conf_image + (size_t)row * K + pred], 1ull);
+            }
+        }
+        if (pred_out && oy < H) {                              // wave-uniform: the wave's row of the tile is in the image
+            const int lane = tid & 63, ncols = min(64, W - tx * 64);
+            uint8_t* a0 = pred_out + ((size_t)n * H + oy) * W + (size_t)tx * 64;
+            const int mis = (int)((uintptr_t)a0 & 3u);
+            const int byte = id_map ? (int)id_map[pred] : pred;
+            uint32_t word = 0u;
+            int have = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int col = 4 * lane + j - mis;            // the tile column of byte j of this lane's dword
+                const int v = __shfl(byte, col & 63);
+                if (col >= 0 && col < ncols) {
+                    word |= ((uint32_t)v & 255u) << (8 * j);
+                    have |= 1 << j;
+                }
+            }
+            uint8_t* q = a0 - mis + 4 * lane;                  // dword-aligned
+            if (have == 15) {
+                *(uint32_t*)q = word;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if ((have >> j) & 1) q[j] = (uint8_t)(word >> (8 * j));
+            }
+        }
+    }
+    if (conf && held >= 0) {
+        __syncthreads();
+        spx_predict_flush(s_conf, nconf, K, full_conf, conf + (size_t)held * conf_image);
+    }
+}
+
+hipError_t spx_launch_predict_accumulate(const float* logits, const long long* lst, const void* labels, int label_bytes,
+                                         const uint8_t* id_map, int N, int K, int h, int w, int H, int W, uint8_t* pred,
+                                         unsigned long long* conf, hipStream_t s) {
+    const float sh = (float)h / (float)H, sw = (float)w / (float)W;
+    const int tiles_x = (W + 63) / 64, tiles_y = (H + SPX_EVAL_TILE_H - 1) / SPX_EVAL_TILE_H;
+    const long long ntiles = (long long)N * tiles_y * tiles_x;
+    const int full = spx_eval_full_conf(K, 0);
+    const size_t lds = sizeof(unsigned int) * ((size_t)(conf ? (full ? (K + 1) * K : K) : 0) + SPX_EVAL_STAGE);
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            cus = 256;
+    }
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, spx_predict_accumulate_kernel, SPX_EVAL_ACC_THREADS, lds) != hipSuccess || per_cu < 1)
+        per_cu = 2;
+    // one contiguous run of tiles per workgroup, as many workgroups as the device holds at once
+    const long long cap = (long long)per_cu * cus;
+    const long long chunk = (ntiles + cap - 1) / cap;
+    const unsigned grid = (unsigned)((ntiles + chunk - 1) / chunk);
+    hipLaunchKernelGGL(spx_predict_accumulate_kernel, dim3(grid), dim3(SPX_EVAL_ACC_THREADS), lds, s, spx_planes(logits, lst), labels,
+                       label_bytes, id_map, N, K, h, w, H, W, sh, sw, tiles_x, tiles_y, chunk, full, pred, conf);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The failure table (failure_cases.py:131-160) from the per-image confusion, one thread per (image, class):
+//   present = sum_j conf[n, k, j] > 0;  I = conf[n, k, k];  U = sum_j conf[n, k, j] + sum_{r <= K} conf[n, r, k] - I
+//   iou = I / U in float64 (the division correctly rounded), fail = iou < threshold (strict),
+//   miss = the lowest j != k with the largest conf[n, k, j] > 0, or -1;  a class that is not present: NaN, -1, 0.
+__global__ __launch_bounds__(SPX_EVAL_THREADS) void spx_failure_table_kernel(const long long* __restrict__ conf, int N, int K,
+                                                                             double threshold, double* __restrict__ iou,
+                                                                             int32_t* __restrict__ miss, uint8_t* __restrict__ fail) {
+    const long long i = (long long)blockIdx.x * SPX_EVAL_THREADS + threadIdx.x;
+    if (i >= (long long)N * K) return;
+    const int n = (int)(i / K), k = (int)(i - (long long)n * K);
+    const long long* cn = conf + (size_t)n * (K + 1) * K;
+    long long row = 0, col = 0, top = 0;
+    int arg = -1;
+    for (int j = 0; j < K; ++j) {
+        const long long v = cn[(size_t)k * K + j];
+        row += v;
+        if (j != k && v > top) {                               // strict: the lowest class among equal counts
+            top = v;
+            arg = j;
+        }
+    }
+    for (int r = 0; r <= K; ++r) col += cn[(size_t)r * K + k];
+    if (row > 0) {
+        const long long I = cn[(size_t)k * K + k];
+        const double v = (double)I / (double)(row + col - I);
+        iou[i] = v;
+        miss[i] = arg;
+        fail[i] = v < threshold ? 1 : 0;
+    } else {
+        iou[i] = __longlong_as_double(0x7ff8000000000000LL);
+        miss[i] = -1;
+        fail[i] = 0;
+    }
+}
+
+hipError_t spx_launch_failure_table(const long long* conf, int N, int K, double threshold, double* iou, int32_t* miss, uint8_t* fail,
+                                    hipStream_t s) {
+    const long long total = (long long)N * K;
+    hipLaunchKernelGGL(spx_failure_table_kernel, dim3((unsigned)((total + SPX_EVAL_THREADS - 1) / SPX_EVAL_THREADS)),
+                       dim3(SPX_EVAL_THREADS), 0, s, conf, N, K, threshold, iou, miss, fail);
+    return hipGetLastError();
+}

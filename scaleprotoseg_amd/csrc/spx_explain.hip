@@ -18,6 +18,9 @@
 // The two byte kernels share exp_store(): lanes are assigned by the ADDRESS of the output dword, so each lane forms four
 // consecutive bytes and stores them as one dword whatever W and the output pointer are; the dwords that straddle the ends of
 // an image are written byte by byte by the image each byte belongs to.  Every output byte is written exactly once.
+//
+// At the end of the file: the paired heat maps of the failure cases (failure_cases.py:188-420), spx_paired_range and
+// spx_paired_heat, which look like the heat maps above and are not: another mask, shared ranges, another divisor.
 #include "spx_overlap_sample.h"
 
 #define EXP_THREADS 256
@@ -265,5 +268,135 @@ hipError_t spx_launch_explain_dominant(const float* planes, const long long* st,
     const ExpLabels lab = {labels, label_bytes};
     hipLaunchKernelGGL(spx_explain_dominant_kernel, dim3((unsigned)((exp_image_dwords(H, W) + per - 1) / per), (unsigned)R),
                        dim3(EXP_THREADS), 0, s, spx_planes(planes, st), lab, rows, table, weights, N, C, K, J, h, w, H, W, dom);
+    return hipGetLastError();
+}
+
+// ---- paired heat maps (segmentation/analysis/failure_cases.py:188-420) ----------------------------------------------------
+// The failure cases draw the slots of two classes over the pixels of ONE of them, on a range shared between rows, and divide by
+// the maximum, not by the width of the range:
+//   row r = (n, c, a, q):   m = labels[n] == a + 1 ? u[n, c] : 0;   lo_q = min m, hi_q = max m over all pixels of all rows of slot q;
+//                           x = (m - lo_q) / hi_q in fp32;  heat = (uint8) trunc(255 * x), 255 where 255 x >= 256 (only when
+//                           lo_q < 0);  hi_q <= 0: all zeros
+// The two kernels are the range and heat kernels above with the slot between the row and its range: keys uint32 [2][Q].
+__global__ __launch_bounds__(EXP_THREADS) void spx_paired_range_kernel(SpxPlanes a, ExpLabels labels, const int32_t* __restrict__ rows,
+                                                                       int Q, int N, int C, int h, int w, int H, int W, int band_rows,
+                                                                       uint32_t* __restrict__ keys) {
+    __shared__ float s_stage[OVL_STAGE];
+    __shared__ int s_oy[EXP_BAND * 4];
+    __shared__ float s_wy[EXP_BAND * 4];
+    __shared__ uint32_t s_lo[EXP_THREADS / 64], s_hi[EXP_THREADS / 64];
+    const int tid = threadIdx.x, r = blockIdx.y;
+    const int n = rows[r * 4 + 0], c = rows[r * 4 + 1], q = rows[r * 4 + 3];
+    const long long want = (long long)rows[r * 4 + 2] + 1;
+    if (!ovl_plane_ok(n, c, N, C) || q < 0 || q >= Q) return;   // workgroup-uniform; the entry point has refused such a row
+    const int Y0 = blockIdx.x * band_rows, nrows = min(H, Y0 + band_rows) - Y0;
+    ovl_stage_band<EXP_THREADS>(a, n, c, h, w, H, Y0, nrows, s_oy, s_wy, s_stage, nullptr, 0);
+    const int wave = tid >> 6, lane = tid & 63;
+    const size_t label0 = (size_t)n * H * W;
+    uint32_t klo = 0xffffffffu, khi = 0u;
+    ovl_walk_band<EXP_THREADS>(w, W, nrows, [&](int i, int X, const int* ox, const float* wx) {
+        float m = 0.0f;
+        if (spx_label(labels.p, labels.bytes, label0 + (size_t)(Y0 + i) * W + X) == want)
+            m = ovl_value(s_stage, &s_oy[4 * i], &s_wy[4 * i], ox, wx);
+        const uint32_t key = float_key(m);
+        klo = min(klo, key);
+        khi = max(khi, key);
+    });
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        klo = min(klo, (uint32_t)__shfl_xor(klo, off));
+        khi = max(khi, (uint32_t)__shfl_xor(khi, off));
+    }
+    if (lane == 0) {
+        s_lo[wave] = klo;
+        s_hi[wave] = khi;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int v = 1; v < EXP_THREADS / 64; ++v) {
+            klo = min(klo, s_lo[v]);
+            khi = max(khi, s_hi[v]);
+        }
+        atomicMin(&keys[q], klo);
+        atomicMax(&keys[(size_t)Q + q], khi);
+    }
+}
+
+hipError_t spx_launch_paired_range(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
+                                   int R, int Q, int N, int C, int h, int w, int H, int W, void* workspace, hipStream_t s) {
+    const int band = ovl_band_plan(h, w, H, EXP_BAND);
+    if (!band) return hipErrorInvalidValue;
+    uint32_t* keys = (uint32_t*)workspace;
+    hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)Q * 4, s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(keys + Q, 0, (size_t)Q * 4, s);
+    if (e != hipSuccess) return e;
+    const ExpLabels lab = {labels, label_bytes};
+    hipLaunchKernelGGL(spx_paired_range_kernel, dim3((unsigned)((H + band - 1) / band), (unsigned)R), dim3(EXP_THREADS), 0, s,
+                       spx_planes(planes, st), lab, rows, Q, N, C, h, w, H, W, band, keys);
+    return hipGetLastError();
+}
+
+// np.uint8(255 * ((m - lo) / hi)) in float32, with the conversion's undefined case defined: 255 from 256 up
+__device__ __forceinline__ uint32_t exp_paired_byte(float m, float lo, float hi) {
+    const float r = m - lo;
+    const float x = r / hi;
+    const float v = 255.0f * x;
+    return v >= 256.0f ? 255u : (uint32_t)(int)v;
+}
+
+struct ExpPairedPixel {
+    SpxPlanes a;
+    ExpLabels labels;
+    const float* plane;
+    size_t label0;
+    long long want;
+    float lo, hi;
+    uint32_t outside;             // the byte of m = 0
+    int h, w, H, W;
+    ExpTaps taps;
+    __device__ __forceinline__ uint32_t operator()(int Y, int X) {
+        if (!(hi > 0.0f)) return 0u;
+        if (spx_label(labels.p, labels.bytes, label0 + (size_t)Y * W + X) != want) return outside;
+        taps.at(a, h, w, H, W, Y, X);
+        return exp_paired_byte(ovl_value(plane, taps.oy, taps.wy, taps.ox, taps.wx), lo, hi);
+    }
+};
+
+__global__ __launch_bounds__(EXP_THREADS) void spx_paired_heat_kernel(SpxPlanes a, ExpLabels labels, const int32_t* __restrict__ rows,
+                                                                      int Q, int N, int C, int h, int w, int H, int W,
+                                                                      const uint32_t* __restrict__ keys, uint8_t* __restrict__ heat,
+                                                                      float* __restrict__ ranges) {
+    const int r = blockIdx.y;
+    const int n = rows[r * 4 + 0], c = rows[r * 4 + 1], q = rows[r * 4 + 3];
+    if (!ovl_plane_ok(n, c, N, C) || q < 0 || q >= Q) return;   // workgroup-uniform; the entry point has refused such a row
+    ExpPairedPixel px;
+    px.a = a;
+    px.labels = labels;
+    px.plane = a.p + (long long)n * a.sn + (long long)c * a.sc;
+    px.label0 = (size_t)n * H * W;
+    px.want = (long long)rows[r * 4 + 2] + 1;
+    px.lo = key_float(keys[q]);
+    px.hi = key_float(keys[(size_t)Q + q]);
+    px.outside = px.hi > 0.0f ? exp_paired_byte(0.0f, px.lo, px.hi) : 0u;
+    px.h = h;
+    px.w = w;
+    px.H = H;
+    px.W = W;
+    px.taps.Y = -1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {                  // every row of the slot writes the same two floats
+        ranges[(size_t)q * 2 + 0] = px.lo;
+        ranges[(size_t)q * 2 + 1] = px.hi;
+    }
+    exp_store(heat, (size_t)r, H, W, px);
+}
+
+hipError_t spx_launch_paired_heat(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* rows,
+                                  int R, int Q, int N, int C, int h, int w, int H, int W, const void* workspace, uint8_t* heat,
+                                  float* ranges, hipStream_t s) {
+    const long long per = (long long)EXP_THREADS * EXP_DWORDS;
+    const ExpLabels lab = {labels, label_bytes};
+    hipLaunchKernelGGL(spx_paired_heat_kernel, dim3((unsigned)((exp_image_dwords(H, W) + per - 1) / per), (unsigned)R), dim3(EXP_THREADS),
+                       0, s, spx_planes(planes, st), lab, rows, Q, N, C, h, w, H, W, (const uint32_t*)workspace, heat, ranges);
     return hipGetLastError();
 }

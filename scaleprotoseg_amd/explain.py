@@ -1,5 +1,6 @@
-"""Explanation maps on the GPU (segmentation/analysis/sample_activations_prototype.py:71-133, sample_activations_group.py:72-131;
-the same code again in failure_cases.py:188-420): the two pictures a user looks at, as uint8 arrays.
+"""Explanation maps on the GPU (segmentation/analysis/sample_activations_prototype.py:71-133, sample_activations_group.py:72-131):
+the two pictures a user looks at, as uint8 arrays.  (failure_cases.py:188-420 looks like the same code but is not: it masks two
+classes' slots with one class, shares the range between them and divides by the maximum; that is ``failures.py``.)
 
 Definition.  Activation planes ``a[n, c, y, x]`` (fp32, latent grid ``h x w``, any strides), labels ``[N, H, W]`` (uint8, int32
 or int64; 0 = void, k + 1 = class k, anything else belongs to no class), a slot table ``[K, J]`` (channel of (class, slot) or
@@ -33,10 +34,10 @@ import torch
 
 from . import _lib, _maps
 from ._lib import SpxError
-from ._maps import LABEL_BYTES, bad_row, host_rows, strides
+from ._maps import LABEL_BYTES, bad_row, byte_output as _output, host_rows, strides, upload as _upload
 
 OFF_CLASS = 255                  # the dominant map outside the class
-MAX_ROWS = 65535                 # rows of one launch; longer row tables are cut into launches
+MAX_ROWS = _maps.MAX_MAP_ROWS    # rows of one launch; longer row tables are cut into launches
 
 
 def _check_channels(table: torch.Tensor, C: int) -> None:
@@ -49,19 +50,6 @@ def _checked(activations, labels, grid):
     planes = _maps.planes(activations, grid, "activations")
     N, C, h, w = (int(v) for v in planes.shape)
     return (planes, N, C, h, w, *_maps.label_map(labels, N, "activations"))
-
-
-def _upload(host: torch.Tensor, device) -> torch.Tensor:
-    """Device copy of a small host table through pinned memory: an asynchronous copy that never waits for the device."""
-    return host.pin_memory().to(device, non_blocking=True)
-
-
-def _output(out: Optional[torch.Tensor], shape, device) -> torch.Tensor:
-    if out is None:
-        return torch.empty(shape, dtype=torch.uint8, device=device)
-    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
-        raise SpxError(f"out must be a contiguous uint8 {tuple(shape)} tensor on {device}")
-    return out
 
 
 def activation_heat_maps(activations: torch.Tensor, labels: torch.Tensor, rows, slot_table, grid: Optional[Tuple[int, int]] = None,
