@@ -732,6 +732,36 @@ int spx_paired_heat(const float* planes, const int64_t* host_strides, const void
                     const int32_t* host_rows, int32_t R, int32_t Q, int32_t N, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
                     const void* workspace, uint8_t* heat, float* ranges, void* stream);
 
+/* Cross-scale feature aggregation (additive to ABI 17; the reference's WeightedAgg, segmentation/model/scale_head.py, called at
+ * model_multiscale.py:306-314): the features of one scale are combined with the activations of the scale above it,
+ *     a = similarity(source)   source fp32 [B, Pn, HW]: source_kind 0 = ready activations, 1 = distances under 'log'
+ *                              (log((d + 1) / (d + epsilon)), the bits the distance kernels emit), 2 = distances under 'linear' (-d)
+ *     s[b][c][px] = sum_p proto[p][c] * a[b][p][px]          proto fp32 [Pn, Cs], Cs a multiple of 16, Pn >= 1
+ *     out = s (mode 0)  |  (x + s) / 2 (mode 1)  |  sqrt(x * s) (mode 2)          out fp32 [B, Cs, HW]
+ * x: [B, Cs, HW] planes of x_dtype (0 bf16, 1 fp32) with channel stride HW and batch stride x_bstride elements (a channel slice
+ * of [B, S * Cs, H, W] is passed in place); ignored (NULL accepted) in mode 0.  The product runs on v_mfma_f32_32x32x2_f32:
+ * fp32 operands and accumulation.  One launch, no workspace.
+ *
+ * spx_scale_agg_bwd: g = dL/dout fp32 [B, Cs, HW].  s is recomputed, never saved.  Outputs, each optional (NULL = not wanted):
+ *   dx       [B, Cs, HW] contiguous, x's dtype (bf16: round to nearest even); not written in mode 0
+ *   dsource  fp32 [B, Pn, HW]; for a distance source it carries the similarity's derivative
+ *            (-(1 - epsilon) / ((d + 1)(d + epsilon)) resp. -1)
+ *   dproto   fp32 [Pn, Cs]: per-workgroup partials over slabs of 256 pixels, summed in slab order by a second kernel
+ * mode 2 follows dx = g s / (2 out), ds = g x / (2 out) in IEEE arithmetic (x s <= 0 gives what that gives).
+ * workspace: spx_scale_agg_workspace_bytes(B, Cs, Pn, HW) bytes, no initialisation needed.  No float atomics: run-to-run identical. */
+#define SPX_SAGG_NONE 0
+#define SPX_SAGG_SUM 1
+#define SPX_SAGG_MULT 2
+#define SPX_SAGG_ACTIVATIONS 0
+#define SPX_SAGG_DIST_LOG 1
+#define SPX_SAGG_DIST_LINEAR 2
+size_t spx_scale_agg_workspace_bytes(int32_t B, int32_t Cs, int32_t Pn, int32_t HW);
+int spx_scale_agg_fwd(const void* x, int32_t x_dtype, int64_t x_bstride, const float* source, int32_t source_kind, const float* proto,
+                      float* out, int32_t B, int32_t Cs, int32_t Pn, int32_t HW, int32_t mode, float epsilon, void* stream);
+int spx_scale_agg_bwd(const void* x, int32_t x_dtype, int64_t x_bstride, const float* source, int32_t source_kind, const float* proto,
+                      const float* g, void* dx, float* dsource, float* dproto, void* workspace, int32_t B, int32_t Cs, int32_t Pn,
+                      int32_t HW, int32_t mode, float epsilon, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,11 @@ Public surface mirrors the reference's module/function names for this path:
                                                      predicted label maps as bytes in the data set's ids with a confusion
                                                      matrix per image, the failing (image, class, mistaken-for) table, and
                                                      the two classes' heat maps over the failing class on shared ranges)
+    scale_aggregate, WeightedAgg, OutSum, OutMult, OutConcat, factory_output_layer
+                                                    (segmentation/model/scale_head.py, model_multiscale.py:306-314: a scale's
+                                                     features combined with the activations of the scale above - the
+                                                     scale_head_type of both PPNetMultiScale classes - as a pixel-tile
+                                                     product on the fp32 matrix pipe, no [B, Pn, Cs, H, W] temporary)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -63,8 +68,10 @@ from .functional import (  # noqa: F401
     prune_nearest_from_map,
     push_masked_argmin,
     push_min_from_features,
+    scale_aggregate,
     upsample_argext,
 )
+from .scale_head import OutConcat, OutMult, OutSum, WeightedAgg, factory_output_layer  # noqa: F401
 from .checkpoint import export_state, import_state, load_reference_state_dict  # noqa: F401
 from .loss import (  # noqa: F401
     ActivationRegularizers,

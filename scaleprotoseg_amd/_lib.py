@@ -201,6 +201,9 @@ SIGNATURES = {
     "spx_paired_range": (C.c_int, [_V, _PL, _V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V]),
     "spx_paired_heat": (C.c_int, [_V, _PL, _V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V, _V]),
     "spx_push_merge": (C.c_int, [_V, _V, _V, _I, _I, _I, _I, _I, _I, _V, C.c_int64, _V, _V, _V, _V, _V]),
+    "spx_scale_agg_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "spx_scale_agg_fwd": (C.c_int, [_V, _I, C.c_int64, _V, _I, _V, _V, _I, _I, _I, _I, _I, _F, _V]),
+    "spx_scale_agg_bwd": (C.c_int, [_V, _I, C.c_int64, _V, _I, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -26,6 +26,16 @@ def _kept_indices(unique_prototypes: Union[None, str, os.PathLike, Iterable[int]
     return sorted(int(i) for i in unique_prototypes)
 
 
+def _check_scale_head_keys(net: nn.Module, state_dict: Dict[str, torch.Tensor]) -> None:
+    """The ``scale_head.*`` entries (the "concat" head's Linear) travel in the ``state_dict`` like any parameter; with the
+    default ``strict=False`` a mismatch would pass in silence and evaluate another model, so it is refused here."""
+    have = sorted(k for k in state_dict if k.startswith("scale_head."))
+    want = sorted(k for k in net.state_dict() if k.startswith("scale_head."))
+    if have != want:
+        raise ValueError(f"checkpoint holds the scale_head entries {have}, the module expects {want}: build the module with the "
+                         "run's scale_head_type")
+
+
 def load_reference_state_dict(
     net: nn.Module,
     state_dict: Dict[str, torch.Tensor],
@@ -40,6 +50,7 @@ def load_reference_state_dict(
     are pruned to them first, so shapes and class tables match the checkpoint.  Returns what
     ``nn.Module.load_state_dict`` returns (the group phase has no ``last_layer``, the prototype phase no
     ``group_projection`` - hence ``strict=False`` by default, as in finetune_wandb_group.py:76)."""
+    _check_scale_head_keys(net, state_dict)
     keep = _kept_indices(unique_prototypes)
     P_ckpt = int(state_dict["prototype_vectors"].shape[0]) if "prototype_vectors" in state_dict else None
     if keep is not None:
@@ -69,6 +80,7 @@ def export_state(net: nn.Module) -> Dict[str, object]:
 
 def import_state(net: nn.Module, blob: Dict[str, object], strict: bool = False):
     """Inverse of ``export_state`` for a module built with the original prototype shape."""
+    _check_scale_head_keys(net, blob["state_dict"])
     ident = blob["prototype_class_identity"]
     ranges = blob["scale_num_prototypes"]
     P = int(ident.shape[0])

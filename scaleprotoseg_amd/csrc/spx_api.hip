@@ -1246,3 +1246,45 @@ int spx_reg_bwd(const spx_reg* r, const float* g_total, const float* g_terms, fl
 }
 
 }  // extern "C"
+
+static int scale_agg_check(const char* who, const void* x, int32_t x_dtype, int64_t x_bstride, const float* source, int32_t source_kind,
+                           const float* proto, int32_t B, int32_t Cs, int32_t Pn, int32_t HW, int32_t mode) {
+    if (!source || !proto) return fail("%s: NULL source / proto", who);
+    if (mode != SPX_SAGG_NONE && mode != SPX_SAGG_SUM && mode != SPX_SAGG_MULT) return fail("%s: mode %d (0 none, 1 sum, 2 mult)", who, mode);
+    if (source_kind < SPX_SAGG_ACTIVATIONS || source_kind > SPX_SAGG_DIST_LINEAR)
+        return fail("%s: source_kind %d (0 activations, 1 distances/log, 2 distances/linear)", who, source_kind);
+    if (B < 1 || HW < 1) return fail("%s: empty input (B=%d HW=%d)", who, B, HW);
+    if (Pn < 1) return fail("%s: empty scale: the aggregated scale has %d prototypes", who, Pn);
+    if (Cs < 16 || Cs % 16) return fail("%s: channels per scale %d must be a positive multiple of 16", who, Cs);
+    if ((long long)B * (Cs > Pn ? Cs : Pn) * HW >= (1LL << 40)) return fail("%s: tensor too large", who);
+    if (mode != SPX_SAGG_NONE) {
+        if (!x) return fail("%s: NULL x (modes sum / mult combine with it)", who);
+        if (x_dtype != 0 && x_dtype != 1) return fail("%s: x_dtype %d (0 bf16, 1 fp32)", who, x_dtype);
+        if (x_bstride < (int64_t)Cs * HW) return fail("%s: x batch stride %lld below Cs * HW", who, (long long)x_bstride);
+    }
+    return 0;
+}
+
+size_t spx_scale_agg_workspace_bytes(int32_t B, int32_t Cs, int32_t Pn, int32_t HW) {
+    if (B < 1 || Cs < 1 || Pn < 1 || HW < 1) return 0;
+    return spx_scale_agg_workspace(B, Cs, Pn, HW);
+}
+
+int spx_scale_agg_fwd(const void* x, int32_t x_dtype, int64_t x_bstride, const float* source, int32_t source_kind, const float* proto,
+                      float* out, int32_t B, int32_t Cs, int32_t Pn, int32_t HW, int32_t mode, float epsilon, void* stream) {
+    static const char* who = "spx_scale_agg_fwd";
+    if (int e = scale_agg_check(who, x, x_dtype, x_bstride, source, source_kind, proto, B, Cs, Pn, HW, mode)) return e;
+    if (!out) return fail("%s: NULL out", who);
+    return hip_status(spx_launch_scale_agg_fwd(x, x_dtype == 0, x_bstride, source, source_kind, proto, out, B, Cs, Pn, HW, mode, epsilon,
+                                               (hipStream_t)stream), who);
+}
+
+int spx_scale_agg_bwd(const void* x, int32_t x_dtype, int64_t x_bstride, const float* source, int32_t source_kind, const float* proto,
+                      const float* g, void* dx, float* dsource, float* dproto, void* workspace, int32_t B, int32_t Cs, int32_t Pn,
+                      int32_t HW, int32_t mode, float epsilon, void* stream) {
+    static const char* who = "spx_scale_agg_bwd";
+    if (int e = scale_agg_check(who, x, x_dtype, x_bstride, source, source_kind, proto, B, Cs, Pn, HW, mode)) return e;
+    if (!g || !workspace) return fail("%s: NULL g / workspace", who);
+    return hip_status(spx_launch_scale_agg_bwd(x, x_dtype == 0, x_bstride, source, source_kind, proto, g, dx, dsource, dproto, workspace,
+                                               B, Cs, Pn, HW, mode, epsilon, (hipStream_t)stream), who);
+}

@@ -276,3 +276,10 @@ hipError_t spx_launch_kld_pairs(const float* vals, const int32_t* labels, int B,
                                 const double* scale, int64_t* a_fx, hipStream_t s);
 hipError_t spx_launch_kld_backward(const float* vals, const int32_t* labels, int B, int J, int HW, int K, const float* lse, const float* A,
                                    const float* Cf, const float* cf_scale, float* grad, hipStream_t s);
+// cross-scale feature aggregation (spx_scale_agg.hip)
+size_t spx_scale_agg_workspace(int B, int Cs, int Pn, int HW);
+hipError_t spx_launch_scale_agg_fwd(const void* x, int x_bf16, long long x_bstride, const float* src, int src_kind, const float* proto,
+                                    float* out, int B, int Cs, int Pn, int HW, int mode, float eps, hipStream_t s);
+hipError_t spx_launch_scale_agg_bwd(const void* x, int x_bf16, long long x_bstride, const float* src, int src_kind, const float* proto,
+                                    const float* g, void* dx, float* dsrc, float* dproto, void* ws, int B, int Cs, int Pn, int HW,
+                                    int mode, float eps, hipStream_t s);

@@ -1019,3 +1019,98 @@ def upsample_argext(src: torch.Tensor, size: Tuple[int, int], largest: bool = Fa
     val = torch.empty((N, H, W), dtype=torch.float32, device=s.device)
     _lib.check(lib.spx_upsample_argext(_lib.ptr(s), N, Cc, h, w, H, W, 1 if largest else 0, _lib.ptr(idx), _lib.ptr(val), _lib.stream_ptr()))
     return idx, val
+
+
+SCALE_AGG_MODES = {"none": 0, "sum": 1, "mult": 2}
+
+
+class _ScaleAggFn(torch.autograd.Function):
+    """out = combine(x, s), s[b, c] = sum_p proto[p, c] . similarity(source)[b, p] (csrc/spx_scale_agg.hip): the forward is
+    one launch; the backward recomputes s, forms dsource and dproto on the fp32 matrix pipe and sums the dproto partials in a
+    fixed order.  Nothing but the inputs is saved."""
+
+    @staticmethod
+    def forward(ctx, x, source, proto, mode, kind, epsilon):
+        lib = _lib.load()
+        B, Pn, H, W = source.shape
+        Cs = int(proto.shape[1])
+        out = torch.empty((B, Cs, H, W), dtype=torch.float32, device=source.device)
+        xd = _x_dtype_code(x) if x is not None else 1
+        _lib.check(lib.spx_scale_agg_fwd(x.data_ptr() if x is not None else None, xd, int(x.stride(0)) if x is not None else 0,
+                                         _lib.ptr(source), kind, _lib.ptr(proto), _lib.ptr(out), B, Cs, Pn, H * W, mode,
+                                         float(epsilon), _lib.stream_ptr()))
+        ctx.save_for_backward(x, source, proto)
+        ctx.args = (mode, kind, float(epsilon))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, source, proto = ctx.saved_tensors
+        mode, kind, epsilon = ctx.args
+        B, Pn, H, W = source.shape
+        Cs = int(proto.shape[1])
+        g = g.contiguous().float()
+        need_x = x is not None and ctx.needs_input_grad[0]
+        dx = torch.empty((B, Cs, H, W), dtype=x.dtype, device=g.device) if need_x else None
+        dsrc = torch.empty_like(source) if ctx.needs_input_grad[1] else None
+        dproto = torch.empty_like(proto) if ctx.needs_input_grad[2] else None
+        ws = torch.empty(lib.spx_scale_agg_workspace_bytes(B, Cs, Pn, H * W), dtype=torch.uint8, device=g.device)
+        xd = _x_dtype_code(x) if x is not None else 1
+        _lib.check(lib.spx_scale_agg_bwd(x.data_ptr() if x is not None else None, xd, int(x.stride(0)) if x is not None else 0,
+                                         _lib.ptr(source), kind, _lib.ptr(proto), _lib.ptr(g), _lib.ptr(dx), _lib.ptr(dsrc),
+                                         _lib.ptr(dproto), _lib.ptr(ws), B, Cs, Pn, H * W, mode, epsilon, _lib.stream_ptr()))
+        return dx, dsrc, dproto, None, None, None
+
+
+def scale_aggregate(x: Optional[torch.Tensor], source: torch.Tensor, prototypes: torch.Tensor, *, mode: str,
+                    source_kind: str = "distances", activation: str = "log", epsilon: float = 1e-4) -> torch.Tensor:
+    """Cross-scale aggregation of the reference's ``WeightedAgg`` (segmentation/model/scale_head.py; model_multiscale.py:306-314)
+    without its [B, Pn, Cs, H, W] temporary: fp32 [B, Cs, H, W],
+
+        s = sum_p prototypes[p, c] . a[b, p, h, w];   mode "none": s,  "sum": (x + s) / 2,  "mult": sqrt(x . s)
+
+    ``x``: [B, Cs, H, W] bf16 / fp32 planes; a channel slice of [B, S.Cs, H, W] is read in place (any batch stride).  Not read
+    (``None`` accepted) in mode "none".  ``source``: fp32 [B, Pn, H, W]; with ``source_kind="distances"`` the similarity
+    ``activation`` ("log" with ``epsilon``, or "linear") is applied while it is loaded - the bits the distance kernels emit -
+    and the gradient on it carries the similarity's derivative; with "activations" it is taken as is.  ``prototypes``: fp32
+    [Pn, Cs] or [Pn, Cs, 1, 1], Cs a multiple of 16.  Differentiable in all three; gradients are run-to-run identical."""
+    if mode not in SCALE_AGG_MODES:
+        raise SpxError(f"scale_aggregate: unknown mode {mode!r} (one of {sorted(SCALE_AGG_MODES)})")
+    if source_kind not in ("distances", "activations"):
+        raise SpxError(f"scale_aggregate: unknown source_kind {source_kind!r} ('distances' or 'activations')")
+    kind = 0
+    if source_kind == "distances":
+        if activation not in ACT_FN:
+            raise SpxError(f"scale_aggregate: similarity {activation!r} has no kernel; apply it and pass source_kind='activations'")
+        kind = 1 + ACT_FN[activation]
+    _lib.require_gpu(source, "source")
+    _lib.require_gpu(prototypes, "prototypes")
+    if source.dim() != 4 or source.dtype != torch.float32:
+        raise SpxError(f"scale_aggregate: source must be float32 [B, Pn, H, W], got {source.dtype} {tuple(source.shape)}")
+    B, Pn, H, W = source.shape
+    if prototypes.dim() == 4 and prototypes.shape[2] == 1 and prototypes.shape[3] == 1:
+        prototypes = prototypes.reshape(prototypes.shape[0], prototypes.shape[1])
+    if prototypes.dim() != 2 or prototypes.dtype != torch.float32:
+        raise SpxError(f"scale_aggregate: prototypes must be float32 [Pn, Cs] or [Pn, Cs, 1, 1], got {prototypes.dtype} "
+                       f"{tuple(prototypes.shape)}")
+    if Pn < 1 or prototypes.shape[0] != Pn:
+        raise SpxError(f"scale_aggregate: source has {Pn} planes, prototypes {int(prototypes.shape[0])} rows (an empty scale "
+                       "cannot be aggregated)")
+    Cs = int(prototypes.shape[1])
+    if Cs < 16 or Cs % 16:
+        raise SpxError(f"scale_aggregate: channels per scale {Cs} must be a positive multiple of 16")
+    if B < 1 or H * W < 1:
+        raise SpxError(f"scale_aggregate: empty source {tuple(source.shape)}")
+    if mode == "none":
+        x = None
+    else:
+        if x is None:
+            raise SpxError(f"scale_aggregate: mode {mode!r} combines with x")
+        _lib.require_gpu(x, "x")
+        _x_dtype_code(x)
+        if tuple(x.shape) != (B, Cs, H, W):
+            raise SpxError(f"scale_aggregate: x must be [{B}, {Cs}, {H}, {W}], got {tuple(x.shape)}")
+        if (x.stride(3), x.stride(2), x.stride(1)) != (1, W, H * W) or x.stride(0) < Cs * H * W:
+            x = x.contiguous()           # (planes of another layout; a channel slice of an NCHW tensor passes as it is)
+    return _ScaleAggFn.apply(x, source.contiguous(), prototypes.contiguous(), SCALE_AGG_MODES[mode], kind, epsilon)

@@ -20,6 +20,7 @@ from .functional import (MAX_FUSED_HEAD_ROWS, BankLayout, ClassGather, SpxError,
                          cross_entropy_from_logits, identity_is_one_hot, invalidate_pack_cache, proto_head_forward,
                          push_min_from_features, shifted_labels_i32, wide_linear)
 from .loss import ClassDistances
+from .scale_head import WeightedAgg
 
 
 def _first_add_on_channels(features: nn.Module) -> int:
@@ -125,11 +126,69 @@ class _PrototypeBankMixin:
         labels0 = shifted_labels_i32(target_labels.reshape(B, -1), device)
         return ClassGather(labels=labels0, keys=keys, width=width, table=table)
 
-    def _check_fusable(self):
+    def _init_scale_head(self, scale_head_type: Optional[str], prototype_shape):
+        """model_multiscale.py:113-117: the cross-scale aggregation layer, or None."""
+        self.scale_head = None
+        if scale_head_type is not None:
+            self.scale_head = WeightedAgg(output_type=scale_head_type, channel_dim=prototype_shape[1])
+
+    def _refuse_scale_head(self, what: str):
+        """Paths that live inside the fused distance kernel see every scale's ORIGINAL features: under a scale_head the lower
+        scales' distances are taken from aggregated features, so these paths refuse instead of answering for another model."""
         if getattr(self, "scale_head", None) is not None:
-            raise SpxError("scale_head aggregation has no fused kernel (every reference config sets scale_head_type=None)")
+            raise SpxError(f"{what} runs inside the fused distance kernel, which does not carry a scale_head "
+                           "(the written distance map of forward / push_forward does)")
+
+    def _check_1x1(self):
         if self.prototype_vectors.shape[2] != 1 or self.prototype_vectors.shape[3] != 1:
             raise SpxError("only 1x1 prototypes are supported (all reference configs)")
+
+    def _check_fusable(self):
+        self._refuse_scale_head("this path")
+        self._check_1x1()
+
+    def _scale_head_chain(self, x: torch.Tensor) -> torch.Tensor:
+        """``_scale_l2_convolution`` under a scale_head (model_multiscale.py:299-317): the scales run S-1 .. 0; every scale but
+        the last first combines its channel slice with the activations of the scale above (csrc/spx_scale_agg.hip: the
+        similarity on load, s = proto^T . a on the fp32 matrix pipe, the combine in the epilogue), then the distance kernel
+        runs on that scale alone.  Autograd links the pieces: a scale's distance map receives the aggregation's gradient on
+        top of whatever else reads it."""
+        self._check_1x1()
+        if x.dim() != 4 or x.shape[1] % self.num_scales:
+            raise SpxError(f"features must be [B, {self.num_scales} x Cs, H, W], got shape {tuple(x.shape)}")
+        Cs = int(x.shape[1]) // self.num_scales
+        fn = self.prototype_activation_function
+        ranges = [tuple(int(v) for v in self.scale_num_prototypes[s]) for s in range(self.num_scales)]
+        outs: List[torch.Tensor] = []
+        for i in range(self.num_scales - 1, -1, -1):
+            lo, hi = ranges[i]
+            if hi <= lo:
+                raise SpxError(f"scale {i} has no prototypes: a scale_head cannot aggregate an empty scale")
+            xs = x[:, i * Cs:(i + 1) * Cs]
+            if i < self.num_scales - 1:
+                above = self.prototype_vectors[ranges[i + 1][0]:ranges[i + 1][1]]
+                if callable(fn):
+                    xs = self.scale_head(xs, fn(outs[-1]), above)
+                else:
+                    xs = self.scale_head.from_distances(xs, outs[-1], above, fn, self.epsilon)
+            layout = BankLayout(num_prototypes=hi - lo, num_classes=1, num_scales=1, channels_per_scale=Cs, scale_ranges=((0, hi - lo),))
+            _, d, _ = proto_head_forward(xs, self.prototype_vectors[lo:hi], None, layout, want_distances=True,
+                                         epsilon=self.epsilon, activation="linear")
+            outs.append(d)
+        return torch.cat(outs[::-1], dim=1)
+
+    def _scale_head_forward(self, conv_features, return_activations: bool, return_distances: bool):
+        """``forward_from_conv_features`` under a scale_head, in the reference's op order (model_multiscale.py:362-388): the
+        chained distance map, the similarity on it as ordinary torch code, the head on the fp32 MFMA product kernels."""
+        B, _, H, W = conv_features.shape
+        dist = self._scale_head_chain(conv_features)
+        act = self.distance_2_similarity(dist).permute(0, 2, 3, 1).reshape(B * H * W, -1)
+        logits = self.run_last_layer(act).reshape(B, H, W, -1)
+        if return_activations and not return_distances:
+            return logits, act
+        if return_activations and return_distances:
+            return logits, dist, act
+        return logits, dist
 
     def _prune_bank(self, prototypes_to_prune) -> List[int]:
         """The bank half of ``prune_prototypes`` (model_multiscale.py:400-423, :428-432): shrinks ``prototype_vectors``,
@@ -157,7 +216,10 @@ class _PrototypeBankMixin:
         return self.add_on_layers(x)
 
     def _scale_l2_convolution(self, x: torch.Tensor) -> torch.Tensor:
-        """[B,S*Cs,H,W] -> distances [B,P,H,W] (model_multiscale.py:283-317), one HIP launch."""
+        """[B,S*Cs,H,W] -> distances [B,P,H,W] (model_multiscale.py:283-317), one HIP launch (a chain of launches under a
+        scale_head)."""
+        if getattr(self, "scale_head", None) is not None:
+            return self._scale_head_chain(x)
         self._check_fusable()
         _, d, _ = proto_head_forward(
             x, self.prototype_vectors, None, self._layout(1), want_distances=True, epsilon=self.epsilon,
@@ -188,13 +250,13 @@ class _PrototypeBankMixin:
         kernel (push_multiscale_optimization.py:68-91 without the [B, P, H, W] map): (indices int64 [B, P], values [B, P]).
         ``labels_for_grid((H, W))`` returns the label map [B, H, W] at the latent resolution (the grid is only known after
         the backbone has run).  Returns None when the fused kernel does not apply (MSC list input, a
-        prototype_class_identity that is not one-hot, features off the GPU): the caller then reduces the written map."""
+        prototype_class_identity that is not one-hot, features off the GPU, a scale_head): the caller then reduces the written map."""
         return self.push_min_from_conv(self.conv_features(x), labels_for_grid, void_class=void_class, max_dist=max_dist)
 
     def push_min_from_conv(self, conv, labels_for_grid, void_class=None, max_dist: float = 1e10):
         """``push_min_distances`` on features that are already computed (the single-pass push encodes a run of images once and
         keeps the features for the gather)."""
-        if isinstance(conv, list) or not conv.is_cuda:
+        if isinstance(conv, list) or not conv.is_cuda or getattr(self, "scale_head", None) is not None:
             return None
         self._check_fusable()
         layout = self._layout(1)
@@ -234,9 +296,7 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         self.img_size = img_size
         self.bottleneck_stride = bottleneck_stride
         self.patch_classification = patch_classification
-        if scale_head_type is not None:
-            raise SpxError("scale_head_type is not supported: no reference config uses it (SURVEY.md §2 #5)")
-        self.scale_head = None
+        self._init_scale_head(scale_head_type, prototype_shape)
         self.prototype_activation_function = prototype_activation_function
         self._init_bank(prototype_shape, num_classes, num_scales)
         self.proto_layer_rf_info = proto_layer_rf_info
@@ -270,6 +330,10 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
             return [self.forward_from_conv_features(c) for c in conv_features]  # flags dropped, as in :359
         if not (hasattr(self, "patch_classification") and self.patch_classification):
             raise Exception("Original Prototype Network Implementation")
+        if self.scale_head is not None:
+            if target_labels is not None or ce_target is not None:
+                raise SpxError("target_labels / ce_target live in the fused distance kernel's epilogues, which do not carry a scale_head")
+            return self._scale_head_forward(conv_features, return_activations, return_distances)
         self._check_fusable()
         B, _, H, W = conv_features.shape
         if callable(self.prototype_activation_function):

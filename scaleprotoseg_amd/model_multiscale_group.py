@@ -93,11 +93,9 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         self.patch_classification = patch_classification
         self.num_groups = num_groups
         self.incorrect_strength = incorrect_strength
-        if scale_head_type is not None:
-            raise SpxError("scale_head_type is not supported: no reference config uses it")
         if equiv_path is not None:
             raise SpxError("equiv_path initialisation is deprecated in the reference (NOT USED) and not built")
-        self.scale_head = None
+        self._init_scale_head(scale_head_type, prototype_shape)
         self.prototype_activation_function = prototype_activation_function
         self._init_bank(prototype_shape, num_classes, num_scales)
         self.proto_layer_rf_info = proto_layer_rf_info
@@ -220,6 +218,10 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
             return [self.forward_from_conv_features(c) for c in conv_features]
         if not (hasattr(self, "patch_classification") and self.patch_classification):
             raise Exception("Original Prototype Network Implementation")
+        if self.scale_head is not None:
+            if ce_target is not None:
+                raise SpxError("ce_target lives in the fused distance kernel's epilogue, which does not carry a scale_head")
+            return self._scale_head_forward(conv_features, return_activations, return_distances)
         self._check_fusable()
         B, _, H, W = conv_features.shape
         wd = self._dense_group_matrix()

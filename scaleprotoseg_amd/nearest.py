@@ -279,6 +279,8 @@ def nearest_images_to_prototypes(dataset, ppnet, n: int = 3, *, batch_size: int 
     if int(batch_size) < 1:
         raise SpxError(f"batch_size = {batch_size} must be positive")
     _rank(q, 2)
+    if getattr(net, "scale_head", None) is not None:
+        net._refuse_scale_head("nearest_images_to_prototypes")
     net.eval()
     dev = torch.device(str(net.prototype_vectors.device))
     P = net.num_prototypes

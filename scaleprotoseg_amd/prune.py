@@ -171,6 +171,8 @@ def find_k_nearest_patches_to_prototypes(
         raise SpxError(f"k = {k} outside 1..{MAX_K}")
     if batch_size < 1:
         raise SpxError(f"batch_size = {batch_size} must be positive")
+    if getattr(net, "scale_head", None) is not None:
+        net._refuse_scale_head("the pruning search")
     net.eval()
     dev = torch.device(device or str(net.prototype_vectors.device))
     _lib.require_gpu(dev, "the model")

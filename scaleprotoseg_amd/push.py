@@ -265,6 +265,8 @@ def push_single_pass(dataset, ppnet, batch_size: int = 8, void_class: Optional[i
     net = unwrap(ppnet)
     if int(batch_size) < 1:
         raise SpxError(f"batch_size = {batch_size} must be positive")
+    if getattr(net, "scale_head", None) is not None:
+        net._refuse_scale_head("the single-pass push (batch_size=)")
     net.eval()
     dev = torch.device(device or str(net.prototype_vectors.device))
     P, S, Cs = net.num_prototypes, net.num_scales, int(net.prototype_shape[1])
