@@ -762,6 +762,66 @@ int spx_scale_agg_bwd(const void* x, int32_t x_dtype, int64_t x_bstride, const f
                       const float* g, void* dx, float* dsource, float* dproto, void* workspace, int32_t B, int32_t Cs, int32_t Pn,
                       int32_t HW, int32_t mode, float epsilon, void* stream);
 
+/* Part consistency and stability (additive to ABI 17; segmentation/analysis/metrics/consistency.py:186-270 and :165-178,
+ * stability.py:169-175): which prototypes or groups of a class fire at the centroids of the annotated object parts.
+ *   labels [N, H, W] (label_bytes 1 / 4 / 8): 0 = void, k + 1 = class k < K, anything else no class
+ *   parts  [N, H, W] (part_bytes 1 / 4 / 8): t in 1..M = part t, anything else no part (the reference raises above M)
+ *   B_t = (labels == k + 1) & (parts == t); a pixel's key (k, t) is k * M + t - 1.
+ *
+ * spx_part_components: the 8-connected components of every B_t of every image in one labelling over the joint key (neighbours
+ * are joined when their keys are equal): union-find, 32 x 32 tiles labelled in LDS, a border-merge launch, a flatten launch.
+ * Every parent is at most its own pixel index and only atomicMin lowers it, so every find / union loop ends; no workgroup waits
+ * for another, kernel boundaries order the launches, and every cross-workgroup access to a parent is an agent-scope atomic.
+ *   workspace  spx_part_components_workspace_bytes(N, H, W) bytes (0 and spx_last_error for bad sizes), no initialisation needed,
+ *              and the result: [sumx uint64 N*H*W | sumy uint64 N*H*W | parent uint32 N*H*W | count uint32 N*H*W].
+ *              parent[n][i] = the smallest pixel index Y * W + X of the pixel's component (0xffffffff: no key); at that root
+ *              count / sumx / sumy = the component's pixels and the integer sums of their X and Y; 0 at every other pixel.
+ *   totals     uint64 [N, K, M, 3] = (count, sum X, sum Y) of B_t: the complement's centroid follows by subtraction.
+ * Integer atomics only: two runs agree bit for bit.
+ *
+ * spx_part_thresholds: T[n, k, j] fp32 [N, K, J] for the slots of slot_table int32 [K, J] (channel or -1) of
+ *   u[Y, X] = labels[n, Y, X] == k + 1 ? a[n, c, sy(Y), sx(X)] : +0,   sx(X) = min(floor(X * (1.0 / (W / w))), w - 1) in float64
+ *   (the source index of OpenCV's INTER_NEAREST, sy alike with H / h; planes / host_strides as spx_overlap_thresholds takes them)
+ *   mode SPX_PART_IMAGE    np.quantile(u, q) over all H * W values
+ *   mode SPX_PART_NONZERO  np.quantile(u[u != 0], q); +inf when there is none
+ * with the rank formed on the device in float64 as spx_masked_thresholds forms it and numpy's fp32 _lerp.  One pass over the labels
+ * counts the pixels of every class per latent cell; one workgroup per (n, k, j) then selects over the h * w cell values with those
+ * multiplicities (and the zero, H * W - n_k times, in image mode).  The [H, W] plane is never formed.  A slot without a channel in
+ * [0, C) and a class with skip[k] != 0 (skip uint8 [K] or NULL) get NaN.  workspace: spx_part_thresholds_workspace_bytes(N, K, h, w)
+ * bytes, no initialisation needed.
+ *
+ * spx_part_presence: given the labelling (comp_workspace, totals) and thresholds fp32 [N, K, J] of the same labels,
+ *   valid uint8 [N, K]           1 when class k is not skipped and some B_t of image n is not empty
+ *   table uint8 [N, K, J, M + 1] 255 (absent) in a row that is not valid, for a slot without a channel, in column 0 and for an empty
+ *                                B_t; else 1 when u[cy, cx] > T (strict) at the centroid of any component of B_t or of the
+ *                                complement of B_t within the image (the label-0 row of cv2.connectedComponentsWithStats, which
+ *                                consistency.py:264 walks too; none when B_t is the whole image), else 0.
+ *   centroid = (rint(sum X / count), rint(sum Y / count)), the quotients in float64: np.round, half to even.
+ * Every byte is written by an initialising launch; later launches store only the byte 1.
+ *
+ * spx_part_fold_consistency: counters int64 [ones K*J*(M+1) | times present K*J*(M+1) | rows K*J], ADDED to, over the valid rows
+ * of the batch and the slots with a channel.  spx_part_fold_stability: counters int64 [stable rows, valid rows], ADDED to: a valid
+ * row is stable when all M + 1 entries of the two tables agree with absent read as 0 (stability.py:242).
+ * No host read, no synchronisation; every launch goes to `stream`.  Limits: N <= 65535, K <= 1024, J <= 32, 1 <= M <= 254, the
+ * map limits of spx_overlap_accumulate. */
+#define SPX_PART_IMAGE 0
+#define SPX_PART_NONZERO 1
+size_t spx_part_components_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int spx_part_components(const void* labels, int32_t label_bytes, const void* parts, int32_t part_bytes, int32_t N, int32_t K, int32_t M,
+                        int32_t H, int32_t W, void* workspace, uint64_t* totals, void* stream);
+size_t spx_part_thresholds_workspace_bytes(int32_t N, int32_t K, int32_t h, int32_t w);
+int spx_part_thresholds(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* slot_table,
+                        const uint8_t* skip, int32_t N, int32_t C, int32_t K, int32_t J, int32_t h, int32_t w, int32_t H, int32_t W,
+                        double q, int32_t mode, void* workspace, float* thresholds, void* stream);
+int spx_part_presence(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const void* parts,
+                      int32_t part_bytes, const int32_t* slot_table, const uint8_t* skip, const float* thresholds,
+                      const void* comp_workspace, const uint64_t* totals, int32_t N, int32_t C, int32_t K, int32_t J, int32_t M, int32_t h,
+                      int32_t w, int32_t H, int32_t W, uint8_t* table, uint8_t* valid, void* stream);
+int spx_part_fold_consistency(const uint8_t* table, const uint8_t* valid, const int32_t* slot_table, int32_t N, int32_t C, int32_t K,
+                              int32_t J, int32_t M, int64_t* counters, void* stream);
+int spx_part_fold_stability(const uint8_t* clean, const uint8_t* noisy, const uint8_t* valid, const int32_t* slot_table, int32_t N, int32_t C,
+                            int32_t K, int32_t J, int32_t M, int64_t* counters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,10 @@ Public surface mirrors the reference's module/function names for this path:
                                                      features combined with the activations of the scale above - the
                                                      scale_head_type of both PPNetMultiScale classes - as a pixel-tile
                                                      product on the fp32 matrix pipe, no [B, Pn, Cs, H, W] temporary)
+    PartConsistency, PartStability, part_presence, part_thresholds, part_components
+                                                    (segmentation/analysis/metrics/consistency.py, stability.py: which
+                                                     prototypes or groups fire at the centroids of the annotated parts'
+                                                     connected components; union-find labelling, weighted exact quantile)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -118,6 +122,16 @@ from .failures import (  # noqa: F401
     failure_table,
     paired_heat_maps,
     predict_label_maps,
+)
+from .parts import (  # noqa: F401
+    PartComponents,
+    PartConsistency,
+    PartConsistencyResult,
+    PartStability,
+    PartStabilityResult,
+    part_components,
+    part_presence,
+    part_thresholds,
 )
 from .prune import NearestPatches, find_k_nearest_patches_to_prototypes, prune_prototypes  # noqa: F401
 from .utils import (  # noqa: F401

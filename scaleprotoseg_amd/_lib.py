@@ -204,6 +204,13 @@ SIGNATURES = {
     "spx_scale_agg_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "spx_scale_agg_fwd": (C.c_int, [_V, _I, C.c_int64, _V, _I, _V, _V, _I, _I, _I, _I, _I, _F, _V]),
     "spx_scale_agg_bwd": (C.c_int, [_V, _I, C.c_int64, _V, _I, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _F, _V]),
+    "spx_part_components_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "spx_part_components": (C.c_int, [_V, _I, _V, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "spx_part_thresholds_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "spx_part_thresholds": (C.c_int, [_V, _PL, _V, _I, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, C.c_double, _I, _V, _V, _V]),
+    "spx_part_presence": (C.c_int, [_V, _PL, _V, _I, _V, _I, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "spx_part_fold_consistency": (C.c_int, [_V, _V, _V, _I, _I, _I, _I, _I, _V, _V]),
+    "spx_part_fold_stability": (C.c_int, [_V, _V, _V, _V, _I, _I, _I, _I, _I, _V, _V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1288,3 +1288,101 @@ int spx_scale_agg_bwd(const void* x, int32_t x_dtype, int64_t x_bstride, const f
     return hip_status(spx_launch_scale_agg_bwd(x, x_dtype == 0, x_bstride, source, source_kind, proto, g, dx, dsource, dproto, workspace,
                                                B, Cs, Pn, HW, mode, epsilon, (hipStream_t)stream), who);
 }
+
+// what the part-metric entry points check alike: the maps [N, H, W] and the (class, part) key space
+#define SPX_PRT_MAX_PARTS 254
+static int parts_maps_check(const char* who, const void* labels, int32_t label_bytes, int32_t N, int32_t K, int32_t M, int32_t H,
+                            int32_t W) {
+    if (!labels) return fail("%s: NULL labels", who);
+    if (int e = check_label_bytes(who, label_bytes)) return e;
+    if (N < 1 || N > 65535 || K < 1 || K > SPX_EVAL_MAX_CLASSES)
+        return fail("%s: bad sizes (N=%d K=%d; 1 <= N <= 65535, 1 <= K <= %d)", who, N, K, SPX_EVAL_MAX_CLASSES);
+    if (M < 1 || M > SPX_PRT_MAX_PARTS) return fail("%s: max_parts %d outside 1..%d", who, M, SPX_PRT_MAX_PARTS);
+    if (H < 1 || W < 1 || (long long)H * W >= (1LL << 31) || H > SPX_OVL_MAX_OUT || W > SPX_OVL_MAX_OUT)
+        return fail("%s: maps %d x %d (1 <= H, W <= %d, H*W < 2^31)", who, H, W, SPX_OVL_MAX_OUT);
+    return 0;
+}
+static int parts_slots_check(const char* who, const int32_t* slot_table, int32_t J) {
+    if (!slot_table) return fail("%s: NULL slot table", who);
+    if (J < 1 || J > SPX_OVL_MAX_SLOTS) return fail("%s: %d slots per class (1..%d)", who, J, SPX_OVL_MAX_SLOTS);
+    return 0;
+}
+
+size_t spx_part_components_workspace_bytes(int32_t N, int32_t H, int32_t W) {
+    if (N < 1 || N > 65535 || H < 1 || W < 1 || (long long)H * W >= (1LL << 31)) {
+        fail("spx_part_components_workspace_bytes: bad sizes (N=%d H=%d W=%d)", N, H, W);
+        return 0;
+    }
+    return spx_parts_comp_ws_bytes(N, H, W);
+}
+
+int spx_part_components(const void* labels, int32_t label_bytes, const void* parts, int32_t part_bytes, int32_t N, int32_t K, int32_t M,
+                        int32_t H, int32_t W, void* workspace, uint64_t* totals, void* stream) {
+    static const char* who = "spx_part_components";
+    if (!parts || !workspace || !totals) return fail("%s: NULL parts / workspace / totals", who);
+    if (int e = check_label_bytes(who, part_bytes)) return e;
+    if (int e = parts_maps_check(who, labels, label_bytes, N, K, M, H, W)) return e;
+    return hip_status(spx_launch_part_components(labels, label_bytes, parts, part_bytes, N, K, M, H, W, workspace,
+                                                 (unsigned long long*)totals, (hipStream_t)stream), who);
+}
+
+size_t spx_part_thresholds_workspace_bytes(int32_t N, int32_t K, int32_t h, int32_t w) {
+    if (N < 1 || N > 65535 || K < 1 || K > SPX_EVAL_MAX_CLASSES || h < 1 || w < 1 || (long long)h * w >= (1LL << 31)) {
+        fail("spx_part_thresholds_workspace_bytes: bad sizes (N=%d K=%d h=%d w=%d)", N, K, h, w);
+        return 0;
+    }
+    return spx_parts_thr_ws_bytes(N, K, h, w);
+}
+
+int spx_part_thresholds(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const int32_t* slot_table,
+                        const uint8_t* skip, int32_t N, int32_t C, int32_t K, int32_t J, int32_t h, int32_t w, int32_t H, int32_t W,
+                        double q, int32_t mode, void* workspace, float* thresholds, void* stream) {
+    static const char* who = "spx_part_thresholds";
+    if (!thresholds) return fail("%s: NULL thresholds", who);
+    if (mode != SPX_PART_IMAGE && mode != SPX_PART_NONZERO) return fail("%s: mode %d (0 image, 1 nonzero)", who, mode);
+    if (!(q > 0.0 && q < 1.0)) return fail("%s: quantile %g outside 0 < q < 1", who, q);
+    if (int e = parts_maps_check(who, labels, label_bytes, N, K, 1, H, W)) return e;
+    if (int e = parts_slots_check(who, slot_table, J)) return e;
+    if (int e = overlap_check(who, planes, host_strides, N, C, h, w, H, W, workspace)) return e;
+    return hip_status(spx_launch_part_thresholds(planes, (const long long*)host_strides, labels, label_bytes, slot_table, skip, N, C, K, J,
+                                                 h, w, H, W, q, mode, workspace, thresholds, (hipStream_t)stream), who);
+}
+
+int spx_part_presence(const float* planes, const int64_t* host_strides, const void* labels, int32_t label_bytes, const void* parts,
+                      int32_t part_bytes, const int32_t* slot_table, const uint8_t* skip, const float* thresholds,
+                      const void* comp_workspace, const uint64_t* totals, int32_t N, int32_t C, int32_t K, int32_t J, int32_t M, int32_t h,
+                      int32_t w, int32_t H, int32_t W, uint8_t* table, uint8_t* valid, void* stream) {
+    static const char* who = "spx_part_presence";
+    if (!parts || !thresholds || !totals || !table || !valid) return fail("%s: NULL parts / thresholds / totals / outputs", who);
+    if (int e = check_label_bytes(who, part_bytes)) return e;
+    if (int e = parts_maps_check(who, labels, label_bytes, N, K, M, H, W)) return e;
+    if (int e = parts_slots_check(who, slot_table, J)) return e;
+    if (int e = overlap_check(who, planes, host_strides, N, C, h, w, H, W, comp_workspace)) return e;
+    return hip_status(spx_launch_part_presence(planes, (const long long*)host_strides, labels, label_bytes, parts, part_bytes, slot_table,
+                                               skip, thresholds, comp_workspace, (const unsigned long long*)totals, N, C, K, J, M, h, w, H,
+                                               W, table, valid, (hipStream_t)stream), who);
+}
+
+static int parts_fold_check(const char* who, const void* a, const void* b, const void* valid, const int32_t* slot_table, const void* counters,
+                            int32_t N, int32_t C, int32_t K, int32_t J, int32_t M) {
+    if (!a || !b || !valid || !counters) return fail("%s: NULL table / valid flags / counters", who);
+    if (int e = parts_slots_check(who, slot_table, J)) return e;
+    if (N < 1 || N > 65535 || C < 1 || K < 1 || K > SPX_EVAL_MAX_CLASSES || M < 1 || M > SPX_PRT_MAX_PARTS)
+        return fail("%s: bad sizes (N=%d C=%d K=%d max_parts=%d)", who, N, C, K, M);
+    return 0;
+}
+
+int spx_part_fold_consistency(const uint8_t* table, const uint8_t* valid, const int32_t* slot_table, int32_t N, int32_t C, int32_t K,
+                              int32_t J, int32_t M, int64_t* counters, void* stream) {
+    static const char* who = "spx_part_fold_consistency";
+    if (int e = parts_fold_check(who, table, table, valid, slot_table, counters, N, C, K, J, M)) return e;
+    return hip_status(spx_launch_part_fold_consistency(table, valid, slot_table, N, C, K, J, M, (long long*)counters, (hipStream_t)stream), who);
+}
+
+int spx_part_fold_stability(const uint8_t* clean, const uint8_t* noisy, const uint8_t* valid, const int32_t* slot_table, int32_t N, int32_t C,
+                            int32_t K, int32_t J, int32_t M, int64_t* counters, void* stream) {
+    static const char* who = "spx_part_fold_stability";
+    if (int e = parts_fold_check(who, clean, noisy, valid, slot_table, counters, N, C, K, J, M)) return e;
+    return hip_status(spx_launch_part_fold_stability(clean, noisy, valid, slot_table, N, C, K, J, M, (unsigned long long*)counters,
+                                                     (hipStream_t)stream), who);
+}

@@ -283,3 +283,19 @@ hipError_t spx_launch_scale_agg_fwd(const void* x, int x_bf16, long long x_bstri
 hipError_t spx_launch_scale_agg_bwd(const void* x, int x_bf16, long long x_bstride, const float* src, int src_kind, const float* proto,
                                     const float* g, void* dx, float* dsrc, float* dproto, void* ws, int B, int Cs, int Pn, int HW,
                                     int mode, float eps, hipStream_t s);
+// part consistency / stability (spx_parts.hip)
+size_t spx_parts_comp_ws_bytes(int N, int H, int W);
+size_t spx_parts_thr_ws_bytes(int N, int K, int h, int w);
+hipError_t spx_launch_part_components(const void* labels, int label_bytes, const void* parts, int part_bytes, int N, int K, int M, int H,
+                                      int W, void* workspace, unsigned long long* totals, hipStream_t s);
+hipError_t spx_launch_part_thresholds(const float* planes, const long long* st, const void* labels, int label_bytes, const int32_t* table,
+                                      const uint8_t* skip, int N, int C, int K, int J, int h, int w, int H, int W, double q, int mode,
+                                      void* workspace, float* thresholds, hipStream_t s);
+hipError_t spx_launch_part_presence(const float* planes, const long long* st, const void* labels, int label_bytes, const void* parts,
+                                    int part_bytes, const int32_t* table, const uint8_t* skip, const float* thresholds,
+                                    const void* comp_workspace, const unsigned long long* totals, int N, int C, int K, int J, int M, int h,
+                                    int w, int H, int W, uint8_t* out, uint8_t* valid, hipStream_t s);
+hipError_t spx_launch_part_fold_consistency(const uint8_t* tab, const uint8_t* valid, const int32_t* table, int N, int C, int K, int J, int M,
+                                            long long* counters, hipStream_t s);
+hipError_t spx_launch_part_fold_stability(const uint8_t* clean, const uint8_t* noisy, const uint8_t* valid, const int32_t* table, int N, int C,
+                                          int K, int J, int M, unsigned long long* counters, hipStream_t s);
