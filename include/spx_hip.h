@@ -822,6 +822,74 @@ int spx_part_fold_consistency(const uint8_t* table, const uint8_t* valid, const 
 int spx_part_fold_stability(const uint8_t* clean, const uint8_t* noisy, const uint8_t* valid, const int32_t* slot_table, int32_t N, int32_t C,
                             int32_t K, int32_t J, int32_t M, int64_t* counters, void* stream);
 
+/* Training-batch preparation (additive to ABI 17; segmentation/data/dataset.py:143-186, resize_label of dataset.py:22-30 and its
+ * per-step use in module_multiscale.py:234-236): from raw uint8 HWC images and integer labels already on the device, ONE launch
+ * writes the scaled, padded, cropped, flipped and normalised window batch, the window labels and the latent labels of up to
+ * SPX_BATCH_MAX_GRIDS grids.  No workspace, no atomics, no host read; every thread writes its own elements, so two runs agree bit
+ * for bit.
+ *
+ * One spx_batch_sample per sample, in DEVICE memory.  The scaled image is never formed: window pixel (y, x) of a sample is
+ *   x' = flip ? Wc - 1 - x : x,   (sy, sx) = (y0 + y, x0 + x')        the position in the scaled, padded image
+ * pad region (sy >= hs or sx >= ws, or a negative position):
+ *   image  0 when normalising (the reference pads with `mean` and normalises afterwards), mean[c] otherwise,
+ *          rint(mean[c] * 255) saturated to 0..255 for uint8 output;   label 0
+ * inside, image: bilinear at the sample position of OpenCV's INTER_LINEAR, every operation in fp32 in this order (the library is
+ * built with -ffp-contract=off; tests/batch_restatement.py restates it in NumPy float32 and matches bit for bit):
+ *   rx = float(w) / float(ws);  fx = (sx + 0.5f) * rx - 0.5f, raised to 0 when negative;  x0 = floor(fx);  a = fx - x0;
+ *   x1 = min(x0 + 1, w - 1);  x0 >= w - 1: x0 = x1 = w - 1, a = 0;      the same in y with b
+ *   v = (p00 * (1 - a) + p01 * a) * (1 - b) + (p10 * (1 - a) + p11 * a) * b         p = the source bytes as fp32
+ *   r = round_u8 ? rintf(v) : v
+ *   fp32 output  normalize ? (r / 255.0f - mean[c]) / std[c] : r / 255.0f;      uint8 output (needs round_u8): the byte r
+ * OpenCV's own INTER_LINEAR works in 11-bit fixed point: it was never run against this rule.
+ * inside, label: src[index[row_tab + sy]][index[col_tab + sx]] - the caller's tables of PIL's NEAREST rule, h -> hs and w -> ws -
+ * then id_map[raw] when an id table is given (a raw value outside 0..L-1 becomes 0; dataset.py:134 `convert_targets`).
+ * latent labels of grid g: the window label at (index[grid_rt[g] + y], index[grid_ct[g] + x]), the tables Hc -> grid_h[g] and
+ * Wc -> grid_w[g] shared by all samples: resize_label of the window, as composing index tables equals resampling twice.
+ * latent[g] int64 [B, grid_h, grid_w] in the reference's convention (0 = void); latent0[g] int32, the same minus one under the
+ * rule of spx_shift_labels (a value whose v - 1 leaves int32 is -1).  Either may be NULL.
+ * A table entry is clamped into the source and a sample whose tables do not lie inside `index` (n_index entries) is written as
+ * pad, so no descriptor can make the kernel read outside `index`; the image and label pointers are the caller's promise.
+ *
+ * spx_resize_labels: the latent-label half alone for labels [B, Hc, Wc] already on the device (labels_in, labels_dtype): reads
+ * `index`, `id_map`, the grids and latent / latent0; `samples`, `image_out` and `window_labels` are not read.
+ * Limits: 1 <= B <= 65535, Hc * Wc < 2^31 - 256 and the same for every grid, G <= 4 (at least one output in all), L >= 0. */
+#define SPX_BATCH_MAX_GRIDS 4
+#define SPX_LABEL_U8 1      /* label dtype codes: the element's size in bytes */
+#define SPX_LABEL_I16 2
+#define SPX_LABEL_I32 4
+#define SPX_LABEL_I64 8
+typedef struct spx_batch_sample {
+    const void* image;          /* uint8, channel stride 1: pixel (Y, X) at image + Y * image_row_stride + X * image_pixel_stride */
+    const void* label;          /* [h, w], element stride 1 within a row */
+    int64_t image_row_stride;   /* bytes */
+    int64_t label_row_stride;   /* elements */
+    int32_t image_pixel_stride; /* bytes (3 for packed HWC) */
+    int32_t label_dtype;        /* SPX_LABEL_* */
+    int32_t h, w;               /* source size */
+    int32_t hs, ws;             /* scaled size, both >= 1 */
+    int32_t y0, x0;             /* crop origin in the scaled, padded image */
+    int32_t flip;
+    int32_t row_tab, col_tab;   /* offsets into `index`: hs entries in 0..h-1, ws entries in 0..w-1 */
+    int32_t reserved;
+} spx_batch_sample;             /* 80 bytes */
+typedef struct spx_batch {
+    const spx_batch_sample* samples;    /* DEVICE [B] */
+    const int32_t* index;               /* DEVICE [n_index] */
+    const int32_t* id_map;              /* DEVICE [L] or NULL */
+    const void* labels_in;              /* spx_resize_labels only: [B, Hc, Wc] */
+    void* image_out;                    /* [B, 3, Hc, Wc] fp32 or uint8, or NULL */
+    int64_t* window_labels;             /* [B, Hc, Wc] or NULL */
+    int64_t* latent[SPX_BATCH_MAX_GRIDS];
+    int32_t* latent0[SPX_BATCH_MAX_GRIDS];
+    int32_t n_index, L, labels_dtype, B, Hc, Wc, G;
+    int32_t grid_h[SPX_BATCH_MAX_GRIDS], grid_w[SPX_BATCH_MAX_GRIDS];
+    int32_t grid_rt[SPX_BATCH_MAX_GRIDS], grid_ct[SPX_BATCH_MAX_GRIDS];     /* offsets into `index` */
+    int32_t normalize, round_u8, out_u8;
+    float mean[3], std[3];
+} spx_batch;
+int spx_batch_prepare(const spx_batch* args, void* stream);
+int spx_resize_labels(const spx_batch* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

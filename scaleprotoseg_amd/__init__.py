@@ -55,6 +55,10 @@ Public surface mirrors the reference's module/function names for this path:
                                                     (segmentation/analysis/metrics/consistency.py, stability.py: which
                                                      prototypes or groups fire at the centroids of the annotated parts'
                                                      connected components; union-find labelling, weighted exact quantile)
+    prepare_batch, resize_labels, draw_augmentation, BatchTable, fill_batch_table
+                                                    (segmentation/data/dataset.py:143-186 and the per-step resize_label of
+                                                     module_multiscale.py:234-236: the augmented, normalised window batch, its
+                                                     labels and the latent labels of every grid from raw uint8 images, one launch)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -132,6 +136,15 @@ from .parts import (  # noqa: F401
     part_components,
     part_presence,
     part_thresholds,
+)
+from .batch import (  # noqa: F401
+    AugmentParams,
+    BatchTable,
+    PreparedBatch,
+    draw_augmentation,
+    fill_batch_table,
+    prepare_batch,
+    resize_labels,
 )
 from .prune import NearestPatches, find_k_nearest_patches_to_prototypes, prune_prototypes  # noqa: F401
 from .utils import (  # noqa: F401

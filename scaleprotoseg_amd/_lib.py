@@ -100,7 +100,65 @@ class SpxActLoss(C.Structure):
     ]
 
 
+SPX_BATCH_MAX_GRIDS = 4
+
+
+class SpxBatchSample(C.Structure):
+    """spx_batch_sample of include/spx_hip.h: one sample's descriptor of spx_batch_prepare (80 bytes, in device memory)."""
+
+    _fields_ = [
+        ("image", C.c_void_p),
+        ("label", C.c_void_p),
+        ("image_row_stride", C.c_int64),
+        ("label_row_stride", C.c_int64),
+        ("image_pixel_stride", C.c_int32),
+        ("label_dtype", C.c_int32),
+        ("h", C.c_int32),
+        ("w", C.c_int32),
+        ("hs", C.c_int32),
+        ("ws", C.c_int32),
+        ("y0", C.c_int32),
+        ("x0", C.c_int32),
+        ("flip", C.c_int32),
+        ("row_tab", C.c_int32),
+        ("col_tab", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class SpxBatch(C.Structure):
+    """spx_batch of include/spx_hip.h: the batch-wide arguments of spx_batch_prepare / spx_resize_labels."""
+
+    _fields_ = [
+        ("samples", C.c_void_p),
+        ("index", C.c_void_p),
+        ("id_map", C.c_void_p),
+        ("labels_in", C.c_void_p),
+        ("image_out", C.c_void_p),
+        ("window_labels", C.c_void_p),
+        ("latent", C.c_void_p * SPX_BATCH_MAX_GRIDS),
+        ("latent0", C.c_void_p * SPX_BATCH_MAX_GRIDS),
+        ("n_index", C.c_int32),
+        ("L", C.c_int32),
+        ("labels_dtype", C.c_int32),
+        ("B", C.c_int32),
+        ("Hc", C.c_int32),
+        ("Wc", C.c_int32),
+        ("G", C.c_int32),
+        ("grid_h", C.c_int32 * SPX_BATCH_MAX_GRIDS),
+        ("grid_w", C.c_int32 * SPX_BATCH_MAX_GRIDS),
+        ("grid_rt", C.c_int32 * SPX_BATCH_MAX_GRIDS),
+        ("grid_ct", C.c_int32 * SPX_BATCH_MAX_GRIDS),
+        ("normalize", C.c_int32),
+        ("round_u8", C.c_int32),
+        ("out_u8", C.c_int32),
+        ("mean", C.c_float * 3),
+        ("std", C.c_float * 3),
+    ]
+
+
 _PP = C.POINTER(SpxPlan)
+_PB = C.POINTER(SpxBatch)
 _PCE = C.POINTER(SpxCe)
 _PR = C.POINTER(SpxReg)
 _PA = C.POINTER(SpxActLoss)
@@ -211,6 +269,8 @@ SIGNATURES = {
     "spx_part_presence": (C.c_int, [_V, _PL, _V, _I, _V, _I, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
     "spx_part_fold_consistency": (C.c_int, [_V, _V, _V, _I, _I, _I, _I, _I, _V, _V]),
     "spx_part_fold_stability": (C.c_int, [_V, _V, _V, _V, _I, _I, _I, _I, _I, _V, _V]),
+    "spx_batch_prepare": (C.c_int, [_PB, _V]),
+    "spx_resize_labels": (C.c_int, [_PB, _V]),
 }
 
 _lib: Optional[C.CDLL] = None

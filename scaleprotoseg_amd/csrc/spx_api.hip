@@ -1386,3 +1386,50 @@ int spx_part_fold_stability(const uint8_t* clean, const uint8_t* noisy, const ui
     return hip_status(spx_launch_part_fold_stability(clean, noisy, valid, slot_table, N, C, K, J, M, (unsigned long long*)counters,
                                                      (hipStream_t)stream), who);
 }
+
+// what the two batch entry points check alike: the sizes, the id table, the grids and their tables, the latent outputs
+static int batch_check(const char* who, const spx_batch* a) {
+    if (!a) return fail("%s: NULL arguments", who);
+    if (!a->index || a->n_index < 1) return fail("%s: NULL or empty index buffer", who);
+    if (a->B < 1 || a->B > 65535) return fail("%s: batch %d outside 1..65535", who, a->B);
+    if (a->Hc < 1 || a->Wc < 1 || (long long)a->Hc * a->Wc >= (1LL << 31) - 256)
+        return fail("%s: window %d x %d (both >= 1, Hc * Wc < 2^31 - 256)", who, a->Hc, a->Wc);
+    if (a->L < 0 || (a->L > 0 && !a->id_map) || (a->id_map && a->L < 1))
+        return fail("%s: id table of %d entries (NULL with 0, a pointer with L >= 1)", who, a->L);
+    if (a->G < 0 || a->G > SPX_BATCH_MAX_GRIDS) return fail("%s: %d latent grids (0..%d)", who, a->G, SPX_BATCH_MAX_GRIDS);
+    for (int g = 0; g < a->G; ++g) {
+        if (a->grid_h[g] < 1 || a->grid_w[g] < 1 || (long long)a->grid_h[g] * a->grid_w[g] >= (1LL << 31) - 256)
+            return fail("%s: latent grid %d is %d x %d", who, g, a->grid_h[g], a->grid_w[g]);
+        if (a->grid_rt[g] < 0 || a->grid_ct[g] < 0 || (long long)a->grid_rt[g] + a->grid_h[g] > a->n_index ||
+            (long long)a->grid_ct[g] + a->grid_w[g] > a->n_index)
+            return fail("%s: the index tables of latent grid %d leave the index buffer", who, g);
+        if (!a->latent[g] && !a->latent0[g]) return fail("%s: latent grid %d has no output", who, g);
+    }
+    return 0;
+}
+
+int spx_batch_prepare(const spx_batch* a, void* stream) {
+    static const char* who = "spx_batch_prepare";
+    if (int e = batch_check(who, a)) return e;
+    if (!a->samples) return fail("%s: NULL sample descriptors", who);
+    if (!a->image_out && !a->window_labels && a->G == 0) return fail("%s: no output requested", who);
+    if (a->image_out) {
+        if (a->out_u8 && !a->round_u8) return fail("%s: uint8 output needs round_u8", who);
+        for (int c = 0; c < 3; ++c) {
+            if (!(a->mean[c] == a->mean[c]) || !(a->std[c] == a->std[c])) return fail("%s: NaN in mean / std", who);
+            if (a->normalize && !a->out_u8 && a->std[c] == 0.0f) return fail("%s: std[%d] is zero", who, c);
+        }
+    }
+    return hip_status(spx_launch_batch_prepare(*a, (hipStream_t)stream), who);
+}
+
+int spx_resize_labels(const spx_batch* a, void* stream) {
+    static const char* who = "spx_resize_labels";
+    if (int e = batch_check(who, a)) return e;
+    if (!a->labels_in) return fail("%s: NULL labels", who);
+    if (a->G < 1) return fail("%s: no latent grid", who);
+    const int d = a->labels_dtype;
+    if (d != SPX_LABEL_U8 && d != SPX_LABEL_I16 && d != SPX_LABEL_I32 && d != SPX_LABEL_I64)
+        return fail("%s: label dtype code %d (1 = uint8, 2 = int16, 4 = int32, 8 = int64)", who, d);
+    return hip_status(spx_launch_resize_labels(*a, (hipStream_t)stream), who);
+}

@@ -299,3 +299,6 @@ hipError_t spx_launch_part_fold_consistency(const uint8_t* tab, const uint8_t* v
                                             long long* counters, hipStream_t s);
 hipError_t spx_launch_part_fold_stability(const uint8_t* clean, const uint8_t* noisy, const uint8_t* valid, const int32_t* table, int N, int C,
                                           int K, int J, int M, unsigned long long* counters, hipStream_t s);
+// training-batch preparation (spx_batch.hip)
+hipError_t spx_launch_batch_prepare(const spx_batch& a, hipStream_t s);
+hipError_t spx_launch_resize_labels(const spx_batch& a, hipStream_t s);
