@@ -890,6 +890,44 @@ typedef struct spx_batch {
 int spx_batch_prepare(const spx_batch* args, void* stream);
 int spx_resize_labels(const spx_batch* args, void* stream);
 
+/* ---- multi-scale input fusion: the pixel-wise maximum of MSC (segmentation/utils.py:71-111) in one launch --------------------
+ * K maps [B, C, h_k, w_k] (1 <= K <= 8), all bf16 (dtype code 0) or all fp32 (1); maps[0] fixes the output grid (H, W) = (h_0,
+ * w_0).  Element (b, c, i, j) of map k is at data + b * batch_stride + c * channel_stride + i * w_k + j (strides in elements: a
+ * channel slice is read in place; the h_k x w_k plane is contiguous).  out is contiguous [B, C, H, W] in out_dtype.
+ *   u_0 = maps[0];   u_k[Y][X], k >= 1: bilinear with align_corners = False, every operation in fp32 in this order
+ *     r = float(h_k) / float(H);  s = r * (Y + 0.5f) - 0.5f, raised to 0 when negative;  i0 = min(floor(s), h_k - 1);
+ *     i1 = min(i0 + 1, h_k - 1);  ly = s - i0;   the same along the columns with lx
+ *     u = (1 - ly) * ((1 - lx) * v00 + lx * v01) + ly * ((1 - lx) * v10 + lx * v11)        (no contraction into fma)
+ *   z = max_k u_k, the lowest k among equal values; a NaN candidate wins and keeps the first NaN's k (torch.max(dim=0));
+ *   activation 0: y = z;  1: y = 1 / (1 + expf(-z));   a bf16 y is the fp32 y rounded to nearest even.
+ * spx_msc_max_fwd writes out and, when index is not NULL, the winning k per element (uint8 [B, C, H, W]).
+ * spx_msc_max_bwd reads g = dL/dout (g_dtype, contiguous [B, C, H, W]), index (may be NULL when K = 1) and, under activation 1,
+ * out (the derivative is y (1 - y) of the SAVED y in out_dtype); of the maps it reads the sizes h, w only; it writes grads[k] (contiguous [B, C, h_k, w_k] in the maps'
+ * dtype) for every k whose pointer is not NULL: one thread per source element gathers g * wy * wx over the destination pixels
+ * whose footprint holds it and whose index is k, in ascending (Y, X) order.  No atomics, no workspace: run-to-run identical.
+ * Both are one launch on `stream` and read nothing on the host.  Limits: 1 <= B <= 65535, C >= 1, H * W < 2^31 and h_k * w_k <
+ * 2^31, B * C * H * W < 2^40, fewer than 2^39 gradient elements in one backward; out, g and the grads are aligned to their
+ * element size. */
+#define SPX_MSC_MAX_MAPS 8
+typedef struct spx_msc_map {
+    const void* data;
+    int64_t batch_stride, channel_stride;   /* elements */
+    int32_t h, w;
+} spx_msc_map;
+typedef struct spx_msc {
+    spx_msc_map maps[SPX_MSC_MAX_MAPS];
+    void* grads[SPX_MSC_MAX_MAPS];          /* backward only */
+    void* out;
+    uint8_t* index;
+    const void* g;                          /* backward only */
+    int32_t K, B, C;
+    int32_t in_dtype, out_dtype, g_dtype;   /* 0 = bf16, 1 = fp32 */
+    int32_t activation;                     /* 0 = none, 1 = sigmoid */
+    int32_t reserved;
+} spx_msc;
+int spx_msc_max_fwd(const spx_msc* args, void* stream);
+int spx_msc_max_bwd(const spx_msc* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,10 @@ Public surface mirrors the reference's module/function names for this path:
                                                     (segmentation/data/dataset.py:143-186 and the per-step resize_label of
                                                      module_multiscale.py:234-236: the augmented, normalised window batch, its
                                                      labels and the latent labels of every grid from raw uint8 images, one launch)
+    MSC, msc_max                                    (segmentation/utils.py:71-111: the backbone on the image and its shrunken
+                                                     copies, the pixel-wise maximum of the bilinearly resampled outputs, the
+                                                     add-on sigmoid and the bf16 cast in one launch;
+                                                     ppnet.fuse_feature_epilogue() makes conv_features use it)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -80,6 +84,7 @@ from .functional import (  # noqa: F401
     upsample_argext,
 )
 from .scale_head import OutConcat, OutMult, OutSum, WeightedAgg, factory_output_layer  # noqa: F401
+from .msc import MSC, msc_max  # noqa: F401
 from .checkpoint import export_state, import_state, load_reference_state_dict  # noqa: F401
 from .loss import (  # noqa: F401
     ActivationRegularizers,

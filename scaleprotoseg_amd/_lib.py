@@ -157,7 +157,43 @@ class SpxBatch(C.Structure):
     ]
 
 
+SPX_MSC_MAX_MAPS = 8
+
+
+class SpxMscMap(C.Structure):
+    """spx_msc_map of include/spx_hip.h: one map of spx_msc_max_fwd / spx_msc_max_bwd (strides in elements)."""
+
+    _fields_ = [
+        ("data", C.c_void_p),
+        ("batch_stride", C.c_int64),
+        ("channel_stride", C.c_int64),
+        ("h", C.c_int32),
+        ("w", C.c_int32),
+    ]
+
+
+class SpxMsc(C.Structure):
+    """spx_msc of include/spx_hip.h: the arguments of spx_msc_max_fwd / spx_msc_max_bwd."""
+
+    _fields_ = [
+        ("maps", SpxMscMap * SPX_MSC_MAX_MAPS),
+        ("grads", C.c_void_p * SPX_MSC_MAX_MAPS),
+        ("out", C.c_void_p),
+        ("index", C.c_void_p),
+        ("g", C.c_void_p),
+        ("K", C.c_int32),
+        ("B", C.c_int32),
+        ("C", C.c_int32),
+        ("in_dtype", C.c_int32),
+        ("out_dtype", C.c_int32),
+        ("g_dtype", C.c_int32),
+        ("activation", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 _PP = C.POINTER(SpxPlan)
+_PM = C.POINTER(SpxMsc)
 _PB = C.POINTER(SpxBatch)
 _PCE = C.POINTER(SpxCe)
 _PR = C.POINTER(SpxReg)
@@ -271,6 +307,8 @@ SIGNATURES = {
     "spx_part_fold_stability": (C.c_int, [_V, _V, _V, _V, _I, _I, _I, _I, _I, _V, _V]),
     "spx_batch_prepare": (C.c_int, [_PB, _V]),
     "spx_resize_labels": (C.c_int, [_PB, _V]),
+    "spx_msc_max_fwd": (C.c_int, [_PM, _V]),
+    "spx_msc_max_bwd": (C.c_int, [_PM, _V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libspx_hip.so")
 SOURCES = ["spx_api.hip", "spx_fwd_npb2.hip", "spx_fwd_npb4.hip", "spx_fwd_npb6.hip", "spx_bwd_npb2.hip", "spx_bwd_npb4.hip",
            "spx_bwd_npb6.hip", "spx_bank.hip", "spx_pack.hip", "spx_push.hip", "spx_prune.hip", "spx_eval.hip", "spx_kld.hip", "spx_ce.hip", "spx_gemm.hip",
            "spx_reg.hip", "spx_actloss.hip", "spx_overlap.hip", "spx_pushbox.hip", "spx_explain.hip", "spx_simplex.hip", "spx_masked_select.hip",
-           "spx_nearest.hip", "spx_scale_agg.hip", "spx_parts.hip", "spx_batch.hip"]
+           "spx_nearest.hip", "spx_scale_agg.hip", "spx_parts.hip", "spx_batch.hip", "spx_msc.hip"]
 HEADERS = ["spx_common.h", "spx_kld_walk.h", "spx_planes.h", "spx_overlap_sample.h", "spx_args.h", "spx_mainloop.h", "spx_fwd_impl.h", "spx_bwd_impl.h", os.path.join("..", "..", "include", "spx_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 FLAGS += os.environ.get("SPX_EXTRA_HIPCC_FLAGS", "").split()

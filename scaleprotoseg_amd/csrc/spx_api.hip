@@ -1433,3 +1433,48 @@ int spx_resize_labels(const spx_batch* a, void* stream) {
         return fail("%s: label dtype code %d (1 = uint8, 2 = int16, 4 = int32, 8 = int64)", who, d);
     return hip_status(spx_launch_resize_labels(*a, (hipStream_t)stream), who);
 }
+
+// what the two MSC entry points check alike: the maps, their common batch and channel counts, the dtype codes
+static int msc_check(const char* who, const spx_msc* a, bool forward) {
+    if (!a) return fail("%s: NULL arguments", who);
+    if (a->K < 1 || a->K > SPX_MSC_MAX_MAPS) return fail("%s: %d maps (1..%d)", who, a->K, SPX_MSC_MAX_MAPS);
+    if (a->B < 1 || a->B > 65535 || a->C < 1) return fail("%s: batch %d (1..65535), channels %d (>= 1)", who, a->B, a->C);
+    if ((a->in_dtype | 1) != 1 || (a->out_dtype | 1) != 1) return fail("%s: dtype codes %d / %d (0 = bf16, 1 = fp32)", who, a->in_dtype, a->out_dtype);
+    if ((a->activation | 1) != 1) return fail("%s: activation code %d (0 = none, 1 = sigmoid)", who, a->activation);
+    for (int k = 0; k < a->K; ++k) {
+        const spx_msc_map& m = a->maps[k];
+        if (forward && !m.data) return fail("%s: map %d is NULL", who, k);
+        if (m.h < 1 || m.w < 1 || (long long)m.h * m.w >= (1LL << 31)) return fail("%s: map %d is %d x %d (both >= 1, h * w < 2^31)", who, k, m.h, m.w);
+        if (forward && (m.batch_stride < 0 || m.channel_stride < 0)) return fail("%s: map %d has a negative stride", who, k);
+        if (forward && (uintptr_t)m.data % (a->in_dtype == 0 ? 2 : 4)) return fail("%s: map %d is not aligned to its element size", who, k);
+    }
+    if ((long long)a->B * a->C > ((1LL << 40) - 1) / ((long long)a->maps[0].h * a->maps[0].w)) return fail("%s: B * C * H * W >= 2^40", who);
+    if (!a->out && (forward || a->activation == 1)) return fail("%s: NULL output", who);
+    if (a->out && (uintptr_t)a->out % (a->out_dtype == 0 ? 2 : 4)) return fail("%s: the output is not aligned to its element size", who);
+    return 0;
+}
+
+int spx_msc_max_fwd(const spx_msc* a, void* stream) {
+    static const char* who = "spx_msc_max_fwd";
+    if (int e = msc_check(who, a, true)) return e;
+    return hip_status(spx_launch_msc_max_fwd(*a, (hipStream_t)stream), who);
+}
+
+int spx_msc_max_bwd(const spx_msc* a, void* stream) {
+    static const char* who = "spx_msc_max_bwd";
+    if (int e = msc_check(who, a, false)) return e;
+    if (!a->g) return fail("%s: NULL upstream gradient", who);
+    if ((a->g_dtype | 1) != 1) return fail("%s: g_dtype code %d (0 = bf16, 1 = fp32)", who, a->g_dtype);
+    if (a->K > 1 && !a->index) return fail("%s: NULL index with %d maps", who, a->K);
+    const size_t gsz = a->g_dtype == 0 ? 2 : 4, msz = a->in_dtype == 0 ? 2 : 4;
+    if ((uintptr_t)a->g % gsz) return fail("%s: the upstream gradient is not aligned to its element size", who);
+    long long total = 0;
+    for (int k = 0; k < a->K; ++k) {
+        if ((uintptr_t)a->grads[k] % msz) return fail("%s: gradient %d is not aligned to its element size", who, k);
+        if (!a->grads[k]) continue;
+        const long long planes = (long long)a->B * a->C, hw = (long long)a->maps[k].h * a->maps[k].w;
+        if (planes > ((1LL << 39) - 1 - total) / hw) return fail("%s: 2^39 or more gradient elements in one launch", who);
+        total += planes * hw;
+    }
+    return hip_status(spx_launch_msc_max_bwd(*a, (hipStream_t)stream), who);
+}

@@ -302,3 +302,6 @@ hipError_t spx_launch_part_fold_stability(const uint8_t* clean, const uint8_t* n
 // training-batch preparation (spx_batch.hip)
 hipError_t spx_launch_batch_prepare(const spx_batch& a, hipStream_t s);
 hipError_t spx_launch_resize_labels(const spx_batch& a, hipStream_t s);
+// multi-scale input fusion (spx_msc.hip)
+hipError_t spx_launch_msc_max_fwd(const spx_msc& a, hipStream_t s);
+hipError_t spx_launch_msc_max_bwd(const spx_msc& a, hipStream_t s);

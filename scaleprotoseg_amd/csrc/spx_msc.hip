@@ -1,0 +1,399 @@
+// Multi-scale input fusion: the pixel-wise maximum of the reference's MSC wrapper (segmentation/utils.py:71-111) over the
+// full-scale backbone output and the bilinearly resampled outputs of the scaled inputs, with the add-on sigmoid and the cast
+// of the deeplab_simple configurations in the same pass.  The rule is stated in include/spx_hip.h (spx_msc_max_fwd).
+//
+//   forward  (spx_msc_max_fwd_kernel)   a thread owns one group of 4 consecutive columns of one output row and walks a chunk of
+//       channels (grid: row groups x channel chunks x batch).  The per-row (i0, i1, ly) of every scaled map is formed once per
+//       thread, before the channel loop.  The groups of a row are anchored where the OUTPUT is 16-byte aligned (8 bytes for
+//       bf16): the row's first a = 0..3 elements belong to the row's thread 0, every later thread stores one aligned vector and
+//       the last one the remainder, element by element - so W, H * W and the output pointer need no alignment and the store of
+//       a wave is still one contiguous piece.  The full-scale map is read as a vector when its own address allows it; the scaled
+//       maps are at most a few taps per output and are read through the caches, element by element.
+//   K = 1    (spx_msc_act_kernel)       the activation and the cast alone: the same groups over a plane taken as one row, four
+//       channels per step with their loads issued together (the bandwidth-bound case).
+//   backward (spx_msc_max_bwd_kernel)   gather form, all maps in one launch: a thread owns one SOURCE element, finds its map by
+//       the descriptor's prefix sums, walks the destination rows and columns whose footprint can hold it (the inverse of s(Y),
+//       widened by one; every candidate is tested with the forward's own index function, so rounding can neither drop nor double
+//       a contribution) and adds g . wy . wx where the saved index names its map, in ascending (Y, X) order.
+// No LDS, no atomics, no workspace.
+#include "spx_args.h"
+#include "spx_common.h"
+
+#define MSC_THREADS 256
+#define MSC_VEC 4
+
+struct SpxMscArgs {
+    spx_msc d;
+    float rh[SPX_MSC_MAX_MAPS], rw[SPX_MSC_MAX_MAPS];   // float(h_k) / float(H), float(w_k) / float(W)
+    long long gofs[SPX_MSC_MAX_MAPS + 1];               // backward: prefix sums of the elements of the maps that get a gradient
+    int H, W, groups, cchunk;                           // forward: groups of a row (ceil(W / 4) + 1), channels per block
+    int out_mis;                                        // forward: (out address / element size) & 3
+};
+
+// source position of destination index D on an axis of n source elements (ratio r = float(n) / float(destination size))
+__device__ __forceinline__ void msc_src(float r, int n, int D, int& i0, int& i1, float& l) {
+    float s = r * ((float)D + 0.5f) - 0.5f;
+    s = s < 0.0f ? 0.0f : s;
+    const int f = (int)floorf(s);
+    i0 = f < n - 1 ? f : n - 1;
+    i1 = i0 + 1 < n - 1 ? i0 + 1 : n - 1;
+    l = s - (float)i0;
+}
+__device__ __forceinline__ float msc_load(const void* p, bool bf16, long long i) {
+    if (bf16) return __uint_as_float((uint32_t)((const uint16_t*)p)[i] << 16);
+    return ((const float*)p)[i];
+}
+__device__ __forceinline__ uint16_t msc_bf16_bits(float v) {
+    const __bf16 h = (__bf16)v;                          // round to nearest even
+    return *(const uint16_t*)&h;
+}
+
+// one thread's group [xs, xs + 4) of a row of the full-scale map (first element p0 + xs ... clipped to [xb, xe)): a vector
+// when the group is whole and its address allows it
+template <bool IN_BF16>
+__device__ __forceinline__ bool msc_group_vector_ok(const void* data, long long p0, bool full) {
+    return full && (((uintptr_t)data + (uintptr_t)p0 * (IN_BF16 ? 2 : 4)) & (IN_BF16 ? 7 : 15)) == 0;
+}
+template <bool IN_BF16>
+__device__ __forceinline__ void msc_load_vector(const void* data, long long p0, float (&v)[MSC_VEC]) {
+    if (IN_BF16) {
+        const uint2 r = *(const uint2*)((const uint16_t*)data + p0);
+        v[0] = __uint_as_float(r.x << 16);
+        v[1] = __uint_as_float(r.x & 0xffff0000u);
+        v[2] = __uint_as_float(r.y << 16);
+        v[3] = __uint_as_float(r.y & 0xffff0000u);
+    } else {
+        const float4 r = *(const float4*)((const float*)data + p0);
+        v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
+    }
+}
+template <bool IN_BF16>
+__device__ __forceinline__ void msc_load_group(const void* data, long long p0, int xs, int xb, int xe, float (&v)[MSC_VEC]) {
+    if (msc_group_vector_ok<IN_BF16>(data, p0, xe - xb == MSC_VEC)) {
+        msc_load_vector<IN_BF16>(data, p0, v);
+    } else {
+#pragma unroll
+        for (int j = 0; j < MSC_VEC; ++j) v[j] = (xs + j >= xb && xs + j < xe) ? msc_load(data, IN_BF16, p0 + j) : 0.0f;
+    }
+}
+// activation, cast and store of a group; o = the row's first element + xs, aligned by the anchoring when the group is whole
+template <bool OUT_BF16>
+__device__ __forceinline__ void msc_store_group(void* out, uint8_t* index, int activation, long long o, int xs, int xb, int xe,
+                                                float (&v)[MSC_VEC], const int (&win)[MSC_VEC]) {
+    const bool full = xe - xb == MSC_VEC;
+    if (activation == 1) {
+#pragma unroll
+        for (int j = 0; j < MSC_VEC; ++j) v[j] = 1.0f / (1.0f + expf(-v[j]));
+    }
+    if (OUT_BF16) {
+        uint16_t* const q = (uint16_t*)out + o;
+        if (full) {
+            uint2 r;
+            r.x = (uint32_t)msc_bf16_bits(v[0]) | ((uint32_t)msc_bf16_bits(v[1]) << 16);
+            r.y = (uint32_t)msc_bf16_bits(v[2]) | ((uint32_t)msc_bf16_bits(v[3]) << 16);
+            *(uint2*)q = r;
+        } else {
+#pragma unroll
+            for (int j = 0; j < MSC_VEC; ++j)
+                if (xs + j >= xb && xs + j < xe) q[j] = msc_bf16_bits(v[j]);
+        }
+    } else {
+        float* const q = (float*)out + o;
+        if (full) {
+            *(float4*)q = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < MSC_VEC; ++j)
+                if (xs + j >= xb && xs + j < xe) q[j] = v[j];
+        }
+    }
+    if (index) {
+        uint8_t* const q = index + o;
+        if (full && ((uintptr_t)q & 3) == 0) {
+            *(uint32_t*)q = (uint32_t)win[0] | ((uint32_t)win[1] << 8) | ((uint32_t)win[2] << 16) | ((uint32_t)win[3] << 24);
+        } else {
+#pragma unroll
+            for (int j = 0; j < MSC_VEC; ++j)
+                if (xs + j >= xb && xs + j < xe) q[j] = (uint8_t)win[j];
+        }
+    }
+}
+// the group of thread t in the output row whose first element is e0: [xs, xs + 4) clipped to [xb, xe) (empty: xb >= xe)
+__device__ __forceinline__ void msc_group(long long e0, int out_mis, int t, int W, int& xs, int& xb, int& xe) {
+    const int head = (int)((MSC_VEC - ((e0 + out_mis) & (MSC_VEC - 1))) & (MSC_VEC - 1));
+    xs = head - MSC_VEC + MSC_VEC * t;
+    xb = xs < 0 ? 0 : xs;
+    xe = xs + MSC_VEC < W ? xs + MSC_VEC : W;
+}
+
+template <bool IN_BF16, bool OUT_BF16>
+__global__ __launch_bounds__(MSC_THREADS) void spx_msc_max_fwd_kernel(const SpxMscArgs a) {
+    const int H = a.H, W = a.W, K = a.d.K, C = a.d.C;
+    const long long task = (long long)blockIdx.x * MSC_THREADS + threadIdx.x;
+    if (task >= (long long)H * a.groups) return;
+    const int Y = (int)(task / a.groups), t = (int)(task - (long long)Y * a.groups);
+    const int b = blockIdx.z;
+    const int c0 = blockIdx.y * a.cchunk;
+    const int c1 = c0 + a.cchunk < C ? c0 + a.cchunk : C;
+
+    // the rows of every scaled map under this output row, once per thread (constant indices after unrolling: registers)
+    int ri0[SPX_MSC_MAX_MAPS], ri1[SPX_MSC_MAX_MAPS];
+    float rl[SPX_MSC_MAX_MAPS];
+#pragma unroll
+    for (int k = 1; k < SPX_MSC_MAX_MAPS; ++k) {
+        ri0[k] = ri1[k] = 0;
+        rl[k] = 0.0f;
+        if (k < K) msc_src(a.rh[k], a.d.maps[k].h, Y, ri0[k], ri1[k], rl[k]);
+    }
+
+    const spx_msc_map m0 = a.d.maps[0];
+    for (int c = c0; c < c1; ++c) {
+        const long long e0 = (((long long)b * C + c) * H + Y) * W;               // the output row's first element
+        int xs, xb, xe;
+        msc_group(e0, a.out_mis, t, W, xs, xb, xe);
+        if (xb >= xe) continue;
+
+        float v[MSC_VEC];
+        int win[MSC_VEC];
+        msc_load_group<IN_BF16>(m0.data, (long long)b * m0.batch_stride + (long long)c * m0.channel_stride + (long long)Y * W + xs, xs, xb,
+                                xe, v);
+#pragma unroll
+        for (int j = 0; j < MSC_VEC; ++j) win[j] = 0;
+
+#pragma unroll
+        for (int k = 1; k < SPX_MSC_MAX_MAPS; ++k) {
+            if (k >= K) break;
+            const spx_msc_map m = a.d.maps[k];
+            const long long pl = (long long)b * m.batch_stride + (long long)c * m.channel_stride;
+            const long long r0 = pl + (long long)ri0[k] * m.w, r1 = pl + (long long)ri1[k] * m.w;
+            const float ly = rl[k];
+#pragma unroll
+            for (int j = 0; j < MSC_VEC; ++j) {
+                const int X = xs + j;
+                if (X < xb || X >= xe) continue;
+                int j0, j1;
+                float lx;
+                msc_src(a.rw[k], m.w, X, j0, j1, lx);
+                const float v00 = msc_load(m.data, IN_BF16, r0 + j0), v01 = msc_load(m.data, IN_BF16, r0 + j1);
+                const float v10 = msc_load(m.data, IN_BF16, r1 + j0), v11 = msc_load(m.data, IN_BF16, r1 + j1);
+                const float u = (1.0f - ly) * ((1.0f - lx) * v00 + lx * v01) + ly * ((1.0f - lx) * v10 + lx * v11);
+                // torch.max(dim=0): a larger value wins, the first of equals stays, the first NaN wins and stays
+                if (u > v[j] || (u != u && v[j] == v[j])) {
+                    v[j] = u;
+                    win[j] = k;
+                }
+            }
+        }
+        msc_store_group<OUT_BF16>(a.d.out, a.d.index, a.d.activation, e0 + xs, xs, xb, xe, v, win);
+    }
+}
+
+// K = 1: the activation and the cast alone.  There is no geometry, so a plane is taken as ONE row of H . W elements (the host
+// passes H = 1, W = H . W): two threads of a plane at most hold a partial group.  Bandwidth-bound: a thread takes four channels
+// per step and, where all four groups are whole vectors (all but the planes' ends), issues the four loads before the first use.
+#define MSC_ACT_UNROLL 4
+template <bool IN_BF16, bool OUT_BF16>
+__global__ __launch_bounds__(MSC_THREADS) void spx_msc_act_kernel(const SpxMscArgs a) {
+    const int W = a.W, C = a.d.C;
+    const int t = blockIdx.x * MSC_THREADS + threadIdx.x;
+    if (t >= a.groups) return;
+    const int b = blockIdx.z;
+    const int c0 = blockIdx.y * a.cchunk;
+    const int c1 = c0 + a.cchunk < C ? c0 + a.cchunk : C;
+    const spx_msc_map m0 = a.d.maps[0];
+    const int win[MSC_VEC] = {0, 0, 0, 0};
+
+    for (int c = c0; c < c1; c += MSC_ACT_UNROLL) {
+        long long e0[MSC_ACT_UNROLL], p0[MSC_ACT_UNROLL];
+        int xs[MSC_ACT_UNROLL], xb[MSC_ACT_UNROLL], xe[MSC_ACT_UNROLL];
+        bool fast = c + MSC_ACT_UNROLL <= c1;
+#pragma unroll
+        for (int u = 0; u < MSC_ACT_UNROLL; ++u) {
+            const int cu = c + u < c1 ? c + u : c1 - 1;
+            e0[u] = ((long long)b * C + cu) * W;
+            msc_group(e0[u], a.out_mis, t, W, xs[u], xb[u], xe[u]);
+            p0[u] = (long long)b * m0.batch_stride + (long long)cu * m0.channel_stride + xs[u];
+            fast = fast && msc_group_vector_ok<IN_BF16>(m0.data, p0[u], xe[u] - xb[u] == MSC_VEC);
+        }
+        if (fast) {
+            float v[MSC_ACT_UNROLL][MSC_VEC];
+#pragma unroll
+            for (int u = 0; u < MSC_ACT_UNROLL; ++u) msc_load_vector<IN_BF16>(m0.data, p0[u], v[u]);
+            if (a.d.activation == 1) {
+#pragma unroll
+                for (int u = 0; u < MSC_ACT_UNROLL; ++u)
+#pragma unroll
+                    for (int j = 0; j < MSC_VEC; ++j) v[u][j] = 1.0f / (1.0f + expf(-v[u][j]));
+            }
+#pragma unroll
+            for (int u = 0; u < MSC_ACT_UNROLL; ++u) {                            // whole groups: aligned by the anchoring
+                if (OUT_BF16) {
+                    uint2 r;
+                    r.x = (uint32_t)msc_bf16_bits(v[u][0]) | ((uint32_t)msc_bf16_bits(v[u][1]) << 16);
+                    r.y = (uint32_t)msc_bf16_bits(v[u][2]) | ((uint32_t)msc_bf16_bits(v[u][3]) << 16);
+                    *(uint2*)((uint16_t*)a.d.out + e0[u] + xs[u]) = r;
+                } else {
+                    *(float4*)((float*)a.d.out + e0[u] + xs[u]) = make_float4(v[u][0], v[u][1], v[u][2], v[u][3]);
+                }
+            }
+            if (a.d.index) {
+#pragma unroll
+                for (int u = 0; u < MSC_ACT_UNROLL; ++u)
+#pragma unroll
+                    for (int j = 0; j < MSC_VEC; ++j) a.d.index[e0[u] + xs[u] + j] = 0;
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < MSC_ACT_UNROLL; ++u) {
+                if (c + u >= c1 || xb[u] >= xe[u]) continue;
+                float v[MSC_VEC];
+                msc_load_group<IN_BF16>(m0.data, p0[u], xs[u], xb[u], xe[u], v);
+                msc_store_group<OUT_BF16>(a.d.out, a.d.index, a.d.activation, e0[u] + xs[u], xs[u], xb[u], xe[u], v, win);
+            }
+        }
+    }
+}
+
+// first and last destination index whose footprint can hold source index i (n source elements, D destination elements)
+__device__ __forceinline__ void msc_dst_range(float r, int n, int D, int i, int& lo, int& hi) {
+    // s(Y) = r (Y + 0.5) - 0.5 lies in (i - 1, i + 1)  <=>  Y in ((i - 0.5) / r - 0.5, (i + 1.5) / r - 0.5); widened by one.
+    // Rows clamped at the borders belong to the border indices: s raised to 0 names i0 = 0 and i1 = 1 (with weight 0 on the
+    // latter), i1 held at n - 1 names the last index.
+    const float a = ((float)i - 0.5f) / r - 0.5f, b = ((float)i + 1.5f) / r - 0.5f;
+    lo = (int)floorf(a) - 1;
+    hi = (int)ceilf(b) + 1;
+    if (i <= 1 || lo < 0) lo = 0;
+    if (i == n - 1 || hi > D - 1) hi = D - 1;
+}
+
+__global__ __launch_bounds__(MSC_THREADS) void spx_msc_max_bwd_kernel(const SpxMscArgs a) {
+    const long long id = (long long)blockIdx.x * MSC_THREADS + threadIdx.x;
+    const int H = a.H, W = a.W, K = a.d.K, C = a.d.C;
+    if (id >= a.gofs[SPX_MSC_MAX_MAPS]) return;
+    // which map: the one whose range of the prefix sums holds id (a map without a gradient has an empty range)
+    int k = 0, h = 1, w = 1;
+    float rh = 1.0f, rw = 1.0f;
+    long long local = 0;
+    void* grad = nullptr;
+#pragma unroll
+    for (int q = 0; q < SPX_MSC_MAX_MAPS; ++q) {
+        if (q < K && id >= a.gofs[q] && id < a.gofs[q + 1]) {
+            k = q;
+            h = a.d.maps[q].h;
+            w = a.d.maps[q].w;
+            rh = a.rh[q];
+            rw = a.rw[q];
+            local = id - a.gofs[q];
+            grad = a.d.grads[q];
+        }
+    }
+    const int j = (int)(local % w);
+    const int i = (int)((local / w) % h);
+    const long long plane = local / ((long long)w * h);                           // b * C + c
+    const bool g16 = a.d.g_dtype == 0, y16 = a.d.out_dtype == 0, sig = a.d.activation == 1;
+    const long long base = plane * H * W;
+
+    float acc = 0.0f;
+    if (k == 0) {
+        const long long o = base + (long long)i * W + j;
+        if (!a.d.index || a.d.index[o] == 0) {
+            float g = msc_load(a.d.g, g16, o);
+            if (sig) {
+                const float y = msc_load(a.d.out, y16, o);
+                g = g * (y * (1.0f - y));
+            }
+            acc = g;
+        }
+    } else {
+        int ylo, yhi, xlo, xhi;
+        msc_dst_range(rh, h, H, i, ylo, yhi);
+        msc_dst_range(rw, w, W, j, xlo, xhi);
+        for (int Y = ylo; Y <= yhi; ++Y) {
+            int i0, i1;
+            float ly;
+            msc_src(rh, h, Y, i0, i1, ly);
+            const float wy = (i0 == i ? 1.0f - ly : 0.0f) + (i1 == i ? ly : 0.0f);
+            if (i0 != i && i1 != i) continue;
+            for (int X = xlo; X <= xhi; ++X) {
+                int j0, j1;
+                float lx;
+                msc_src(rw, w, X, j0, j1, lx);
+                if (j0 != j && j1 != j) continue;
+                const long long o = base + (long long)Y * W + X;
+                if (a.d.index[o] != k) continue;
+                const float wx = (j0 == j ? 1.0f - lx : 0.0f) + (j1 == j ? lx : 0.0f);
+                float g = msc_load(a.d.g, g16, o);
+                if (sig) {
+                    const float y = msc_load(a.d.out, y16, o);
+                    g = g * (y * (1.0f - y));
+                }
+                acc += g * wy * wx;
+            }
+        }
+    }
+    if (a.d.in_dtype == 0) ((uint16_t*)grad)[local] = msc_bf16_bits(acc);
+    else ((float*)grad)[local] = acc;
+}
+
+static void msc_fill(SpxMscArgs& a, const spx_msc& d) {
+    a.d = d;
+    a.H = d.maps[0].h;
+    a.W = d.maps[0].w;
+    for (int k = 0; k < SPX_MSC_MAX_MAPS; ++k) {
+        a.rh[k] = a.rw[k] = 1.0f;
+        if (k < d.K) {
+            a.rh[k] = (float)d.maps[k].h / (float)a.H;
+            a.rw[k] = (float)d.maps[k].w / (float)a.W;
+        }
+    }
+}
+
+#define MSC_LAUNCH_FWD(kernel)                                                                                   \
+    do {                                                                                                         \
+        if (d.in_dtype == 0) {                                                                                   \
+            if (d.out_dtype == 0) hipLaunchKernelGGL((kernel<true, true>), grid, dim3(MSC_THREADS), 0, s, a);    \
+            else hipLaunchKernelGGL((kernel<true, false>), grid, dim3(MSC_THREADS), 0, s, a);                    \
+        } else {                                                                                                 \
+            if (d.out_dtype == 0) hipLaunchKernelGGL((kernel<false, true>), grid, dim3(MSC_THREADS), 0, s, a);   \
+            else hipLaunchKernelGGL((kernel<false, false>), grid, dim3(MSC_THREADS), 0, s, a);                   \
+        }                                                                                                        \
+    } while (0)
+
+hipError_t spx_launch_msc_max_fwd(const spx_msc& d, hipStream_t s) {
+    SpxMscArgs a = {};
+    msc_fill(a, d);
+    if (d.K == 1) {                 // no geometry: a plane is one row (spx_msc_act_kernel)
+        a.W = a.H * a.W;
+        a.H = 1;
+    }
+    a.groups = (a.W + MSC_VEC - 1) / MSC_VEC + 1;
+    const size_t esz = d.out_dtype == 0 ? 2 : 4;
+    a.out_mis = (int)(((uintptr_t)d.out / esz) & (MSC_VEC - 1));
+    const long long tasks = (long long)a.H * a.groups;
+    const unsigned bx = (unsigned)((tasks + MSC_THREADS - 1) / MSC_THREADS);
+    // enough blocks to fill the chip (about 8 per CU), then as many channels per block as that leaves: the per-row setup is
+    // paid once per block and thread
+    long long chunks = 2048 / ((long long)bx * d.B);
+    if (chunks < 1) chunks = 1;
+    if (chunks > d.C) chunks = d.C;
+    a.cchunk = (int)((d.C + chunks - 1) / chunks);
+    if (d.K == 1) a.cchunk = (a.cchunk + MSC_ACT_UNROLL - 1) / MSC_ACT_UNROLL * MSC_ACT_UNROLL;
+    const dim3 grid(bx, (unsigned)((d.C + a.cchunk - 1) / a.cchunk), (unsigned)d.B);
+    if (d.K == 1) MSC_LAUNCH_FWD(spx_msc_act_kernel);
+    else MSC_LAUNCH_FWD(spx_msc_max_fwd_kernel);
+    return hipGetLastError();
+}
+
+hipError_t spx_launch_msc_max_bwd(const spx_msc& d, hipStream_t s) {
+    SpxMscArgs a = {};
+    msc_fill(a, d);
+    a.gofs[0] = 0;
+    for (int k = 0; k < SPX_MSC_MAX_MAPS; ++k) {
+        const long long n = (k < d.K && d.grads[k]) ? (long long)d.B * d.C * d.maps[k].h * d.maps[k].w : 0;
+        a.gofs[k + 1] = a.gofs[k] + n;
+    }
+    const long long total = a.gofs[SPX_MSC_MAX_MAPS];
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(spx_msc_max_bwd_kernel, dim3((unsigned)((total + MSC_THREADS - 1) / MSC_THREADS)), dim3(MSC_THREADS), 0, s, a);
+    return hipGetLastError();
+}

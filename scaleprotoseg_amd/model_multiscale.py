@@ -20,6 +20,7 @@ from .functional import (MAX_FUSED_HEAD_ROWS, BankLayout, ClassGather, SpxError,
                          cross_entropy_from_logits, identity_is_one_hot, invalidate_pack_cache, proto_head_forward,
                          push_min_from_features, shifted_labels_i32, wide_linear)
 from .loss import ClassDistances
+from .msc import MSC
 from .scale_head import WeightedAgg
 
 
@@ -208,8 +209,27 @@ class _PrototypeBankMixin:
         return keep
 
     # -- reference methods on the distance path ---------------------------------------------------
+    _feature_epilogue = None
+
+    def fuse_feature_epilogue(self, dtype: Optional[torch.dtype] = torch.bfloat16):
+        """Opt in (``None``: undo): ``conv_features`` calls ``features.fused(x, "sigmoid", dtype)`` - the MSC maximum, the add-on
+        sigmoid and the cast in one launch (csrc/spx_msc.hip) - instead of ``add_on_layers(features(x))``, so that everything
+        downstream receives ``dtype`` features without an fp32 round trip.  Accepted only when ``features`` is a
+        ``scaleprotoseg_amd.MSC`` and ``add_on_layers`` is exactly ``nn.Sequential(nn.Sigmoid())`` (deeplab_simple)."""
+        if dtype is not None:
+            add_on = self.add_on_layers
+            if not isinstance(self.features, MSC):
+                raise SpxError(f"fuse_feature_epilogue: features is {type(self.features).__name__}, not scaleprotoseg_amd.MSC")
+            if type(add_on) is not nn.Sequential or len(add_on) != 1 or type(add_on[0]) is not nn.Sigmoid:
+                raise SpxError("fuse_feature_epilogue: add_on_layers must be exactly nn.Sequential(nn.Sigmoid()) (deeplab_simple)")
+            if dtype not in (torch.bfloat16, torch.float32):
+                raise SpxError(f"fuse_feature_epilogue: dtype {dtype}; bfloat16 or float32")
+        object.__setattr__(self, "_feature_epilogue", dtype)
+
     def conv_features(self, x):
         """features -> add_on_layers, list-aware for MSC training inputs (model_multiscale.py:246-253)."""
+        if self._feature_epilogue is not None:
+            return self.features.fused(x, "sigmoid", self._feature_epilogue)
         x = self.features(x)
         if isinstance(x, list):
             return [self.add_on_layers(xs) for xs in x]
