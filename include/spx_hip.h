@@ -928,6 +928,27 @@ typedef struct spx_msc {
 int spx_msc_max_fwd(const spx_msc* args, void* stream);
 int spx_msc_max_bwd(const spx_msc* args, void* stream);
 
+/* ---- the packed training maps: MSC's training list [full] + pyramid + [max] on ONE pixel axis, one launch ---------------------
+ * The same K maps (spx_msc, same stride rules, same dtype codes).  out is ONE contiguous buffer [C, M] in out_dtype with
+ * nseg = K + (with_max ? 1 : 0) segments side by side and no padding: pixel (b, i) of segment q (i = row * w_q + column) is
+ * column off_q + b * h_q * w_q + i of every channel row, off_q = sum_{j < q} B * h_j * w_j, M = off_nseg.
+ *   segment q < K   act(maps[q]) at the map's own grid (h_q, w_q);
+ *   segment K       (with_max != 0) act(max_k u_k) at (H, W) = (h_0, w_0): the candidates u_k, the tie and NaN rules, the
+ *                   activation and the bf16 rounding are spx_msc_max_fwd's, above, operation for operation; index (uint8
+ *                   [B, C, H, W], the usual layout, not packed) receives the winning k when it is not NULL.
+ * Taken as features [1, C, 1, M] the buffer is what the distance entry points read (B = 1, HW = M): their workgroup tiles
+ * straddle segment and image boundaries, which changes nothing, as every quantity of theirs is per pixel.  With with_max = 0
+ * any K maps of a common B and C form a ragged batch.  Stores are 8- / 16-byte vectors when M is a multiple of 4 and out is
+ * aligned to them, element stores otherwise (any M, any element-aligned out).
+ * spx_msc_pack_bwd reads g = dL/dout (g_dtype, contiguous [C, M]), index (with_max; may be NULL when K = 1) and, under activation
+ * 1, out; it writes grads[k] (contiguous [B, C, h_k, w_k] in the maps' dtype) for every k whose pointer is not NULL, one thread
+ * per source element: first the element's own segment, g * y (1 - y) (or g), then the gather over segment K in
+ * spx_msc_max_bwd's ascending (Y, X) order, all added in fp32 in that order and rounded once.  No atomics, no workspace:
+ * run-to-run identical.  Both are one launch on `stream`; offsets and sizes travel in the kernel arguments, nothing is read
+ * on the host.  Limits: those of spx_msc_max_fwd / _bwd per map, and M < 2^31, C * M < 2^40. */
+int spx_msc_pack_fwd(const spx_msc* args, int with_max, void* stream);
+int spx_msc_pack_bwd(const spx_msc* args, int with_max, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

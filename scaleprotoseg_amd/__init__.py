@@ -63,6 +63,10 @@ Public surface mirrors the reference's module/function names for this path:
                                                      copies, the pixel-wise maximum of the bilinearly resampled outputs, the
                                                      add-on sigmoid and the bf16 cast in one launch;
                                                      ppnet.fuse_feature_epilogue() makes conv_features use it)
+    msc_pack, PackedMaps, PackedLayout              (module_multiscale.py:216-277 runs the model on MSC's four training maps:
+                                                     here they are written on one pixel axis in one launch, and one distance
+                                                     forward / backward serves all four;
+                                                     ppnet.fuse_feature_epilogue(dtype, packed=True))
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -84,7 +88,7 @@ from .functional import (  # noqa: F401
     upsample_argext,
 )
 from .scale_head import OutConcat, OutMult, OutSum, WeightedAgg, factory_output_layer  # noqa: F401
-from .msc import MSC, msc_max  # noqa: F401
+from .msc import MSC, PackedLayout, PackedMaps, msc_max, msc_pack  # noqa: F401
 from .checkpoint import export_state, import_state, load_reference_state_dict  # noqa: F401
 from .loss import (  # noqa: F401
     ActivationRegularizers,

@@ -309,6 +309,8 @@ SIGNATURES = {
     "spx_resize_labels": (C.c_int, [_PB, _V]),
     "spx_msc_max_fwd": (C.c_int, [_PM, _V]),
     "spx_msc_max_bwd": (C.c_int, [_PM, _V]),
+    "spx_msc_pack_fwd": (C.c_int, [_PM, _I, _V]),
+    "spx_msc_pack_bwd": (C.c_int, [_PM, _I, _V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1460,12 +1460,11 @@ int spx_msc_max_fwd(const spx_msc* a, void* stream) {
     return hip_status(spx_launch_msc_max_fwd(*a, (hipStream_t)stream), who);
 }
 
-int spx_msc_max_bwd(const spx_msc* a, void* stream) {
-    static const char* who = "spx_msc_max_bwd";
-    if (int e = msc_check(who, a, false)) return e;
+// what the two MSC backward entry points check alike: the upstream gradient, the index, the gradient buffers
+static int msc_bwd_check(const char* who, const spx_msc* a, bool need_index) {
     if (!a->g) return fail("%s: NULL upstream gradient", who);
     if ((a->g_dtype | 1) != 1) return fail("%s: g_dtype code %d (0 = bf16, 1 = fp32)", who, a->g_dtype);
-    if (a->K > 1 && !a->index) return fail("%s: NULL index with %d maps", who, a->K);
+    if (need_index && !a->index) return fail("%s: NULL index with %d maps", who, a->K);
     const size_t gsz = a->g_dtype == 0 ? 2 : 4, msz = a->in_dtype == 0 ? 2 : 4;
     if ((uintptr_t)a->g % gsz) return fail("%s: the upstream gradient is not aligned to its element size", who);
     long long total = 0;
@@ -1476,5 +1475,39 @@ int spx_msc_max_bwd(const spx_msc* a, void* stream) {
         if (planes > ((1LL << 39) - 1 - total) / hw) return fail("%s: 2^39 or more gradient elements in one launch", who);
         total += planes * hw;
     }
+    return 0;
+}
+
+int spx_msc_max_bwd(const spx_msc* a, void* stream) {
+    static const char* who = "spx_msc_max_bwd";
+    if (int e = msc_check(who, a, false)) return e;
+    if (int e = msc_bwd_check(who, a, a->K > 1)) return e;
     return hip_status(spx_launch_msc_max_bwd(*a, (hipStream_t)stream), who);
+}
+
+// the packed axis: M = sum over the segments of B * h * w below 2^31, C * M below 2^40
+static int msc_pack_check(const char* who, const spx_msc* a, int with_max) {
+    long long M = 0;
+    for (int k = 0; k < a->K + (with_max ? 1 : 0); ++k) {
+        const spx_msc_map& m = a->maps[k < a->K ? k : 0];
+        M += (long long)a->B * m.h * m.w;                  // (each term below 2^47: msc_check)
+    }
+    if (M >= (1LL << 31)) return fail("%s: %lld packed pixels (M < 2^31)", who, M);
+    if ((long long)a->C > ((1LL << 40) - 1) / M) return fail("%s: C * M >= 2^40", who);
+    return 0;
+}
+
+int spx_msc_pack_fwd(const spx_msc* a, int with_max, void* stream) {
+    static const char* who = "spx_msc_pack_fwd";
+    if (int e = msc_check(who, a, true)) return e;
+    if (int e = msc_pack_check(who, a, with_max)) return e;
+    return hip_status(spx_launch_msc_pack_fwd(*a, with_max, (hipStream_t)stream), who);
+}
+
+int spx_msc_pack_bwd(const spx_msc* a, int with_max, void* stream) {
+    static const char* who = "spx_msc_pack_bwd";
+    if (int e = msc_check(who, a, false)) return e;
+    if (int e = msc_pack_check(who, a, with_max)) return e;
+    if (int e = msc_bwd_check(who, a, with_max && a->K > 1)) return e;
+    return hip_status(spx_launch_msc_pack_bwd(*a, with_max, (hipStream_t)stream), who);
 }

@@ -305,3 +305,5 @@ hipError_t spx_launch_resize_labels(const spx_batch& a, hipStream_t s);
 // multi-scale input fusion (spx_msc.hip)
 hipError_t spx_launch_msc_max_fwd(const spx_msc& a, hipStream_t s);
 hipError_t spx_launch_msc_max_bwd(const spx_msc& a, hipStream_t s);
+hipError_t spx_launch_msc_pack_fwd(const spx_msc& a, int with_max, hipStream_t s);
+hipError_t spx_launch_msc_pack_bwd(const spx_msc& a, int with_max, hipStream_t s);

@@ -266,6 +266,40 @@ __device__ __forceinline__ void msc_dst_range(float r, int n, int D, int i, int&
     if (i == n - 1 || hi > D - 1) hi = D - 1;
 }
 
+// The gather of source element (i, j) of map k >= 1 (h x w, ratios rh, rw) over the H x W destination pixels whose footprint can
+// hold it and whose index names k, added to acc in ascending (Y, X) order.  Pixel (Y, X) is element gbase + Y W + X of the
+// upstream gradient and of the saved output, and element ibase + Y W + X of the index.
+__device__ __forceinline__ float msc_gather(const spx_msc& d, int k, int h, int w, float rh, float rw, int H, int W, int i, int j,
+                                            long long gbase, long long ibase, float acc) {
+    const bool g16 = d.g_dtype == 0, y16 = d.out_dtype == 0, sig = d.activation == 1;
+    int ylo, yhi, xlo, xhi;
+    msc_dst_range(rh, h, H, i, ylo, yhi);
+    msc_dst_range(rw, w, W, j, xlo, xhi);
+    for (int Y = ylo; Y <= yhi; ++Y) {
+        int i0, i1;
+        float ly;
+        msc_src(rh, h, Y, i0, i1, ly);
+        const float wy = (i0 == i ? 1.0f - ly : 0.0f) + (i1 == i ? ly : 0.0f);
+        if (i0 != i && i1 != i) continue;
+        for (int X = xlo; X <= xhi; ++X) {
+            int j0, j1;
+            float lx;
+            msc_src(rw, w, X, j0, j1, lx);
+            if (j0 != j && j1 != j) continue;
+            const long long p = (long long)Y * W + X;
+            if (d.index[ibase + p] != k) continue;
+            const float wx = (j0 == j ? 1.0f - lx : 0.0f) + (j1 == j ? lx : 0.0f);
+            float g = msc_load(d.g, g16, gbase + p);
+            if (sig) {
+                const float y = msc_load(d.out, y16, gbase + p);
+                g = g * (y * (1.0f - y));
+            }
+            acc += g * wy * wx;
+        }
+    }
+    return acc;
+}
+
 __global__ __launch_bounds__(MSC_THREADS) void spx_msc_max_bwd_kernel(const SpxMscArgs a) {
     const long long id = (long long)blockIdx.x * MSC_THREADS + threadIdx.x;
     const int H = a.H, W = a.W, K = a.d.K, C = a.d.C;
@@ -305,31 +339,7 @@ __global__ __launch_bounds__(MSC_THREADS) void spx_msc_max_bwd_kernel(const SpxM
             acc = g;
         }
     } else {
-        int ylo, yhi, xlo, xhi;
-        msc_dst_range(rh, h, H, i, ylo, yhi);
-        msc_dst_range(rw, w, W, j, xlo, xhi);
-        for (int Y = ylo; Y <= yhi; ++Y) {
-            int i0, i1;
-            float ly;
-            msc_src(rh, h, Y, i0, i1, ly);
-            const float wy = (i0 == i ? 1.0f - ly : 0.0f) + (i1 == i ? ly : 0.0f);
-            if (i0 != i && i1 != i) continue;
-            for (int X = xlo; X <= xhi; ++X) {
-                int j0, j1;
-                float lx;
-                msc_src(rw, w, X, j0, j1, lx);
-                if (j0 != j && j1 != j) continue;
-                const long long o = base + (long long)Y * W + X;
-                if (a.d.index[o] != k) continue;
-                const float wx = (j0 == j ? 1.0f - lx : 0.0f) + (j1 == j ? lx : 0.0f);
-                float g = msc_load(a.d.g, g16, o);
-                if (sig) {
-                    const float y = msc_load(a.d.out, y16, o);
-                    g = g * (y * (1.0f - y));
-                }
-                acc += g * wy * wx;
-            }
-        }
+        acc = msc_gather(a.d, k, h, w, rh, rw, H, W, i, j, base, base, acc);
     }
     if (a.d.in_dtype == 0) ((uint16_t*)grad)[local] = msc_bf16_bits(acc);
     else ((float*)grad)[local] = acc;
@@ -395,5 +405,295 @@ hipError_t spx_launch_msc_max_bwd(const spx_msc& d, hipStream_t s) {
     const long long total = a.gofs[SPX_MSC_MAX_MAPS];
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(spx_msc_max_bwd_kernel, dim3((unsigned)((total + MSC_THREADS - 1) / MSC_THREADS)), dim3(MSC_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- the packed training maps (spx_msc_pack_fwd / _bwd) ------------------------------------------------------------------------
+// The K maps at their own grids and, with_max, their maximum written side by side on ONE pixel axis: out [C, M], pixel (b, i) of
+// segment q at column off_q + b . h_q . w_q + i (include/spx_hip.h).  Values, index and rounding are those of the kernels above.
+//
+//   forward   a thread owns the columns [4 t, 4 t + 4) of a chunk of channels (grid: column groups x channel chunks).  Its four
+//       columns are decoded once, before the channel loop: segment, image, pixel.  A group that lies inside one plane of a plain
+//       segment, at addresses a vector may take, runs four channels per step with their loads issued together (the K = 1 lesson:
+//       the bandwidth-bound case); every other group - the maximum's, those that straddle a segment or an image, those of a
+//       buffer whose rows a vector cannot address (M no multiple of 4, a misaligned out) - goes column by column.
+//   backward  gather form as above, one thread per source element: first its own segment's term, then the maximum's segment.
+struct SpxMscPackArgs {
+    spx_msc d;
+    float rh[SPX_MSC_MAX_MAPS], rw[SPX_MSC_MAX_MAPS];
+    long long gofs[SPX_MSC_MAX_MAPS + 1];               // backward: prefix sums of the elements of the maps that get a gradient
+    int off[SPX_MSC_MAX_MAPS + 2];                      // first column of every segment; off[nseg] = M
+    int nseg, with_max, off_max, M, H, W, cchunk;
+    int vec_ok;                                         // forward: M % 4 == 0 and out aligned to a vector
+};
+
+struct MscCol {
+    const void* data;                                   // plain segment: its map
+    long long base;                                     // plain: b . batch_stride + i;  maximum: b
+    long long cs;                                       // plain: channel stride
+    int seg, b, i;                                      // segment, image, pixel of the plane
+};
+
+__device__ __forceinline__ MscCol msc_pack_col(const SpxMscPackArgs& a, int m) {
+    MscCol r;
+    r.data = nullptr;
+    r.base = r.cs = 0;
+    r.seg = r.b = r.i = 0;
+#pragma unroll
+    for (int q = 0; q < SPX_MSC_MAX_MAPS + 1; ++q) {
+        if (q < a.nseg && m >= a.off[q] && m < a.off[q + 1]) {
+            const bool plain = q < a.d.K;
+            const spx_msc_map mp = a.d.maps[q < SPX_MSC_MAX_MAPS ? q : 0];
+            const int hw = plain ? mp.h * mp.w : a.H * a.W;
+            const int local = m - a.off[q];
+            r.seg = q;
+            r.b = local / hw;
+            r.i = local - r.b * hw;
+            r.data = plain ? mp.data : nullptr;
+            r.cs = plain ? mp.channel_stride : 0;
+            r.base = plain ? (long long)r.b * mp.batch_stride + r.i : (long long)r.b;
+        }
+    }
+    return r;
+}
+
+// the value of one column of channel c before the activation; win: the winning map (the maximum's segment only)
+template <bool IN_BF16>
+__device__ __forceinline__ float msc_pack_value(const SpxMscPackArgs& a, const MscCol& col, int c, int& win) {
+    win = 0;
+    if (col.seg < a.d.K) return msc_load(col.data, IN_BF16, col.base + (long long)c * col.cs);
+    const int W = a.W, K = a.d.K;
+    const int Y = col.i / W, X = col.i - Y * W;
+    const spx_msc_map m0 = a.d.maps[0];
+    float v = msc_load(m0.data, IN_BF16, (long long)col.b * m0.batch_stride + (long long)c * m0.channel_stride + col.i);
+    // (a rolled loop on purpose: unrolled, the source positions of 4 columns x 7 maps are hoisted out of the channel loop and
+    // take every register the file has; k is uniform, so maps[k] is a scalar load)
+#pragma unroll 1
+    for (int k = 1; k < K; ++k) {
+        const spx_msc_map m = a.d.maps[k];
+        int i0, i1, j0, j1;
+        float ly, lx;
+        msc_src(a.rh[k], m.h, Y, i0, i1, ly);
+        msc_src(a.rw[k], m.w, X, j0, j1, lx);
+        const long long pl = (long long)col.b * m.batch_stride + (long long)c * m.channel_stride;
+        const long long r0 = pl + (long long)i0 * m.w, r1 = pl + (long long)i1 * m.w;
+        const float v00 = msc_load(m.data, IN_BF16, r0 + j0), v01 = msc_load(m.data, IN_BF16, r0 + j1);
+        const float v10 = msc_load(m.data, IN_BF16, r1 + j0), v11 = msc_load(m.data, IN_BF16, r1 + j1);
+        const float u = (1.0f - ly) * ((1.0f - lx) * v00 + lx * v01) + ly * ((1.0f - lx) * v10 + lx * v11);
+        if (u > v || (u != u && v == v)) {                 // torch.max(dim=0), as in spx_msc_max_fwd_kernel
+            v = u;
+            win = k;
+        }
+    }
+    return v;
+}
+
+template <bool OUT_BF16>
+__device__ __forceinline__ void msc_pack_store_vector(void* out, long long o, const float (&v)[MSC_VEC]) {
+    if (OUT_BF16) {
+        uint2 r;
+        r.x = (uint32_t)msc_bf16_bits(v[0]) | ((uint32_t)msc_bf16_bits(v[1]) << 16);
+        r.y = (uint32_t)msc_bf16_bits(v[2]) | ((uint32_t)msc_bf16_bits(v[3]) << 16);
+        *(uint2*)((uint16_t*)out + o) = r;
+    } else {
+        *(float4*)((float*)out + o) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+template <bool IN_BF16, bool OUT_BF16>
+__global__ __launch_bounds__(MSC_THREADS) void spx_msc_pack_fwd_kernel(const SpxMscPackArgs a) {
+    const int M = a.M, C = a.d.C;
+    const long long first = ((long long)blockIdx.x * MSC_THREADS + threadIdx.x) * MSC_VEC;
+    if (first >= M) return;
+    const int xs = (int)first;
+    const int n = M - xs < MSC_VEC ? M - xs : MSC_VEC;                              // columns [xs, xs + n)
+    const int c0 = blockIdx.y * a.cchunk;
+    const int c1 = c0 + a.cchunk < C ? c0 + a.cchunk : C;
+    const bool sig = a.d.activation == 1;
+
+    MscCol col[MSC_VEC];
+    col[0] = msc_pack_col(a, xs);
+    col[MSC_VEC - 1] = msc_pack_col(a, xs + n - 1);
+    const bool one_plane = n == MSC_VEC && col[0].seg == col[MSC_VEC - 1].seg && col[0].b == col[MSC_VEC - 1].b;
+    if (one_plane) {
+#pragma unroll
+        for (int j = 1; j < MSC_VEC - 1; ++j) {
+            col[j] = col[0];
+            col[j].i += j;
+            if (col[0].seg < a.d.K) col[j].base += j;
+        }
+    } else {
+#pragma unroll
+        for (int j = 1; j < MSC_VEC; ++j) col[j] = msc_pack_col(a, xs + j < M ? xs + j : M - 1);
+    }
+
+    // whole group in one plane of a plain segment, source and destination addressable as vectors for every channel
+    const bool fast = one_plane && a.vec_ok && col[0].seg < a.d.K && (col[0].cs & (MSC_VEC - 1)) == 0 &&
+                      msc_group_vector_ok<IN_BF16>(col[0].data, col[0].base, true);
+    if (fast) {
+        int c = c0;
+        for (; c + MSC_ACT_UNROLL <= c1; c += MSC_ACT_UNROLL) {
+            float v[MSC_ACT_UNROLL][MSC_VEC];
+#pragma unroll
+            for (int u = 0; u < MSC_ACT_UNROLL; ++u) msc_load_vector<IN_BF16>(col[0].data, col[0].base + (long long)(c + u) * col[0].cs, v[u]);
+            if (sig) {
+#pragma unroll
+                for (int u = 0; u < MSC_ACT_UNROLL; ++u)
+#pragma unroll
+                    for (int j = 0; j < MSC_VEC; ++j) v[u][j] = 1.0f / (1.0f + expf(-v[u][j]));
+            }
+#pragma unroll
+            for (int u = 0; u < MSC_ACT_UNROLL; ++u) msc_pack_store_vector<OUT_BF16>(a.d.out, (long long)(c + u) * M + xs, v[u]);
+        }
+        for (; c < c1; ++c) {
+            float v[MSC_VEC];
+            msc_load_vector<IN_BF16>(col[0].data, col[0].base + (long long)c * col[0].cs, v);
+            if (sig) {
+#pragma unroll
+                for (int j = 0; j < MSC_VEC; ++j) v[j] = 1.0f / (1.0f + expf(-v[j]));
+            }
+            msc_pack_store_vector<OUT_BF16>(a.d.out, (long long)c * M + xs, v);
+        }
+        return;
+    }
+
+    const long long HW = (long long)a.H * a.W;
+    for (int c = c0; c < c1; ++c) {
+        float v[MSC_VEC];
+        const long long o = (long long)c * M + xs;
+#pragma unroll
+        for (int j = 0; j < MSC_VEC; ++j) {
+            v[j] = 0.0f;
+            if (j >= n) continue;
+            int win;
+            v[j] = msc_pack_value<IN_BF16>(a, col[j], c, win);
+            if (sig) v[j] = 1.0f / (1.0f + expf(-v[j]));
+            if (col[j].seg >= a.d.K && a.d.index) a.d.index[((long long)col[j].b * C + c) * HW + col[j].i] = (uint8_t)win;
+        }
+        if (a.vec_ok && n == MSC_VEC) {
+            msc_pack_store_vector<OUT_BF16>(a.d.out, o, v);
+        } else {
+#pragma unroll
+            for (int j = 0; j < MSC_VEC; ++j) {
+                if (j >= n) continue;
+                if (OUT_BF16) ((uint16_t*)a.d.out)[o + j] = msc_bf16_bits(v[j]);
+                else ((float*)a.d.out)[o + j] = v[j];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MSC_THREADS) void spx_msc_pack_bwd_kernel(const SpxMscPackArgs a) {
+    const long long id = (long long)blockIdx.x * MSC_THREADS + threadIdx.x;
+    const int H = a.H, W = a.W, K = a.d.K, C = a.d.C, M = a.M;
+    if (id >= a.gofs[SPX_MSC_MAX_MAPS]) return;
+    int k = 0, h = 1, w = 1, off = 0;
+    float rh = 1.0f, rw = 1.0f;
+    long long local = 0;
+    void* grad = nullptr;
+#pragma unroll
+    for (int q = 0; q < SPX_MSC_MAX_MAPS; ++q) {
+        if (q < K && id >= a.gofs[q] && id < a.gofs[q + 1]) {
+            k = q;
+            h = a.d.maps[q].h;
+            w = a.d.maps[q].w;
+            rh = a.rh[q];
+            rw = a.rw[q];
+            off = a.off[q];
+            local = id - a.gofs[q];
+            grad = a.d.grads[q];
+        }
+    }
+    const int j = (int)(local % w);
+    const int i = (int)((local / w) % h);
+    const long long plane = local / ((long long)w * h);                           // b * C + c
+    const int b = (int)(plane / C), c = (int)(plane - (long long)b * C);
+    const bool g16 = a.d.g_dtype == 0, y16 = a.d.out_dtype == 0, sig = a.d.activation == 1;
+    const long long row = (long long)c * M;
+
+    // the map's own segment first
+    float acc;
+    {
+        const long long o = row + off + (long long)b * h * w + (long long)i * w + j;
+        float g = msc_load(a.d.g, g16, o);
+        if (sig) {
+            const float y = msc_load(a.d.out, y16, o);
+            g = g * (y * (1.0f - y));
+        }
+        acc = g;
+    }
+    if (a.with_max) {
+        const long long ibase = plane * H * W;                                    // the index is [B, C, H, W]
+        const long long gbase = row + a.off_max + (long long)b * H * W;
+        if (k == 0) {
+            const long long p = (long long)i * W + j;
+            if (!a.d.index || a.d.index[ibase + p] == 0) {
+                float g = msc_load(a.d.g, g16, gbase + p);
+                if (sig) {
+                    const float y = msc_load(a.d.out, y16, gbase + p);
+                    g = g * (y * (1.0f - y));
+                }
+                acc += g;
+            }
+        } else {
+            acc = msc_gather(a.d, k, h, w, rh, rw, H, W, i, j, gbase, ibase, acc);
+        }
+    }
+    if (a.d.in_dtype == 0) ((uint16_t*)grad)[local] = msc_bf16_bits(acc);
+    else ((float*)grad)[local] = acc;
+}
+
+static void msc_pack_fill(SpxMscPackArgs& a, const spx_msc& d, int with_max) {
+    a.d = d;
+    a.H = d.maps[0].h;
+    a.W = d.maps[0].w;
+    a.with_max = with_max ? 1 : 0;
+    a.nseg = d.K + a.with_max;
+    long long m = 0;
+    for (int k = 0; k < SPX_MSC_MAX_MAPS + 2; ++k) {
+        a.off[k] = (int)m;
+        if (k < SPX_MSC_MAX_MAPS) a.rh[k] = a.rw[k] = 1.0f;
+        if (k < d.K) {
+            a.rh[k] = (float)d.maps[k].h / (float)a.H;
+            a.rw[k] = (float)d.maps[k].w / (float)a.W;
+            m += (long long)d.B * d.maps[k].h * d.maps[k].w;
+        } else if (k == d.K && with_max) {
+            m += (long long)d.B * a.H * a.W;
+        }
+    }
+    a.M = (int)m;                                        // (< 2^31: checked by the entry point)
+    a.off_max = a.off[d.K];
+}
+
+hipError_t spx_launch_msc_pack_fwd(const spx_msc& d, int with_max, hipStream_t s) {
+    SpxMscPackArgs a = {};
+    msc_pack_fill(a, d, with_max);
+    const size_t vbytes = d.out_dtype == 0 ? 8 : 16;
+    a.vec_ok = (a.M % MSC_VEC == 0 && (uintptr_t)d.out % vbytes == 0) ? 1 : 0;
+    const long long groups = ((long long)a.M + MSC_VEC - 1) / MSC_VEC;
+    const unsigned bx = (unsigned)((groups + MSC_THREADS - 1) / MSC_THREADS);
+    // enough blocks to fill the chip (about 8 per CU), then as many channels per block as that leaves (a multiple of the four
+    // channels of a step): the decode of the columns is paid once per block and thread
+    long long chunks = 2048 / (long long)bx;
+    if (chunks < 1) chunks = 1;
+    if (chunks > d.C) chunks = d.C;
+    a.cchunk = (int)((d.C + chunks - 1) / chunks);
+    a.cchunk = (a.cchunk + MSC_ACT_UNROLL - 1) / MSC_ACT_UNROLL * MSC_ACT_UNROLL;
+    const dim3 grid(bx, (unsigned)((d.C + a.cchunk - 1) / a.cchunk), 1);
+    MSC_LAUNCH_FWD(spx_msc_pack_fwd_kernel);
+    return hipGetLastError();
+}
+
+hipError_t spx_launch_msc_pack_bwd(const spx_msc& d, int with_max, hipStream_t s) {
+    SpxMscPackArgs a = {};
+    msc_pack_fill(a, d, with_max);
+    a.gofs[0] = 0;
+    for (int k = 0; k < SPX_MSC_MAX_MAPS; ++k) {
+        const long long n = (k < d.K && d.grads[k]) ? (long long)d.B * d.C * d.maps[k].h * d.maps[k].w : 0;
+        a.gofs[k + 1] = a.gofs[k] + n;
+    }
+    const long long total = a.gofs[SPX_MSC_MAX_MAPS];
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(spx_msc_pack_bwd_kernel, dim3((unsigned)((total + MSC_THREADS - 1) / MSC_THREADS)), dim3(MSC_THREADS), 0, s, a);
     return hipGetLastError();
 }

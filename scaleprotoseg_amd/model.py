@@ -16,6 +16,8 @@ from .model_multiscale import PPNetMultiScale
 
 
 class PPNet(PPNetMultiScale):
+    _supports_packed = False      # fuse_feature_epilogue(packed=True): the multi-scale prototype model only
+
     def __init__(
         self,
         features: nn.Module,

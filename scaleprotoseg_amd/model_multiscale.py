@@ -20,7 +20,7 @@ from .functional import (MAX_FUSED_HEAD_ROWS, BankLayout, ClassGather, SpxError,
                          cross_entropy_from_logits, identity_is_one_hot, invalidate_pack_cache, proto_head_forward,
                          push_min_from_features, shifted_labels_i32, wide_linear)
 from .loss import ClassDistances
-from .msc import MSC
+from .msc import MSC, PackedMaps
 from .scale_head import WeightedAgg
 
 
@@ -210,12 +210,21 @@ class _PrototypeBankMixin:
 
     # -- reference methods on the distance path ---------------------------------------------------
     _feature_epilogue = None
+    _feature_packed = False
+    _supports_packed = False      # packed=True: PPNetMultiScale alone sets it
 
-    def fuse_feature_epilogue(self, dtype: Optional[torch.dtype] = torch.bfloat16):
+    def fuse_feature_epilogue(self, dtype: Optional[torch.dtype] = torch.bfloat16, packed: bool = False):
         """Opt in (``None``: undo): ``conv_features`` calls ``features.fused(x, "sigmoid", dtype)`` - the MSC maximum, the add-on
         sigmoid and the cast in one launch (csrc/spx_msc.hip) - instead of ``add_on_layers(features(x))``, so that everything
         downstream receives ``dtype`` features without an fp32 round trip.  Accepted only when ``features`` is a
-        ``scaleprotoseg_amd.MSC`` and ``add_on_layers`` is exactly ``nn.Sequential(nn.Sigmoid())`` (deeplab_simple)."""
+        ``scaleprotoseg_amd.MSC`` and ``add_on_layers`` is exactly ``nn.Sequential(nn.Sigmoid())`` (deeplab_simple).
+
+        ``packed=True`` (``PPNetMultiScale`` only): in training ``conv_features`` returns the four maps as ONE ``PackedMaps``
+        (``features.fused_packed``: one launch instead of four), and ``forward`` / ``forward_from_conv_features`` run ONE distance
+        launch over all of them and split its outputs into the reference's list.  In eval nothing changes."""
+        if packed and dtype is not None and not self._supports_packed:
+            raise SpxError(f"fuse_feature_epilogue: packed=True is for PPNetMultiScale, not {type(self).__name__} "
+                           "(the group model's spx_group / spx_group_wd attachments are per tensor)")
         if dtype is not None:
             add_on = self.add_on_layers
             if not isinstance(self.features, MSC):
@@ -225,10 +234,13 @@ class _PrototypeBankMixin:
             if dtype not in (torch.bfloat16, torch.float32):
                 raise SpxError(f"fuse_feature_epilogue: dtype {dtype}; bfloat16 or float32")
         object.__setattr__(self, "_feature_epilogue", dtype)
+        object.__setattr__(self, "_feature_packed", bool(packed) and dtype is not None)
 
     def conv_features(self, x):
         """features -> add_on_layers, list-aware for MSC training inputs (model_multiscale.py:246-253)."""
         if self._feature_epilogue is not None:
+            if self._feature_packed:
+                return self.features.fused_packed(x, "sigmoid", self._feature_epilogue)
             return self.features.fused(x, "sigmoid", self._feature_epilogue)
         x = self.features(x)
         if isinstance(x, list):
@@ -261,6 +273,8 @@ class _PrototypeBankMixin:
     def push_forward(self, x):
         """(conv_features, distances) for the push (model_multiscale.py:390-398)."""
         conv = self.conv_features(x)
+        if isinstance(conv, PackedMaps):
+            raise SpxError("push_forward: the push runs in eval mode; packed training maps have no push path")
         if isinstance(conv, list):
             return [(c, self._scale_l2_convolution(c)) for c in conv]
         return conv, self._scale_l2_convolution(conv)
@@ -276,6 +290,8 @@ class _PrototypeBankMixin:
     def push_min_from_conv(self, conv, labels_for_grid, void_class=None, max_dist: float = 1e10):
         """``push_min_distances`` on features that are already computed (the single-pass push encodes a run of images once and
         keeps the features for the gather)."""
+        if isinstance(conv, PackedMaps):
+            raise SpxError("push_min_from_conv: the push runs in eval mode; packed training maps have no push path")
         if isinstance(conv, list) or not conv.is_cuda or getattr(self, "scale_head", None) is not None:
             return None
         self._check_fusable()
@@ -291,12 +307,16 @@ class _PrototypeBankMixin:
 
     def forward(self, x, **kwargs):
         conv = self.conv_features(x)
+        if isinstance(conv, PackedMaps):  # MSC in training, one launch: the flags pass through, as upstream :336
+            return self.forward_from_conv_features(conv, **kwargs)
         if isinstance(conv, list):  # MSC
             return [self.forward_from_conv_features(c, **kwargs) for c in conv]
         return self.forward_from_conv_features(conv, **kwargs)
 
 
 class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
+    _supports_packed = True
+
     def __init__(
         self,
         features: nn.Module,
@@ -345,7 +365,13 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         as is.  With ``ce_target`` (same convention and grid) the pixel-wise cross entropy of the logits is computed in the
         kernel's logits epilogue and travels on the returned logits as ``logits.spx_ce`` (loss, argmax prediction);
         ``scaleprotoseg_amd.loss.PixelWiseCrossEntropyLoss(ignore_index=-1)`` called with that ``logits`` and the same
-        ``ce_target`` returns it instead of running a second pass (loss.py:9-48, caller module_multiscale.py:239)."""
+        ``ce_target`` returns it instead of running a second pass (loss.py:9-48, caller module_multiscale.py:239).
+
+        A ``PackedMaps`` (``msc_pack``; ``fuse_feature_epilogue(dtype, packed=True)`` in training) is taken as the list of its
+        segments, computed by ONE launch: the result is a list with one tuple per segment, in the reference's order and tuple
+        modes, and the flags apply to every segment.  ``target_labels`` is then a list of one [B, h_k, w_k] map per segment."""
+        if isinstance(conv_features, PackedMaps):
+            return self._forward_packed(conv_features, return_activations, return_distances, target_labels, ce_target)
         if isinstance(conv_features, list):
             return [self.forward_from_conv_features(c) for c in conv_features]  # flags dropped, as in :359
         if not (hasattr(self, "patch_classification") and self.patch_classification):
@@ -397,6 +423,60 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         if return_activations and return_distances:
             return logits, dist, act
         return logits, dist
+
+    def _forward_packed(self, pk: PackedMaps, return_activations, return_distances, target_labels, ce_target):
+        """The four training maps on one pixel axis (``pk.features`` [1, C, 1, M]): one forward launch - and, through autograd,
+        one pixel-side and one parameter-side backward launch - for all segments.  Distances, activations and logits are
+        per-pixel quantities, so the outputs are split by columns / rows: logits [B, h_k, w_k, K] and activations [B h_k w_k, P]
+        are row slices, distances [B, P, h_k, w_k] strided views of the one map.  ``torch.split_with_sizes`` gives each output
+        one backward that assembles the packed gradient in a single pass."""
+        who = "forward_from_conv_features(PackedMaps)"
+        if not (hasattr(self, "patch_classification") and self.patch_classification):
+            raise Exception("Original Prototype Network Implementation")
+        if ce_target is not None:
+            raise SpxError(f"{who}: ce_target is refused - the fused cross entropy has one mean and one backward coefficient per "
+                           "launch, the objective one per segment (module_multiscale.py:273); call PixelWiseCrossEntropyLoss on "
+                           "each segment's logits")
+        if self.scale_head is not None:
+            raise SpxError(f"{who}: a scale_head chains launches per scale and has no packed form")
+        if callable(self.prototype_activation_function):
+            raise SpxError(f"{who}: a callable similarity has no packed form ('log' or 'linear')")
+        self._check_fusable()
+        lay = pk.layout
+        want_dist = return_distances or not return_activations
+        wide = self.num_classes > MAX_FUSED_HEAD_ROWS
+        layout = self._layout(1 if wide else self.num_classes)
+        gather = None
+        if target_labels is not None:
+            lay.check_labels(target_labels, f"{who}: target_labels")                       # before any launch
+            if want_dist:
+                gather = self._class_gather(lay.pack_labels(target_labels), layout, pk.features.device)
+        logits, dist, act = proto_head_forward(
+            pk.features, self.prototype_vectors, None if wide else self.last_layer.weight, layout,
+            want_distances=want_dist and gather is None, want_activations=return_activations or wide,
+            epsilon=self.epsilon, activation=self.prototype_activation_function, class_gather=gather,
+        )[:3]
+        if wide:
+            logits = wide_linear(act, self.last_layer.weight)
+        n = len(lay)
+        logits_k = [t.reshape(lay.B, h, w, -1) for t, (h, w) in zip(lay.split_rows(logits), lay.grids)]
+        acts_k = lay.split_rows(act) if return_activations else [None] * n
+        dists_k = [None] * n
+        if want_dist:
+            dists_k = list(lay.split_columns(dist))
+            if gather is not None:
+                dists_k = [ClassDistances(values=v, labels=gather.labels[0, o:o + m].view(lay.B, -1), table=gather.table, grid=g,
+                                          target=t, target_version=t._version)
+                           for v, o, m, g, t in zip(dists_k, lay.offsets, lay.sizes, lay.grids, target_labels)]
+        out = []
+        for l, d, a in zip(logits_k, dists_k, acts_k):
+            if return_activations and not return_distances:
+                out.append((l, a))
+            elif return_activations and return_distances:
+                out.append((l, d, a))
+            else:
+                out.append((l, d))
+        return out
 
     def _forward_callable_similarity(self, conv_features, return_activations, return_distances, target_labels, ce_target):
         """A user-supplied ``prototype_activation_function`` (model_multiscale.py:329-330: any callable on the [B, P, H, W]

@@ -41,13 +41,31 @@ stock formula, so that its structure can be tested without a GPU.  ``fused(x, ac
 returns with activation and dtype applied by the same launch (in training the three unfused list elements go through the K = 1
 launch); ``_PrototypeBankMixin.fuse_feature_epilogue`` makes a model's ``conv_features`` call it.
 
-Left out: the input-image pyramid (stock ``F.interpolate``), list outputs of the base (the reference raises on them too), add-ons
-other than the bare sigmoid, and one ragged launch of the distance kernel over the four training outputs.
+The packed training maps ``msc_pack(maps, activation="none", dtype=None, with_max=True, out=None)``
+---------------------------------------------------------------------------------------------------
+In training the reference's ``MSC`` returns four maps, ``[full] + pyramid + [max]``, and the model runs its prototype path on
+each.  ``msc_pack`` writes them in ONE launch (``spx_msc_pack_fwd``) side by side on one pixel axis: a contiguous buffer
+``[C, M]``, segment ``k < K`` = ``act(maps[k])`` at its own grid, segment ``K`` (``with_max``) = the ``msc_max`` of all maps, pixel
+``(b, i)`` of segment ``k`` at column ``off_k + b h_k w_k + i``, ``off_k = sum_{j<k} B h_j w_j``, no padding (``PackedLayout``, pure
+Python).  Every value, the index and the rounding are ``msc_max``'s, bit for bit.  The result is a ``PackedMaps``: ``features``
+``[1, C, 1, M]`` is what the distance kernels take as a one-image batch of M pixels - distances, activations, logits and
+gradients are per-pixel quantities, so one forward and one backward launch serve all four maps -, ``views()`` are the maps
+``[B, C, h_k, w_k]`` as strided views, ``index`` the uint8 winner ``[B, C, H, W]`` (None without the maximum).  With
+``with_max=False`` any maps of a common B and C form a ragged batch.  The backward (``spx_msc_pack_bwd``) is one launch for all
+maps: per source element its own segment's term ``g y (1 - y)`` first, then the gather over the maximum's segment in
+``msc_max``'s order, summed in fp32 and rounded once; no atomics, no workspace, capturable.  ``out=`` ([C, M], calls without a
+gradient) may be any element-aligned contiguous buffer: the kernel stores vectors when M is a multiple of 4 and ``out`` is
+aligned to 8 (bf16) / 16 (fp32) bytes, and element by element otherwise.  Limits: ``M < 2^31``, ``C M < 2^40``.
+``MSC.fused_packed(x, activation, dtype)`` returns the ``PackedMaps`` in training and what ``fused`` returns otherwise.
+
+Left out: the input-image pyramid (stock ``F.interpolate``), list outputs of the base (the reference raises on them too) and
+add-ons other than the bare sigmoid.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -124,23 +142,7 @@ def msc_max(maps: Sequence[torch.Tensor], activation: str = "none", dtype: Optio
     ``dtype``: one launch.  The contract is the module docstring's.  Returns ``y`` or ``(y, index)``."""
     if activation not in MSC_ACTIVATIONS:
         raise SpxError(f"msc_max: unknown activation {activation!r} (one of {sorted(MSC_ACTIVATIONS)})")
-    if isinstance(maps, torch.Tensor):
-        maps = [maps]
-    maps = list(maps)
-    if not 1 <= len(maps) <= _lib.SPX_MSC_MAX_MAPS:
-        raise SpxError(f"msc_max: {len(maps)} maps (1 to {_lib.SPX_MSC_MAX_MAPS})")
-    for k, m in enumerate(maps):
-        if m.dtype not in _DTYPE_CODE:
-            raise SpxError(f"msc_max: map {k} is {m.dtype}; float32 or bfloat16")
-        if m.dtype != maps[0].dtype:
-            raise SpxError(f"msc_max: mixed dtypes ({maps[0].dtype} and {m.dtype})")
-        if m.dim() != 4 or min(m.shape) < 1:
-            raise SpxError(f"msc_max: map {k} must be a non-empty [B, C, h, w], got {tuple(m.shape)}")
-        if tuple(m.shape[:2]) != tuple(maps[0].shape[:2]):
-            raise SpxError(f"msc_max: map {k} has (B, C) = {tuple(m.shape[:2])}, map 0 {tuple(maps[0].shape[:2])}")
-        h, w = int(m.shape[2]), int(m.shape[3])
-        if (w > 1 and m.stride(3) != 1) or (h > 1 and m.stride(2) != w) or m.stride(0) < 0 or m.stride(1) < 0:
-            raise SpxError(f"msc_max: the {h} x {w} plane of map {k} is not contiguous (strides {tuple(m.stride())})")
+    maps = _check_maps("msc_max", maps)
     out_dtype = dtype if dtype is not None else maps[0].dtype
     if out_dtype not in _DTYPE_CODE:
         raise SpxError(f"msc_max: dtype {out_dtype}; float32 or bfloat16")
@@ -159,6 +161,196 @@ def msc_max(maps: Sequence[torch.Tensor], activation: str = "none", dtype: Optio
     return (y, index) if return_index else y
 
 
+class PackedLayout:
+    """The segment arithmetic of the packed pixel axis, on the host alone: ``grids`` = the (h, w) of every segment in order (for
+    the training maps: the K maps, then the first grid again for the maximum), ``B`` the common batch."""
+
+    def __init__(self, B: int, grids: Sequence[Tuple[int, int]]):
+        self.B = int(B)
+        self.grids = tuple((int(h), int(w)) for h, w in grids)
+        if self.B < 1 or not self.grids or any(h < 1 or w < 1 for h, w in self.grids):
+            raise SpxError(f"PackedLayout: batch {B} and grids {tuple(grids)} (all >= 1, at least one grid)")
+        self.sizes = tuple(self.B * h * w for h, w in self.grids)          # columns per segment
+        offs = [0]
+        for n in self.sizes:
+            offs.append(offs[-1] + n)
+        self.offsets, self.M = tuple(offs[:-1]), offs[-1]
+        if self.M >= 2 ** 31:
+            raise SpxError(f"PackedLayout: {self.M} packed pixels (M < 2^31)")
+
+    @classmethod
+    def of_maps(cls, B: int, grids: Sequence[Tuple[int, int]], with_max: bool = True) -> "PackedLayout":
+        grids = list(grids)
+        return cls(B, grids + ([grids[0]] if with_max else []))
+
+    def __len__(self) -> int:
+        return len(self.grids)
+
+    @property
+    def segments(self) -> Tuple[Tuple[int, int, int, int], ...]:
+        """((off, B, h, w), ...)"""
+        return tuple((o, self.B, h, w) for o, (h, w) in zip(self.offsets, self.grids))
+
+    def column(self, k: int, b: int, i: int) -> int:
+        h, w = self.grids[k]
+        return self.offsets[k] + b * h * w + i
+
+    def view_strides(self, k: int) -> Tuple[int, int, int, int]:
+        """Element strides of segment k taken as [B, C, h, w] out of the [C, M] buffer."""
+        h, w = self.grids[k]
+        return (h * w, self.M, w, 1)
+
+    def view(self, buffer: torch.Tensor, k: int) -> torch.Tensor:
+        """Segment k of ``buffer`` ([..., rows, M] contiguous, e.g. [C, M], [1, C, 1, M] or a distance map [1, P, 1, M]) as the
+        strided view [B, rows, h, w]."""
+        rows = buffer.numel() // self.M
+        h, w = self.grids[k]
+        return buffer.as_strided((self.B, rows, h, w), self.view_strides(k), buffer.storage_offset() + self.offsets[k])
+
+    def check_labels(self, labels, what: str = "target_labels") -> None:
+        if isinstance(labels, torch.Tensor) or len(labels) != len(self.grids):
+            n = "a tensor" if isinstance(labels, torch.Tensor) else f"{len(labels)} maps"
+            raise SpxError(f"{what}: a list with one label map per segment ({len(self.grids)}), got {n}")
+        for k, (t, (h, w)) in enumerate(zip(labels, self.grids)):
+            if tuple(t.shape) != (self.B, h, w):
+                raise SpxError(f"{what}[{k}] must be [{self.B}, {h}, {w}] (the segment's grid), got {tuple(t.shape)}")
+
+    def pack_labels(self, labels: Sequence[torch.Tensor]) -> torch.Tensor:
+        """One [B, h_k, w_k] label map per segment -> the packed label row [1, M], in the maps' common dtype."""
+        self.check_labels(labels)
+        return torch.cat([t.reshape(-1) for t in labels]).reshape(1, self.M)
+
+    def split_rows(self, t: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        """[M, n] -> the segments' row slices [B h_k w_k, n] (one backward pass assembles their gradients)."""
+        return torch.split_with_sizes(t, list(self.sizes), dim=0)
+
+    def split_columns(self, t: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        """[1, R, (1,) M] -> the segments as [B, R, h_k, w_k] views (4-d input) or [B, R, h_k w_k] (3-d input)."""
+        R = t.shape[1]
+        parts = torch.split_with_sizes(t.reshape(R, self.M), list(self.sizes), dim=1)
+        if t.dim() == 4:
+            return tuple(p.reshape(R, self.B, h, w).permute(1, 0, 2, 3) for p, (h, w) in zip(parts, self.grids))
+        return tuple(p.reshape(R, self.B, h * w).permute(1, 0, 2) for p, (h, w) in zip(parts, self.grids))
+
+
+@dataclass
+class PackedMaps:
+    """The result of ``msc_pack``: ``features`` [1, C, 1, M] (contiguous; what ``forward_from_conv_features`` takes), the
+    ``layout`` and the uint8 ``index`` [B, C, H, W] of the maximum's segment (None without one)."""
+
+    features: torch.Tensor
+    layout: PackedLayout
+    index: Optional[torch.Tensor] = None
+
+    @property
+    def segments(self):
+        return self.layout.segments
+
+    @property
+    def M(self) -> int:
+        return self.layout.M
+
+    def views(self) -> List[torch.Tensor]:
+        """The segments as [B, C, h_k, w_k] views, strides (h_k w_k, M, w_k, 1)."""
+        return [self.layout.view(self.features, k) for k in range(len(self.layout))]
+
+
+def _check_maps(who: str, maps) -> List[torch.Tensor]:
+    if isinstance(maps, torch.Tensor):
+        maps = [maps]
+    maps = list(maps)
+    if not 1 <= len(maps) <= _lib.SPX_MSC_MAX_MAPS:
+        raise SpxError(f"{who}: {len(maps)} maps (1 to {_lib.SPX_MSC_MAX_MAPS})")
+    for k, m in enumerate(maps):
+        if m.dtype not in _DTYPE_CODE:
+            raise SpxError(f"{who}: map {k} is {m.dtype}; float32 or bfloat16")
+        if m.dtype != maps[0].dtype:
+            raise SpxError(f"{who}: mixed dtypes ({maps[0].dtype} and {m.dtype})")
+        if m.dim() != 4 or min(m.shape) < 1:
+            raise SpxError(f"{who}: map {k} must be a non-empty [B, C, h, w], got {tuple(m.shape)}")
+        if tuple(m.shape[:2]) != tuple(maps[0].shape[:2]):
+            raise SpxError(f"{who}: map {k} has (B, C) = {tuple(m.shape[:2])}, map 0 {tuple(maps[0].shape[:2])}")
+        h, w = int(m.shape[2]), int(m.shape[3])
+        if (w > 1 and m.stride(3) != 1) or (h > 1 and m.stride(2) != w) or m.stride(0) < 0 or m.stride(1) < 0:
+            raise SpxError(f"{who}: the {h} x {w} plane of map {k} is not contiguous (strides {tuple(m.stride())})")
+    return maps
+
+
+class _MscPackFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, activation, out_dtype, out, with_max, layout, *maps):
+        lib = _lib.load()
+        B, Cc, H, W = maps[0].shape
+        need = any(ctx.needs_input_grad[5:])
+        if out is not None:
+            ctx.mark_dirty(out)
+        y = out if out is not None else torch.empty((Cc, layout.M), dtype=out_dtype, device=maps[0].device)
+        index = torch.empty((B, Cc, H, W), dtype=torch.uint8, device=y.device) if with_max else None
+        a = _describe(maps, out_dtype, activation)
+        a.out, a.index = y.data_ptr(), None if index is None else index.data_ptr()
+        _lib.check(lib.spx_msc_pack_fwd(C.byref(a), int(with_max), _lib.stream_ptr()))
+        ctx.activation, ctx.out_dtype, ctx.with_max = activation, out_dtype, with_max
+        ctx.shapes = [tuple(m.shape) for m in maps]
+        ctx.map_dtype = maps[0].dtype
+        if need:
+            ctx.save_for_backward(y, index)
+        if index is None:
+            index = torch.empty(0, dtype=torch.uint8, device=y.device)
+        ctx.mark_non_differentiable(index)
+        return y, index
+
+    @staticmethod
+    def backward(ctx, g, _g_index):
+        lib = _lib.load()
+        y, index = ctx.saved_tensors
+        if g.dtype not in _DTYPE_CODE:
+            g = g.float()
+        g = g.contiguous()
+        grads: List[Optional[torch.Tensor]] = [
+            torch.empty(s, dtype=ctx.map_dtype, device=g.device) if ctx.needs_input_grad[5 + k] else None
+            for k, s in enumerate(ctx.shapes)]
+        a = _lib.SpxMsc()
+        a.K, a.B, a.C = len(ctx.shapes), ctx.shapes[0][0], ctx.shapes[0][1]
+        a.in_dtype, a.out_dtype, a.g_dtype = _DTYPE_CODE[ctx.map_dtype], _DTYPE_CODE[ctx.out_dtype], _DTYPE_CODE[g.dtype]
+        a.activation = ctx.activation
+        for k, s in enumerate(ctx.shapes):
+            a.maps[k].h, a.maps[k].w = s[2], s[3]              # (the backward reads the maps' sizes only)
+            a.grads[k] = None if grads[k] is None else grads[k].data_ptr()
+        a.out, a.g = y.data_ptr(), g.data_ptr()
+        a.index = None if index is None else index.data_ptr()
+        _lib.check(lib.spx_msc_pack_bwd(C.byref(a), int(ctx.with_max), _lib.stream_ptr()))
+        return (None, None, None, None, None, *grads)
+
+
+def msc_pack(maps: Sequence[torch.Tensor], activation: str = "none", dtype: Optional[torch.dtype] = None,
+             with_max: bool = True, out: Optional[torch.Tensor] = None) -> PackedMaps:
+    """``act(maps[k])`` at every map's own grid and (``with_max``) the ``msc_max`` of all of them, side by side on one pixel
+    axis, cast to ``dtype``: one launch.  The contract is the module docstring's.  Returns a ``PackedMaps``."""
+    who = "msc_pack"
+    if activation not in MSC_ACTIVATIONS:
+        raise SpxError(f"{who}: unknown activation {activation!r} (one of {sorted(MSC_ACTIVATIONS)})")
+    maps = _check_maps(who, maps)
+    out_dtype = dtype if dtype is not None else maps[0].dtype
+    if out_dtype not in _DTYPE_CODE:
+        raise SpxError(f"{who}: dtype {out_dtype}; float32 or bfloat16")
+    B, Cc = int(maps[0].shape[0]), int(maps[0].shape[1])
+    layout = PackedLayout.of_maps(B, [tuple(m.shape[2:]) for m in maps], bool(with_max))
+    if Cc * layout.M >= 2 ** 40:
+        raise SpxError(f"{who}: C * M = {Cc} * {layout.M} (below 2^40)")
+    if out is not None:
+        if tuple(out.shape) != (Cc, layout.M) or out.dtype != out_dtype or not out.is_contiguous():
+            raise SpxError(f"{who}: out must be a contiguous {out_dtype} {(Cc, layout.M)}, got {out.dtype} "
+                           f"{tuple(out.shape)} with strides {tuple(out.stride())}")
+    for k, m in enumerate(maps + ([out] if out is not None else [])):
+        _lib.require_gpu(m, f"{who}: out" if k == len(maps) else f"{who}: map {k}")
+        if m.device != maps[0].device:
+            raise SpxError(f"{who}: {m.device} and {maps[0].device} in one call")
+    if out is not None and torch.is_grad_enabled() and any(m.requires_grad for m in maps):
+        raise SpxError(f"{who}: out= is for calls without a gradient")
+    y, index = _MscPackFn.apply(MSC_ACTIVATIONS[activation], out_dtype, out, bool(with_max), layout, *maps)
+    return PackedMaps(features=y.view(1, Cc, 1, layout.M), layout=layout, index=index if with_max else None)
+
+
 class MSC(nn.Module):
     """Multi-scale inputs (segmentation/utils.py:71-111) on ``msc_max``; see the module docstring."""
 
@@ -167,7 +359,7 @@ class MSC(nn.Module):
         self.base = base
         self.scales = scales if scales is not None else [0.5, 0.75]
 
-    def _run(self, x, activation: Optional[str], dtype):
+    def _run(self, x, activation: Optional[str], dtype, packed: bool = False):
         logits = self.base(x)
         if len(self.scales) == 0:
             return logits if activation is None else self._finish(logits, activation, dtype)
@@ -177,6 +369,8 @@ class MSC(nn.Module):
         for p in self.scales:
             h = F.interpolate(x, scale_factor=p, mode="bilinear", align_corners=False)
             pyramid.append(self.base(h))
+        if packed and self.training:
+            return msc_pack([logits] + pyramid, activation, dtype, with_max=True)
         if logits.is_cuda:
             fused = msc_max([logits] + pyramid, activation or "none", dtype)
         else:
@@ -205,3 +399,8 @@ class MSC(nn.Module):
     def fused(self, x, activation: str = "sigmoid", dtype: Optional[torch.dtype] = torch.bfloat16):
         """What ``forward`` returns, with ``activation`` and the cast to ``dtype`` applied by the same launch."""
         return self._run(x, activation, dtype)
+
+    def fused_packed(self, x, activation: str = "sigmoid", dtype: Optional[torch.dtype] = torch.bfloat16):
+        """In training (with scales): the four maps of ``fused`` as ONE ``PackedMaps`` (``msc_pack``: one launch instead of
+        four).  In eval, or with empty ``scales``: what ``fused`` returns."""
+        return self._run(x, activation, dtype, packed=True)
