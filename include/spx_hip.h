@@ -209,6 +209,33 @@ int spx_ce_bwd(const float* logits, const float* lse, const int32_t* labels, con
 int spx_ce_finish(const float* partials, int64_t n_pairs, float* loss, float* count_sum, void* stream);
 int spx_shift_labels(const void* labels, int32_t is_int64, int64_t n, int32_t* out, void* stream);
 
+/* Segmented cross entropy: S <= 16 row ranges of ONE [M, K] logits tensor (the packed MSC training maps: the four maps'
+ * logits of one distance launch), each with its own mean and its own backward coefficient, in one forward, one finish and
+ * one backward launch.  Segment k is the rows [off[k], off[k+1]); off[0] = 0, off[S] = M, every segment non-empty.  The
+ * table is copied into the kernel arguments: no device table, and a captured launch keeps the layout it was captured with.
+ *   spx_ce_seg_partials  number of (loss sum, valid count, correct count) fp32 triples the forward writes: 4 per started
+ *                        block of 256 rows of every segment (0 with spx_last_error() for a bad table)
+ *   spx_ce_seg_fwd       lse [M], pred [M] (may be NULL) and the triples; block j of segment k starts at row off[k] + 256 j,
+ *                        so no wave holds rows of two segments
+ *   spx_ce_seg_finish    losses[k] = sum_k / count_k (0 / 0 = nan), mean[0] = (((l_0 + l_1) + l_2) + ...) / S, count[k] the fp32
+ *                        divisor, valid[k] / correct[k] int32 (correct: a valid row whose pred equals its label)
+ *   spx_ce_seg_bwd       d_logits[m, :] = c_k (softmax - onehot) on the valid rows of segment k and exactly 0 on the ignored
+ *                        ones, c_k = (g_losses[k] + g_mean[0] / S) / count[k]; g_losses / g_mean are DEVICE arrays, NULL = 0
+ * For every segment losses[k], the lse / pred rows, the counts and d_logits carry the bits spx_ce_fwd / spx_ce_finish /
+ * spx_ce_bwd give on the contiguous slice with coef = g / count: the same lanes, the same summation order.  No float
+ * atomics, no workspace besides the triples, no host read. */
+typedef struct spx_ce_segments {
+    int32_t S;
+    int64_t off[17];
+} spx_ce_segments;
+size_t spx_ce_seg_partials(const spx_ce_segments* seg);
+int spx_ce_seg_fwd(const float* logits, const int32_t* labels, const spx_ce_segments* seg, int32_t K, float* lse, int32_t* pred,
+                   float* partials, void* stream);
+int spx_ce_seg_finish(const float* partials, const spx_ce_segments* seg, float* losses, float* mean, float* count, int32_t* valid,
+                      int32_t* correct, void* stream);
+int spx_ce_seg_bwd(const float* logits, const float* lse, const int32_t* labels, const spx_ce_segments* seg, const float* count,
+                   const float* g_losses, const float* g_mean, int32_t K, float* d_logits, void* stream);
+
 /* out [n1, n2] = a^T . b for tall-skinny fp32 operands a [M, n1], b [M, n2] with n1 * n2 <= 8192: the d W_g = d_logits^T . g
  * product of the grouping tail (segmentation/model/model_multiscale_group.py:305-308 through autograd) and its relatives.
  * Deterministic (per-workgroup partials summed in workgroup order).  workspace: spx_pixel_outer_workspace_bytes(). */

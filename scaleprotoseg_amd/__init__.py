@@ -67,6 +67,10 @@ Public surface mirrors the reference's module/function names for this path:
                                                      here they are written on one pixel axis in one launch, and one distance
                                                      forward / backward serves all four;
                                                      ppnet.fuse_feature_epilogue(dtype, packed=True))
+    SegmentedCrossEntropy, segmented_cross_entropy  (module_multiscale_group_train.py:232-310: the cross entropy of every
+                                                     segment of one packed forward, each with its own mean, counts and
+                                                     gradient, in three launches without a host read; the group model takes a
+                                                     PackedMaps too: PPNetMultiScaleGroup.forward_packed)
 Arithmetic runs in libspx_hip.so (hand-written gfx950 HIP); there is no CPU fallback.
 """
 from ._lib import SpxError, load as load_library  # noqa: F401
@@ -74,7 +78,9 @@ from .functional import (  # noqa: F401
     BankLayout,
     ClassGather,
     FusedCrossEntropy,
+    SegmentedCE,
     cross_entropy_from_logits,
+    segmented_cross_entropy,
     argmin_over_images,
     class_gather_table,
     proto_head_forward,
@@ -103,6 +109,7 @@ from .loss import (  # noqa: F401
     NormLoss,
     PixelWiseCrossEntropyLoss,
     ScaleMax,
+    SegmentedCrossEntropy,
     head_l1,
 )
 from .metrics import SegmentationMetrics, SegmentationResult  # noqa: F401

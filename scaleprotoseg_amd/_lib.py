@@ -52,6 +52,18 @@ class SpxCe(C.Structure):
     ]
 
 
+SPX_CE_MAX_SEGMENTS = 16
+
+
+class SpxCeSegments(C.Structure):
+    """spx_ce_segments of include/spx_hip.h: the row ranges of the segmented cross entropy (copied into the kernel arguments)."""
+
+    _fields_ = [
+        ("S", C.c_int32),
+        ("off", C.c_int64 * (SPX_CE_MAX_SEGMENTS + 1)),
+    ]
+
+
 class SpxReg(C.Structure):
     """spx_reg of include/spx_hip.h: the weight-side regularisers' inputs (spx_reg_fwd / spx_reg_bwd)."""
 
@@ -198,6 +210,7 @@ _PB = C.POINTER(SpxBatch)
 _PCE = C.POINTER(SpxCe)
 _PR = C.POINTER(SpxReg)
 _PA = C.POINTER(SpxActLoss)
+_PS = C.POINTER(SpxCeSegments)
 _V = C.c_void_p
 _I = C.c_int32
 _F = C.c_float
@@ -263,6 +276,10 @@ SIGNATURES = {
     "spx_dist_bwd_ce": (C.c_int, [_PP, _V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _V, _V, _V, _PCE, _V, _V, _V, _V, _F, _I, _V]),
     "spx_ce_fwd": (C.c_int, [_V, _V, C.c_int64, _I, _V, _V, _V, _V]),
     "spx_ce_bwd": (C.c_int, [_V, _V, _V, _V, C.c_int64, _I, _V, _V]),
+    "spx_ce_seg_partials": (C.c_size_t, [_PS]),
+    "spx_ce_seg_fwd": (C.c_int, [_V, _V, _PS, _I, _V, _V, _V, _V]),
+    "spx_ce_seg_finish": (C.c_int, [_V, _PS, _V, _V, _V, _V, _V, _V]),
+    "spx_ce_seg_bwd": (C.c_int, [_V, _V, _V, _PS, _V, _V, _V, _I, _V, _V]),
     "spx_eval_accumulate": (C.c_int, [_V, _PL, _V, _PL, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
     "spx_eval_topk": (C.c_int, [_V, _PL, _V, _PL, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
     "spx_eval_check_classes": (C.c_int, [C.POINTER(_I), _I, _I]),

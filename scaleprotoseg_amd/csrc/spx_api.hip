@@ -641,6 +641,47 @@ int spx_ce_bwd(const float* logits, const float* lse, const int32_t* labels, con
     return hip_status(spx_launch_ce_bwd(logits, lse, labels, coef, M, K, d_logits, (hipStream_t)stream), "spx_ce_bwd");
 }
 
+// segmented cross entropy: the table is checked on every call (it is all the kernels know about the buffers' sizes)
+static int check_ce_segments(const spx_ce_segments* seg, const char* who) {
+    if (!seg) return fail("%s: NULL segment table", who);
+    if (seg->S < 1 || seg->S > 16) return fail("%s: %d segments (1..16)", who, seg->S);
+    if (seg->off[0] != 0) return fail("%s: off[0] = %lld (must be 0)", who, (long long)seg->off[0]);
+    for (int k = 0; k < seg->S; ++k)
+        if (seg->off[k + 1] <= seg->off[k])
+            return fail("%s: segment %d is empty or the table is not increasing (off %lld .. %lld)", who, k, (long long)seg->off[k],
+                        (long long)seg->off[k + 1]);
+    if (seg->off[seg->S] > (1LL << 40) || spx_ce_seg_blocks(*seg) > 0x7fffffffLL)
+        return fail("%s: %lld rows are too many", who, (long long)seg->off[seg->S]);
+    return 0;
+}
+size_t spx_ce_seg_partials(const spx_ce_segments* seg) {
+    if (check_ce_segments(seg, "spx_ce_seg_partials")) return 0;
+    return (size_t)spx_ce_seg_blocks(*seg) * 4;
+}
+int spx_ce_seg_fwd(const float* logits, const int32_t* labels, const spx_ce_segments* seg, int32_t K, float* lse, int32_t* pred,
+                   float* partials, void* stream) {
+    if (check_ce_segments(seg, "spx_ce_seg_fwd")) return 1;
+    if (!logits || !labels || !lse || !partials) return fail("spx_ce_seg_fwd: NULL buffer");
+    if (K < 1) return fail("spx_ce_seg_fwd: K = %d", K);
+    return hip_status(spx_launch_ce_seg_fwd(logits, labels, *seg, K, lse, pred, partials, (hipStream_t)stream), "spx_ce_seg_fwd");
+}
+int spx_ce_seg_finish(const float* partials, const spx_ce_segments* seg, float* losses, float* mean, float* count, int32_t* valid,
+                      int32_t* correct, void* stream) {
+    if (check_ce_segments(seg, "spx_ce_seg_finish")) return 1;
+    if (!partials || !losses || !mean || !count || !valid || !correct) return fail("spx_ce_seg_finish: NULL buffer");
+    return hip_status(spx_launch_ce_seg_finish(partials, *seg, losses, mean, count, valid, correct, (hipStream_t)stream),
+                      "spx_ce_seg_finish");
+}
+int spx_ce_seg_bwd(const float* logits, const float* lse, const int32_t* labels, const spx_ce_segments* seg, const float* count,
+                   const float* g_losses, const float* g_mean, int32_t K, float* d_logits, void* stream) {
+    if (check_ce_segments(seg, "spx_ce_seg_bwd")) return 1;
+    if (!logits || !lse || !labels || !count || !d_logits) return fail("spx_ce_seg_bwd: NULL buffer");
+    if (K < 1 || seg->off[seg->S] > (0x7fffffffLL * 256 - 255) / K)                 /* the grid: one thread per element */
+        return fail("spx_ce_seg_bwd: bad sizes (M=%lld K=%d)", (long long)seg->off[seg->S], K);
+    return hip_status(spx_launch_ce_seg_bwd(logits, lse, labels, *seg, count, g_losses, g_mean, K, d_logits, (hipStream_t)stream),
+                      "spx_ce_seg_bwd");
+}
+
 size_t spx_bank_bwd_workspace_bytes(const spx_plan* pl, int32_t B, int32_t HW) {
     const int nsplit = spx_bank_bwd_nsplit(*pl, B, HW);
     return spx_bank_bwd_ws_floats(*pl, nsplit) * sizeof(float);

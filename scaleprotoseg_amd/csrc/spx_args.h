@@ -215,6 +215,14 @@ hipError_t spx_launch_ce_fwd(const float* logits, const int32_t* labels, long lo
                              float* partials, hipStream_t s);
 hipError_t spx_launch_ce_bwd(const float* logits, const float* lse, const int32_t* labels, const float* coef, long long M, int K,
                              float* d_logits, hipStream_t s);
+// segmented cross entropy (spx_ce_seg_*): the table by value
+long long spx_ce_seg_blocks(const spx_ce_segments& seg);
+hipError_t spx_launch_ce_seg_fwd(const float* logits, const int32_t* labels, const spx_ce_segments& seg, int K, float* lse, int32_t* pred,
+                                 float* partials, hipStream_t s);
+hipError_t spx_launch_ce_seg_finish(const float* partials, const spx_ce_segments& seg, float* losses, float* mean, float* count,
+                                    int32_t* valid, int32_t* correct, hipStream_t s);
+hipError_t spx_launch_ce_seg_bwd(const float* logits, const float* lse, const int32_t* labels, const spx_ce_segments& seg,
+                                 const float* count, const float* g_losses, const float* g_mean, int K, float* d_logits, hipStream_t s);
 hipError_t spx_launch_exp(const float* x, const float* g, const float* y, float* out, long long n, hipStream_t s);
 hipError_t spx_launch_kld_lse(const uint32_t* keys, const uint64_t* ssum_fx, int n, float* lse, const uint32_t* range_keys, int HW,
                               double* scale_out, hipStream_t s);

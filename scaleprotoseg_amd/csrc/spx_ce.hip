@@ -425,6 +425,175 @@ hipError_t spx_launch_ce_bwd(const float* logits, const float* lse, const int32_
     return hipGetLastError();
 }
 
+// ---- segmented cross entropy: S <= 16 row ranges [off_k, off_{k+1}) of one [M, K] logits tensor, each with its own mean and
+// its own backward coefficient, in one forward, one finish and one backward launch (the packed MSC training maps: four losses
+// of one launch's logits).  The table travels by value in the kernel arguments (a captured step has one layout).  Every
+// segment's numbers are bit for bit what the stand-alone kernels above give on its contiguous slice: workgroups are assigned
+// per segment (block j of segment k starts at row off_k + 256 j, so a pixel sits in the lane the stand-alone launch would
+// give it and no wave holds pixels of two segments), the per-pixel arithmetic and the wave butterfly are
+// spx_ce_fwd_kernel's, and the finish walks a segment's partials in spx_ce_finish_kernel's order.
+__device__ __forceinline__ long long ce_seg_blocks(const spx_ce_segments& seg, int k) {
+    return (seg.off[k + 1] - seg.off[k] + SPX_CE_THREADS - 1) / SPX_CE_THREADS;
+}
+// per-wave (loss sum, valid count, correct count) triples; correct = valid and pred == label
+__global__ __launch_bounds__(SPX_CE_THREADS) void spx_ce_seg_fwd_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                                                      const spx_ce_segments seg, int K, float* __restrict__ lse_out,
+                                                                      int32_t* __restrict__ pred, float* __restrict__ partials) {
+    long long b = blockIdx.x;
+    int k = 0;
+    for (; k < seg.S - 1; ++k) {                         // the block's segment: a prefix walk over the table (uniform)
+        const long long nb = ce_seg_blocks(seg, k);
+        if (b < nb) break;
+        b -= nb;
+    }
+    const long long m_ = seg.off[k] + b * SPX_CE_THREADS + threadIdx.x;
+    const bool in = m_ < seg.off[k + 1];
+    const float* row = logits + (in ? m_ : 0) * K;
+    const int lab = in ? labels[m_] : -1;
+    const bool valid = in && (unsigned)lab < (unsigned)K;
+    float mx = -3.0e38f;
+    int best = 0x7fffffff;
+    for (int c = 0; c < K; ++c) ce_best(row[c], c, mx, best);
+    float ssum = 0.0f;
+    for (int c = 0; c < K; ++c) ssum += ce_exp(row[c] - mx);
+    const float lse = mx + ce_log(ssum);
+    if (in) {
+        lse_out[m_] = lse;
+        if (pred) pred[m_] = best;
+    }
+    float lossv = valid ? lse - row[lab] : 0.0f, cnt = valid ? 1.0f : 0.0f, hit = (valid && best == lab) ? 1.0f : 0.0f;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        lossv += __shfl_xor(lossv, off);
+        cnt += __shfl_xor(cnt, off);
+        hit += __shfl_xor(hit, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        float* const pp = partials + ((size_t)blockIdx.x * (SPX_CE_THREADS / 64) + (threadIdx.x >> 6)) * 3;
+        pp[0] = lossv;
+        pp[1] = cnt;
+        pp[2] = hit;
+    }
+}
+// (loss sum, fp32 count, valid, correct) of n triples in spx_ce_finish_kernel's order (thread-strided in two accumulators, wave
+// butterfly, waves in order); the two integer counts with integer adds.  Every thread returns; thread 0 holds the totals.
+__device__ __forceinline__ void ce_seg_sum(const float* __restrict__ tr, long long n, float (*red)[SPX_CE_THREADS / 64],
+                                           int (*redi)[SPX_CE_THREADS / 64], float& st, float& ct, int& vt, int& ht) {
+    float s0 = 0.0f, s1 = 0.0f, c0 = 0.0f, c1 = 0.0f;
+    int v = 0, h = 0;
+    long long i = threadIdx.x;
+    for (; i + SPX_CE_THREADS < n; i += 2 * SPX_CE_THREADS) {
+        const float* const a = tr + i * 3;
+        const float* const b = tr + (i + SPX_CE_THREADS) * 3;
+        const float ax = a[0], ay = a[1], az = a[2], bx = b[0], by = b[1], bz = b[2];
+        s0 += ax; c0 += ay; s1 += bx; c1 += by;
+        v += (int)ay + (int)by;
+        h += (int)az + (int)bz;
+    }
+    if (i < n) {
+        const float* const a = tr + i * 3;
+        const float ax = a[0], ay = a[1], az = a[2];
+        s0 += ax; c0 += ay;
+        v += (int)ay;
+        h += (int)az;
+    }
+    float sv = s0 + s1, cv = c0 + c1;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        sv += __shfl_xor(sv, off);
+        cv += __shfl_xor(cv, off);
+        v += __shfl_xor(v, off);
+        h += __shfl_xor(h, off);
+    }
+    __syncthreads();                                    // the previous call's totals have been read
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = sv;
+        red[1][threadIdx.x >> 6] = cv;
+        redi[0][threadIdx.x >> 6] = v;
+        redi[1][threadIdx.x >> 6] = h;
+    }
+    __syncthreads();
+    st = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    ct = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+    vt = ((redi[0][0] + redi[0][1]) + redi[0][2]) + redi[0][3];
+    ht = ((redi[1][0] + redi[1][1]) + redi[1][2]) + redi[1][3];
+}
+// one workgroup per segment: losses[k] = sum / count (0 / 0 = nan), the fp32 divisor and the two int32 counts.  Workgroup 0
+// also walks the other segments in turn - the same sums in the same order, so the same bits - and writes
+// mean = (((l_0 + l_1) + l_2) + ...) / S: no ticket, no atomics, no workspace.
+__global__ __launch_bounds__(SPX_CE_THREADS) void spx_ce_seg_finish_kernel(const float* __restrict__ partials, const spx_ce_segments seg,
+                                                                         float* __restrict__ losses, float* __restrict__ mean,
+                                                                         float* __restrict__ count, int32_t* __restrict__ valid,
+                                                                         int32_t* __restrict__ correct) {
+    __shared__ float red[2][SPX_CE_THREADS / 64];
+    __shared__ int redi[2][SPX_CE_THREADS / 64];
+    const int mine = blockIdx.x;
+    long long first = 0;                                // the segment's first triple: 4 per block of the segments before it
+    float acc = 0.0f;
+    for (int k = 0; k < seg.S; ++k) {
+        const long long n = ce_seg_blocks(seg, k) * (SPX_CE_THREADS / 64);
+        if (k == mine || mine == 0) {
+            float st, ct;
+            int vt, ht;
+            ce_seg_sum(partials + first * 3, n, red, redi, st, ct, vt, ht);
+            const float l = st / ct;
+            if (k == mine && threadIdx.x == 0) {
+                losses[k] = l;
+                count[k] = ct;
+                valid[k] = vt;
+                correct[k] = ht;
+            }
+            acc = k == 0 ? l : acc + l;
+        }
+        first += n;
+    }
+    if (mine == 0 && threadIdx.x == 0) mean[0] = acc / (float)seg.S;
+}
+// d_logits[m, :] = c_k (softmax - onehot) on the valid pixels of segment k, 0 on the ignored ones;
+// c_k = (g_losses[k] + g_mean / S) / count_k, a NULL gradient reading as 0
+__global__ __launch_bounds__(SPX_CE_THREADS) void spx_ce_seg_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
+                                                                      const int32_t* __restrict__ labels, const spx_ce_segments seg,
+                                                                      const float* __restrict__ count, const float* __restrict__ g_losses,
+                                                                      const float* __restrict__ g_mean, int K,
+                                                                      float* __restrict__ d_logits) {
+    const long long i = (long long)blockIdx.x * SPX_CE_THREADS + threadIdx.x;
+    if (i >= seg.off[seg.S] * K) return;
+    const long long m_ = i / K;
+    const int c = (int)(i - m_ * K);
+    int k = 0;
+    for (int j = 1; j < seg.S; ++j) k += m_ >= seg.off[j] ? 1 : 0;
+    const float gl = g_losses ? g_losses[k] : 0.0f;
+    const float gm = g_mean ? g_mean[0] / (float)seg.S : 0.0f;
+    const float coef = (gl + gm) / count[k];
+    const int lab = labels[m_];
+    const bool valid = (unsigned)lab < (unsigned)K;
+    d_logits[i] = valid ? coef * (ce_exp(logits[i] - lse[m_]) - (c == lab ? 1.0f : 0.0f)) : 0.0f;
+}
+long long spx_ce_seg_blocks(const spx_ce_segments& seg) {
+    long long n = 0;
+    for (int k = 0; k < seg.S; ++k) n += (seg.off[k + 1] - seg.off[k] + SPX_CE_THREADS - 1) / SPX_CE_THREADS;
+    return n;
+}
+hipError_t spx_launch_ce_seg_fwd(const float* logits, const int32_t* labels, const spx_ce_segments& seg, int K, float* lse, int32_t* pred,
+                                 float* partials, hipStream_t s) {
+    hipLaunchKernelGGL(spx_ce_seg_fwd_kernel, dim3((unsigned)spx_ce_seg_blocks(seg)), dim3(SPX_CE_THREADS), 0, s, logits, labels, seg, K,
+                       lse, pred, partials);
+    return hipGetLastError();
+}
+hipError_t spx_launch_ce_seg_finish(const float* partials, const spx_ce_segments& seg, float* losses, float* mean, float* count,
+                                    int32_t* valid, int32_t* correct, hipStream_t s) {
+    hipLaunchKernelGGL(spx_ce_seg_finish_kernel, dim3((unsigned)seg.S), dim3(SPX_CE_THREADS), 0, s, partials, seg, losses, mean, count,
+                       valid, correct);
+    return hipGetLastError();
+}
+hipError_t spx_launch_ce_seg_bwd(const float* logits, const float* lse, const int32_t* labels, const spx_ce_segments& seg,
+                                 const float* count, const float* g_losses, const float* g_mean, int K, float* d_logits, hipStream_t s) {
+    const long long n = seg.off[seg.S] * K;
+    hipLaunchKernelGGL(spx_ce_seg_bwd_kernel, dim3((unsigned)((n + SPX_CE_THREADS - 1) / SPX_CE_THREADS)), dim3(SPX_CE_THREADS), 0, s, logits,
+                       lse, labels, seg, count, g_losses, g_mean, K, d_logits);
+    return hipGetLastError();
+}
+
 // g = exp(units) of the grouping head as a stand-alone elementwise kernel (compute_group on activations that did not come
 // out of the fused forward, and the heads wider than the fused kernels; segmentation/model/model_multiscale_group.py:283-303):
 // forward out = exp(x); backward (g, y given) out = g * y.

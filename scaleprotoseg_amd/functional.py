@@ -133,6 +133,98 @@ class _CrossEntropyFn(torch.autograd.Function):
 
 
 @dataclass
+class SegmentedCE:
+    """Cross entropy of S row segments of one [M, K] logits tensor (``segmented_cross_entropy``): ``losses`` fp32 [S] (segment
+    k's mean over its non-ignored rows; NaN without one) and ``mean`` fp32 [] = (((l_0 + l_1) + l_2) + ...) / S, both
+    differentiable; ``valid`` / ``correct`` int32 [S] (non-ignored rows; those whose argmax is the label); ``pred`` int32 [M]
+    (argmax class) and the ``labels`` int32 [M] it was computed for; ``offsets`` the S + 1 row bounds."""
+
+    losses: torch.Tensor
+    mean: torch.Tensor
+    valid: torch.Tensor
+    correct: torch.Tensor
+    pred: torch.Tensor
+    labels: torch.Tensor
+    offsets: Tuple[int, ...] = ()
+
+
+def ce_segment_table(offsets: Sequence[int], M: Optional[int] = None) -> "_lib.SpxCeSegments":
+    """The kernels' by-value table of ``offsets`` = (0, off_1, ..., off_S = M): checked here, before any launch."""
+    offs = [int(o) for o in offsets]
+    S = len(offs) - 1
+    if not 1 <= S <= _lib.SPX_CE_MAX_SEGMENTS:
+        raise SpxError(f"segmented cross entropy: {S} segments (1 to {_lib.SPX_CE_MAX_SEGMENTS})")
+    if offs[0] != 0 or (M is not None and offs[-1] != M):
+        raise SpxError(f"segmented cross entropy: offsets run from {offs[0]} to {offs[-1]} (0 to the {M} logit rows)")
+    for k in range(S):
+        if offs[k + 1] <= offs[k]:
+            raise SpxError(f"segmented cross entropy: segment {k} is empty or out of order (rows {offs[k]} to {offs[k + 1]})")
+    seg = _lib.SpxCeSegments()
+    seg.S = S
+    for k, o in enumerate(offs):
+        seg.off[k] = o
+    return seg
+
+
+class _SegmentedCrossEntropyFn(torch.autograd.Function):
+    """Three launches forward (spx_ce_seg_fwd, spx_ce_seg_finish) and one backward (spx_ce_seg_bwd) for all segments; the
+    upstream gradients of ``losses`` and ``mean`` are read on the device.  Nothing here reads a value back to the host."""
+
+    @staticmethod
+    def forward(ctx, logits, lab, seg):
+        lib = _lib.load()
+        K = int(logits.shape[-1])
+        lg = logits.detach()
+        M, S, dev = int(lg.shape[0]), int(seg.S), lg.device
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        lse, pred = torch.empty((M,), **f32), torch.empty((M,), **i32)
+        partials = torch.empty((lib.spx_ce_seg_partials(C.byref(seg)), 3), **f32)
+        s = _lib.stream_ptr()
+        _lib.check(lib.spx_ce_seg_fwd(_lib.ptr(lg), _lib.ptr(lab), C.byref(seg), K, _lib.ptr(lse), _lib.ptr(pred), _lib.ptr(partials), s))
+        # separate allocations: the losses and the mean become autograd OUTPUTS, the divisor is kept by the node
+        losses, mean, count = torch.empty((S,), **f32), torch.empty((), **f32), torch.empty((S,), **f32)
+        valid, correct = torch.empty((S,), **i32), torch.empty((S,), **i32)
+        _lib.check(lib.spx_ce_seg_finish(_lib.ptr(partials), C.byref(seg), _lib.ptr(losses), _lib.ptr(mean), _lib.ptr(count),
+                                         _lib.ptr(valid), _lib.ptr(correct), s))
+        ctx.save_for_backward(lg, lse, lab, count)
+        ctx.seg = seg
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(valid, correct, pred)
+        return losses, mean, valid, correct, pred
+
+    @staticmethod
+    def backward(ctx, g_losses, g_mean, *_):
+        if g_losses is None and g_mean is None:
+            return None, None, None
+        lg, lse, lab, count = ctx.saved_tensors
+        gl = g_losses.float().contiguous() if g_losses is not None else None
+        gm = g_mean.float().reshape(1).contiguous() if g_mean is not None else None
+        dl = torch.empty_like(lg)
+        _lib.check(_lib.load().spx_ce_seg_bwd(_lib.ptr(lg), _lib.ptr(lse), _lib.ptr(lab), C.byref(ctx.seg), _lib.ptr(count),
+                                              _lib.ptr(gl), _lib.ptr(gm), int(lg.shape[1]), _lib.ptr(dl), _lib.stream_ptr()))
+        return dl, None, None
+
+
+def segmented_cross_entropy(logits: torch.Tensor, labels0: torch.Tensor, offsets: Sequence[int]) -> SegmentedCE:
+    """Pixel-wise cross entropy of the row segments [offsets[k], offsets[k+1]) of ``logits`` [M, K] (fp32, contiguous, on the
+    GPU), each with its own mean: one forward, one finish and one backward launch for up to 16 segments
+    (csrc/spx_ce.hip: spx_ce_seg_*).  ``labels0`` [M]: class 0..K-1, anything else ignored; ``offsets``: host ints, 0 first, M
+    last, strictly increasing.  Per segment the values, counts and gradients carry the bits ``cross_entropy_from_logits``
+    gives on the contiguous slice."""
+    _lib.require_gpu(logits, "segmented cross entropy: logits")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.shape[1] < 1:
+        raise SpxError(f"segmented cross entropy: logits must be a contiguous fp32 [M, K], got {logits.dtype} {tuple(logits.shape)} "
+                       f"with strides {tuple(logits.stride())}")
+    M = int(logits.shape[0])
+    seg = ce_segment_table(offsets, M)
+    if labels0.numel() != M:
+        raise SpxError(f"segmented cross entropy: {labels0.numel()} labels for {M} logit rows")
+    lab = labels0.to(device=logits.device, dtype=torch.int32).reshape(-1).contiguous()
+    losses, mean, valid, correct, pred = _SegmentedCrossEntropyFn.apply(logits, lab, seg)
+    return SegmentedCE(losses, mean, valid, correct, pred, lab, tuple(int(o) for o in offsets))
+
+
+@dataclass
 class ClassGather:
     """Class-gathered distance mode: per pixel, only the distances to its own class's prototypes.
 

@@ -21,7 +21,7 @@ from . import _gathered, _lib
 from ._cache import cached
 from ._gathered import ClassDistances, Gathered, class_slot_table, gather_class_distances, slot_scale_table  # noqa: F401
 from ._lib import SpxError
-from .functional import cross_entropy_from_logits
+from .functional import SegmentedCE, cross_entropy_from_logits, segmented_cross_entropy, shifted_labels_i32
 
 
 class PixelWiseCrossEntropyLoss(nn.Module):
@@ -56,6 +56,75 @@ class PixelWiseCrossEntropyLoss(nn.Module):
         correct = fused.pred.reshape(-1).to(labels0.dtype) == labels0
         mask = (labels0 != self.ignore_index).nonzero().squeeze()                             # loss.py:43-46
         return fused.loss, correct[mask]
+
+
+class SegmentedCrossEntropy(nn.Module):
+    """The cross entropy of every segment of an MSC training step in three launches (module_multiscale.py:232-310 calls
+    ``PixelWiseCrossEntropyLoss`` once per map: three launches, a division and - with ``return_correct`` - a ``nonzero()`` host
+    sync each).  ``forward(logits, targets)`` takes the forward's per-segment logits ``[o[0] for o in outputs]`` ([..., K] each)
+    and the list of their targets (0 = void, 1..K, ``ignore_index`` as in ``PixelWiseCrossEntropyLoss``) and returns a
+    ``SegmentedCE``: ``losses`` [S] and ``mean`` [] (differentiable), ``valid`` / ``correct`` int32 [S] - the reference's
+    ``correct.shape[0]`` and ``sum(correct)`` as device counters - ``pred`` and ``labels`` int32 [M].  Nothing reads the host, so
+    the step stays capturable.
+
+    Segments of ONE packed forward (``forward_from_conv_features(PackedMaps)``: every segment's logits carry ``spx_packed``)
+    run on the packed [M, K] logits as they are and send their gradient straight to them; any other list is reshaped and
+    concatenated once.  Up to 16 segments, none empty; GPU fp32 logits only - anything else raises ``SpxError``."""
+
+    def __init__(self, ignore_index: int = 255) -> None:
+        super().__init__()
+        self.ignore_index = ignore_index
+
+    @staticmethod
+    def _packed_base(logits):
+        """(packed logits [M, K], layout) when ``logits`` are the segments of one packed forward, in order and unedited."""
+        tags = [getattr(l, "spx_packed", None) for l in logits]
+        if any(t is None for t in tags):
+            return None
+        base, layout = tags[0][0], tags[0][1]
+        if len(layout) != len(tags) or base.dim() != 2 or base.dtype != torch.float32 or not base.is_contiguous():
+            return None
+        for k, (t, l) in enumerate(zip(tags, logits)):
+            if t[0] is not base or t[1] is not layout or t[2] != k or t[3] != base._version or l._version != t[3]:
+                return None
+        return base, layout
+
+    def forward(self, logits, targets) -> SegmentedCE:
+        who = "SegmentedCrossEntropy"
+        if isinstance(logits, torch.Tensor) or isinstance(targets, torch.Tensor):
+            raise SpxError(f"{who}: a list of per-segment logits and the list of their targets")
+        logits, targets = list(logits), list(targets)
+        S = len(logits)
+        if not 1 <= S <= _lib.SPX_CE_MAX_SEGMENTS:
+            raise SpxError(f"{who}: {S} segments (1 to {_lib.SPX_CE_MAX_SEGMENTS})")
+        if len(targets) != S:
+            raise SpxError(f"{who}: {len(targets)} target maps for {S} segments")
+        K = int(logits[0].shape[-1]) if logits[0].dim() else 0
+        for k, (l, t) in enumerate(zip(logits, targets)):
+            _lib.require_gpu(l, f"{who}: logits[{k}]")
+            if l.dtype != torch.float32:
+                raise SpxError(f"{who}: logits[{k}] are {l.dtype}; the kernels take fp32")
+            if l.dim() < 1 or int(l.shape[-1]) != K or K < 1:
+                raise SpxError(f"{who}: logits[{k}] {tuple(l.shape)} do not end in the {K} classes of logits[0]")
+            if l.numel() == 0:
+                raise SpxError(f"{who}: segment {k} is empty")
+            if tuple(t.shape) != tuple(l.shape[:-1]):
+                raise SpxError(f"{who}: targets[{k}] must be {tuple(l.shape[:-1])} (the segment's pixels), got {tuple(t.shape)}")
+        packed = self._packed_base(logits)
+        if packed is not None:
+            base, layout = packed
+            offsets = tuple(layout.offsets) + (layout.M,)
+            raw = layout.pack_labels(targets).reshape(-1)
+        else:
+            base = torch.cat([l.reshape(-1, K) for l in logits]) if S > 1 else logits[0].reshape(-1, K).contiguous()
+            offsets = [0]
+            for l in logits:
+                offsets.append(offsets[-1] + l.numel() // K)
+            raw = torch.cat([t.reshape(-1) for t in targets]) if S > 1 else targets[0].reshape(-1)
+        labels0 = shifted_labels_i32(raw, base.device)                                        # loss.py:32, one launch
+        if self.ignore_index is not None and 0 <= self.ignore_index < K:
+            labels0 = torch.where(labels0 == self.ignore_index, torch.full_like(labels0, -1), labels0)
+        return segmented_cross_entropy(base, labels0, offsets)
 
 
 def _kld_segment_passes(lib, v, lab, K, Wk, s):
@@ -215,6 +284,8 @@ class KLDLossGroup(KLDLoss):
     def _gathered(self, list_group_activation, target_labels: torch.Tensor) -> Gathered:
         proj, table = self._class_tables()
         dev = (list_group_activation if isinstance(list_group_activation, torch.Tensor) else list_group_activation[0]).device
+        # (the projection table on the device once, not a host copy per call: the loss stays legal inside a captured step)
+        proj = cached(self, "_proj_dev_cache", (proj,), (str(dev),), lambda: proj.to(dev))
         return _gathered.from_groups(list_group_activation, target_labels, proj, self._table_on(table, dev))
 
     def forward(self, list_group_activation, target_labels: torch.Tensor) -> torch.Tensor:       # the reference's argument names

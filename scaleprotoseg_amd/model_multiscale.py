@@ -460,6 +460,8 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
             logits = wide_linear(act, self.last_layer.weight)
         n = len(lay)
         logits_k = [t.reshape(lay.B, h, w, -1) for t, (h, w) in zip(lay.split_rows(logits), lay.grids)]
+        for k, l in enumerate(logits_k):            # segment k of ONE packed forward: SegmentedCrossEntropy runs on ``logits`` as it is
+            l.spx_packed = (logits, lay, k, logits._version)
         acts_k = lay.split_rows(act) if return_activations else [None] * n
         dists_k = [None] * n
         if want_dist:

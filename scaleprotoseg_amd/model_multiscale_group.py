@@ -23,6 +23,7 @@ from .functional import (MAX_FUSED_HEAD_ROWS, MAX_FUSED_TAIL_CLASSES, GroupTable
                          group_dense, group_exp, invalidate_pack_cache, proto_head_forward, shifted_labels_i32, wide_group_tail,
                          wide_linear)
 from .model_multiscale import _PrototypeBankMixin, _build_add_on, _first_add_on_channels
+from .msc import PackedMaps
 from .utils import projection_simplex_sort, projection_simplex_sort_
 
 
@@ -214,6 +215,8 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         """Same return-tuple rules as model_multiscale_group.py:404-452.  Extension: ``ce_target`` ([B, H, W] at the latent
         resolution, 0 = void, 1..K) computes the pixel-wise cross entropy in the kernel that produces the logits and hangs
         it on the returned logits (``logits.spx_ce``), exactly as the prototype-phase module does."""
+        if isinstance(conv_features, PackedMaps):
+            return self._forward_packed(conv_features, return_activations, return_distances, ce_target)
         if isinstance(conv_features, list):
             return [self.forward_from_conv_features(c) for c in conv_features]
         if not (hasattr(self, "patch_classification") and self.patch_classification):
@@ -293,6 +296,82 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         if return_activations and return_distances:
             return logits, dist, act
         return logits, dist
+
+    def _forward_packed(self, pk: PackedMaps, return_activations, return_distances, ce_target):
+        """The four training maps on one pixel axis (``pk.features`` [1, C, 1, M]; module_multiscale_group_train.py:232,
+        forward :396-402): ONE launch of the distance kernel for all segments, then the head branch this bank takes on a single
+        map.  Units, group activations and logits are per-pixel quantities like the distances: logits [B, h_k, w_k, K],
+        activations, units and group activations are row slices (``split_with_sizes``: one backward assembles each packed
+        gradient), distances [B, P, h_k, w_k] strided views.  Every segment's activations carry ``spx_group`` with ITS rows of
+        the one [M, U] tensor - ``compute_group`` returns views of it and a KLD gradient on them enters the one backward as part
+        of dUnits - and every segment's logits carry ``spx_group_wd`` and ``spx_packed`` (``SegmentedCrossEntropy`` then runs
+        on the packed logits as they are)."""
+        who = "forward_from_conv_features(PackedMaps)"
+        if not (hasattr(self, "patch_classification") and self.patch_classification):
+            raise Exception("Original Prototype Network Implementation")
+        if ce_target is not None:
+            raise SpxError(f"{who}: ce_target is refused - the fused cross entropy has one mean and one backward coefficient per "
+                           "launch, the objective one per segment (module_multiscale_group_train.py:232-310); call "
+                           "SegmentedCrossEntropy on the segments' logits")
+        if self.scale_head is not None:
+            raise SpxError(f"{who}: a scale_head chains launches per scale and has no packed form")
+        if callable(self.prototype_activation_function):
+            raise SpxError(f"{who}: a callable similarity has no packed form ('log' or 'linear')")
+        self._check_fusable()
+        lay = pk.layout
+        wd = self._dense_group_matrix()
+        wg = self.last_layer_group.weight
+        rows, k2 = int(wd.shape[0]), int(wg.shape[0])
+        want_dist = return_distances or not return_activations
+        kw = dict(want_distances=want_dist, epsilon=self.epsilon, activation=self.prototype_activation_function)
+        units = g = None
+        if rows <= MAX_FUSED_HEAD_ROWS and k2 <= MAX_FUSED_TAIL_CLASSES:
+            out = proto_head_forward(pk.features, self.prototype_vectors, wd, self._layout(rows), want_activations=return_activations,
+                                     group_tail=wg, **kw)
+            logits, dist, act = out[:3]
+            g = out[-1] if act is not None else None          # exp(units) [M, U], written by the kernel
+        elif rows <= MAX_FUSED_HEAD_ROWS:
+            units, dist, act = proto_head_forward(pk.features, self.prototype_vectors, wd, self._layout(rows),
+                                                  want_activations=return_activations, **kw)
+            logits = wide_group_tail(units, wg)
+        else:
+            _, dist, act = proto_head_forward(pk.features, self.prototype_vectors, None, self._layout(1), want_activations=True, **kw)
+            units = wide_linear(act, wd)
+            logits = wide_group_tail(units, wg)
+        n = len(lay)
+        versions = tuple(gp.weight._version for gp in self.group_projection)
+        logits_k = [t.reshape(lay.B, h, w, -1) for t, (h, w) in zip(lay.split_rows(logits), lay.grids)]
+        for k, l in enumerate(logits_k):
+            l.spx_group_wd = (wd, self, versions)
+            l.spx_packed = (logits, lay, k, logits._version)
+        acts_k = [None] * n
+        if return_activations:
+            acts_k = lay.split_rows(act)
+            units_k = lay.split_rows(units) if units is not None else [None] * n
+            g_k = lay.split_rows(g) if g is not None else [None] * n
+            for a, u, gg in zip(acts_k, units_k, g_k):
+                a.spx_group = (a._version, u, gg)
+        dists_k = list(lay.split_columns(dist)) if want_dist else [None] * n
+        out = []
+        for l, d, a in zip(logits_k, dists_k, acts_k):
+            if return_activations and not return_distances:
+                out.append((l, a))
+            elif return_activations and return_distances:
+                out.append((l, d, a))
+            else:
+                out.append((l, d))
+        return out
+
+    def forward_packed(self, x, **kwargs):
+        """``forward`` with MSC's training maps packed (after ``fuse_feature_epilogue(dtype)``): in training
+        ``features.fused_packed(x, "sigmoid", dtype)`` - the four maps in one launch - and the packed forward above, one tuple
+        per segment; in eval, or with ``scales = []``, exactly ``forward(x, **kwargs)``.  (``fuse_feature_epilogue(dtype,
+        packed=True)`` stays refused for this class; this method is the opt-in.)"""
+        if self._feature_epilogue is None:
+            raise SpxError("forward_packed: call fuse_feature_epilogue(dtype) first (features must be scaleprotoseg_amd.MSC)")
+        if not self.training or len(self.features.scales) == 0:
+            return self.forward(x, **kwargs)
+        return self.forward_from_conv_features(self.features.fused_packed(x, "sigmoid", self._feature_epilogue), **kwargs)
 
     def prune_prototypes(self, prototypes_to_prune: List[int]):
         """Not in the upstream group class (it receives an already pruned bank by attribute assignment,
