@@ -15,6 +15,11 @@
 //       the descriptor's prefix sums, walks the destination rows and columns whose footprint can hold it (the inverse of s(Y),
 //       widened by one; every candidate is tested with the forward's own index function, so rounding can neither drop nor double
 //       a contribution) and adds g . wy . wx where the saved index names its map, in ascending (Y, X) order.
+//   packed   (spx_msc_pack_fwd / _bwd_kernel)   the K maps and their maximum side by side on one pixel axis; see below.
+// Every rule has ONE statement, shared by the plain and the packed kernels: the candidate and the rule of the maximum (msc_tap,
+// msc_takes_over), the activation and the stores (msc_sigmoid, msc_store_vector, msc_store), and in the backward the upstream
+// term, the decode of a source element and the term of the maximum (msc_upstream, msc_source, msc_max_term).  On the host:
+// msc_fill, msc_grad_offsets, msc_channel_chunk.
 // No LDS, no atomics, no workspace.
 #include "spx_args.h"
 #include "spx_common.h"
@@ -22,11 +27,15 @@
 #define MSC_THREADS 256
 #define MSC_VEC 4
 
-struct SpxMscArgs {
+// what every kernel's arguments begin with (msc_fill; gofs: msc_grad_offsets)
+struct SpxMscCommon {
     spx_msc d;
     float rh[SPX_MSC_MAX_MAPS], rw[SPX_MSC_MAX_MAPS];   // float(h_k) / float(H), float(w_k) / float(W)
     long long gofs[SPX_MSC_MAX_MAPS + 1];               // backward: prefix sums of the elements of the maps that get a gradient
-    int H, W, groups, cchunk;                           // forward: groups of a row (ceil(W / 4) + 1), channels per block
+    int H, W;
+};
+struct SpxMscArgs : SpxMscCommon {
+    int groups, cchunk;                                 // forward: groups of a row (ceil(W / 4) + 1), channels per block
     int out_mis;                                        // forward: (out address / element size) & 3
 };
 
@@ -46,6 +55,23 @@ __device__ __forceinline__ float msc_load(const void* p, bool bf16, long long i)
 __device__ __forceinline__ uint16_t msc_bf16_bits(float v) {
     const __bf16 h = (__bf16)v;                          // round to nearest even
     return *(const uint16_t*)&h;
+}
+__device__ __forceinline__ void msc_store(void* p, bool bf16, long long i, float v) {
+    if (bf16) ((uint16_t*)p)[i] = msc_bf16_bits(v);
+    else ((float*)p)[i] = v;
+}
+// the bilinear candidate of a scaled map: rows r0, r1 (their first elements), columns j0, j1, weights ly, lx
+__device__ __forceinline__ float msc_tap(const void* data, bool bf16, long long r0, long long r1, int j0, int j1, float ly, float lx) {
+    const float v00 = msc_load(data, bf16, r0 + j0), v01 = msc_load(data, bf16, r0 + j1);
+    const float v10 = msc_load(data, bf16, r1 + j0), v11 = msc_load(data, bf16, r1 + j1);
+    return (1.0f - ly) * ((1.0f - lx) * v00 + lx * v01) + ly * ((1.0f - lx) * v10 + lx * v11);
+}
+// torch.max(dim=0): a larger value wins, the first of equals stays, the first NaN wins and stays
+__device__ __forceinline__ bool msc_takes_over(float u, float v) { return u > v || (u != u && v == v); }
+__device__ __forceinline__ float msc_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+__device__ __forceinline__ void msc_sigmoid(float (&v)[MSC_VEC]) {
+#pragma unroll
+    for (int j = 0; j < MSC_VEC; ++j) v[j] = msc_sigmoid(v[j]);
 }
 
 // one thread's group [xs, xs + 4) of a row of the full-scale map (first element p0 + xs ... clipped to [xb, xe)): a vector
@@ -67,6 +93,18 @@ __device__ __forceinline__ void msc_load_vector(const void* data, long long p0, 
         v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
     }
 }
+// the cast and the store of a whole group at element o of out, where a vector may go (8 bytes for bf16, 16 for fp32)
+template <bool OUT_BF16>
+__device__ __forceinline__ void msc_store_vector(void* out, long long o, const float (&v)[MSC_VEC]) {
+    if (OUT_BF16) {
+        uint2 r;
+        r.x = (uint32_t)msc_bf16_bits(v[0]) | ((uint32_t)msc_bf16_bits(v[1]) << 16);
+        r.y = (uint32_t)msc_bf16_bits(v[2]) | ((uint32_t)msc_bf16_bits(v[3]) << 16);
+        *(uint2*)((uint16_t*)out + o) = r;
+    } else {
+        *(float4*)((float*)out + o) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
 template <bool IN_BF16>
 __device__ __forceinline__ void msc_load_group(const void* data, long long p0, int xs, int xb, int xe, float (&v)[MSC_VEC]) {
     if (msc_group_vector_ok<IN_BF16>(data, p0, xe - xb == MSC_VEC)) {
@@ -81,31 +119,13 @@ template <bool OUT_BF16>
 __device__ __forceinline__ void msc_store_group(void* out, uint8_t* index, int activation, long long o, int xs, int xb, int xe,
                                                 float (&v)[MSC_VEC], const int (&win)[MSC_VEC]) {
     const bool full = xe - xb == MSC_VEC;
-    if (activation == 1) {
-#pragma unroll
-        for (int j = 0; j < MSC_VEC; ++j) v[j] = 1.0f / (1.0f + expf(-v[j]));
-    }
-    if (OUT_BF16) {
-        uint16_t* const q = (uint16_t*)out + o;
-        if (full) {
-            uint2 r;
-            r.x = (uint32_t)msc_bf16_bits(v[0]) | ((uint32_t)msc_bf16_bits(v[1]) << 16);
-            r.y = (uint32_t)msc_bf16_bits(v[2]) | ((uint32_t)msc_bf16_bits(v[3]) << 16);
-            *(uint2*)q = r;
-        } else {
-#pragma unroll
-            for (int j = 0; j < MSC_VEC; ++j)
-                if (xs + j >= xb && xs + j < xe) q[j] = msc_bf16_bits(v[j]);
-        }
+    if (activation == 1) msc_sigmoid(v);
+    if (full) {
+        msc_store_vector<OUT_BF16>(out, o, v);
     } else {
-        float* const q = (float*)out + o;
-        if (full) {
-            *(float4*)q = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
 #pragma unroll
-            for (int j = 0; j < MSC_VEC; ++j)
-                if (xs + j >= xb && xs + j < xe) q[j] = v[j];
-        }
+        for (int j = 0; j < MSC_VEC; ++j)
+            if (xs + j >= xb && xs + j < xe) msc_store(out, OUT_BF16, o + j, v[j]);
     }
     if (index) {
         uint8_t* const q = index + o;
@@ -166,7 +186,6 @@ __global__ __launch_bounds__(MSC_THREADS) void spx_msc_max_fwd_kernel(const SpxM
             const spx_msc_map m = a.d.maps[k];
             const long long pl = (long long)b * m.batch_stride + (long long)c * m.channel_stride;
             const long long r0 = pl + (long long)ri0[k] * m.w, r1 = pl + (long long)ri1[k] * m.w;
-            const float ly = rl[k];
 #pragma unroll
             for (int j = 0; j < MSC_VEC; ++j) {
                 const int X = xs + j;
@@ -174,11 +193,8 @@ __global__ __launch_bounds__(MSC_THREADS) void spx_msc_max_fwd_kernel(const SpxM
                 int j0, j1;
                 float lx;
                 msc_src(a.rw[k], m.w, X, j0, j1, lx);
-                const float v00 = msc_load(m.data, IN_BF16, r0 + j0), v01 = msc_load(m.data, IN_BF16, r0 + j1);
-                const float v10 = msc_load(m.data, IN_BF16, r1 + j0), v11 = msc_load(m.data, IN_BF16, r1 + j1);
-                const float u = (1.0f - ly) * ((1.0f - lx) * v00 + lx * v01) + ly * ((1.0f - lx) * v10 + lx * v11);
-                // torch.max(dim=0): a larger value wins, the first of equals stays, the first NaN wins and stays
-                if (u > v[j] || (u != u && v[j] == v[j])) {
+                const float u = msc_tap(m.data, IN_BF16, r0, r1, j0, j1, rl[k], lx);
+                if (msc_takes_over(u, v[j])) {
                     v[j] = u;
                     win[j] = k;
                 }
@@ -221,21 +237,10 @@ __global__ __launch_bounds__(MSC_THREADS) void spx_msc_act_kernel(const SpxMscAr
             for (int u = 0; u < MSC_ACT_UNROLL; ++u) msc_load_vector<IN_BF16>(m0.data, p0[u], v[u]);
             if (a.d.activation == 1) {
 #pragma unroll
-                for (int u = 0; u < MSC_ACT_UNROLL; ++u)
-#pragma unroll
-                    for (int j = 0; j < MSC_VEC; ++j) v[u][j] = 1.0f / (1.0f + expf(-v[u][j]));
+                for (int u = 0; u < MSC_ACT_UNROLL; ++u) msc_sigmoid(v[u]);
             }
 #pragma unroll
-            for (int u = 0; u < MSC_ACT_UNROLL; ++u) {                            // whole groups: aligned by the anchoring
-                if (OUT_BF16) {
-                    uint2 r;
-                    r.x = (uint32_t)msc_bf16_bits(v[u][0]) | ((uint32_t)msc_bf16_bits(v[u][1]) << 16);
-                    r.y = (uint32_t)msc_bf16_bits(v[u][2]) | ((uint32_t)msc_bf16_bits(v[u][3]) << 16);
-                    *(uint2*)((uint16_t*)a.d.out + e0[u] + xs[u]) = r;
-                } else {
-                    *(float4*)((float*)a.d.out + e0[u] + xs[u]) = make_float4(v[u][0], v[u][1], v[u][2], v[u][3]);
-                }
-            }
+            for (int u = 0; u < MSC_ACT_UNROLL; ++u) msc_store_vector<OUT_BF16>(a.d.out, e0[u] + xs[u], v[u]);   // aligned by the anchoring
             if (a.d.index) {
 #pragma unroll
                 for (int u = 0; u < MSC_ACT_UNROLL; ++u)
@@ -266,35 +271,83 @@ __device__ __forceinline__ void msc_dst_range(float r, int n, int D, int i, int&
     if (i == n - 1 || hi > D - 1) hi = D - 1;
 }
 
-// The gather of source element (i, j) of map k >= 1 (h x w, ratios rh, rw) over the H x W destination pixels whose footprint can
-// hold it and whose index names k, added to acc in ascending (Y, X) order.  Pixel (Y, X) is element gbase + Y W + X of the
-// upstream gradient and of the saved output, and element ibase + Y W + X of the index.
-__device__ __forceinline__ float msc_gather(const spx_msc& d, int k, int h, int w, float rh, float rw, int H, int W, int i, int j,
-                                            long long gbase, long long ibase, float acc) {
-    const bool g16 = d.g_dtype == 0, y16 = d.out_dtype == 0, sig = d.activation == 1;
+// the upstream term at element o of the output: g, under the sigmoid g y (1 - y) at the SAVED y
+__device__ __forceinline__ float msc_upstream(const spx_msc& d, long long o) {
+    float g = msc_load(d.g, d.g_dtype == 0, o);
+    if (d.activation == 1) {
+        const float y = msc_load(d.out, d.out_dtype == 0, o);
+        g = g * (y * (1.0f - y));
+    }
+    return g;
+}
+
+// The source element a backward thread owns: element `local` = ((b C + c) h + i) w + j of map k, the map whose range of the
+// prefix sums holds id (a map without a gradient has an empty range).  off: the first column of every segment (the pack) or null.
+struct MscSource {
+    int k, h, w, off, i, j;
+    float rh, rw;
+    long long local, plane;                             // plane = b * C + c
+    void* grad;
+};
+__device__ __forceinline__ MscSource msc_source(const SpxMscCommon& a, const int* off, long long id) {
+    MscSource s;
+    s.k = s.off = 0;
+    s.h = s.w = 1;
+    s.rh = s.rw = 1.0f;
+    s.local = 0;
+    s.grad = nullptr;
+#pragma unroll
+    for (int q = 0; q < SPX_MSC_MAX_MAPS; ++q) {
+        if (q < a.d.K && id >= a.gofs[q] && id < a.gofs[q + 1]) {
+            s.k = q;
+            s.h = a.d.maps[q].h;
+            s.w = a.d.maps[q].w;
+            s.rh = a.rh[q];
+            s.rw = a.rw[q];
+            if (off) s.off = off[q];
+            s.local = id - a.gofs[q];
+            s.grad = a.d.grads[q];
+        }
+    }
+    s.j = (int)(s.local % s.w);
+    s.i = (int)((s.local / s.w) % s.h);
+    s.plane = s.local / ((long long)s.w * s.h);
+    return s;
+}
+
+// The term of the maximum for source element s: the upstream terms of the H x W destination pixels whose index names map s.k,
+// added to acc in ascending (Y, X) order.  Map 0 is its own pixel.  A scaled map gathers over the pixels whose footprint can
+// hold (i, j), with the forward's weights: acc += g . wy . wx.  Pixel (Y, X) is element gbase + Y W + X of the upstream gradient
+// and of the saved output, and element ibase + Y W + X of the index.  has_own: acc holds the element's own term (the pack);
+// without one, map 0's term is the result as it stands, not 0 + term (a -0 keeps its sign).
+__device__ __forceinline__ float msc_max_term(const SpxMscCommon& a, const MscSource& s, long long gbase, long long ibase, float acc,
+                                              bool has_own) {
+    const spx_msc& d = a.d;
+    const int H = a.H, W = a.W, k = s.k, i = s.i, j = s.j;
+    if (k == 0) {
+        const long long p = (long long)i * W + j;
+        if (d.index && d.index[ibase + p] != 0) return acc;
+        const float g = msc_upstream(d, gbase + p);
+        return has_own ? acc + g : g;
+    }
     int ylo, yhi, xlo, xhi;
-    msc_dst_range(rh, h, H, i, ylo, yhi);
-    msc_dst_range(rw, w, W, j, xlo, xhi);
+    msc_dst_range(s.rh, s.h, H, i, ylo, yhi);
+    msc_dst_range(s.rw, s.w, W, j, xlo, xhi);
     for (int Y = ylo; Y <= yhi; ++Y) {
         int i0, i1;
         float ly;
-        msc_src(rh, h, Y, i0, i1, ly);
+        msc_src(s.rh, s.h, Y, i0, i1, ly);
         const float wy = (i0 == i ? 1.0f - ly : 0.0f) + (i1 == i ? ly : 0.0f);
         if (i0 != i && i1 != i) continue;
         for (int X = xlo; X <= xhi; ++X) {
             int j0, j1;
             float lx;
-            msc_src(rw, w, X, j0, j1, lx);
+            msc_src(s.rw, s.w, X, j0, j1, lx);
             if (j0 != j && j1 != j) continue;
             const long long p = (long long)Y * W + X;
             if (d.index[ibase + p] != k) continue;
             const float wx = (j0 == j ? 1.0f - lx : 0.0f) + (j1 == j ? lx : 0.0f);
-            float g = msc_load(d.g, g16, gbase + p);
-            if (sig) {
-                const float y = msc_load(d.out, y16, gbase + p);
-                g = g * (y * (1.0f - y));
-            }
-            acc += g * wy * wx;
+            acc += msc_upstream(d, gbase + p) * wy * wx;
         }
     }
     return acc;
@@ -302,50 +355,14 @@ __device__ __forceinline__ float msc_gather(const spx_msc& d, int k, int h, int 
 
 __global__ __launch_bounds__(MSC_THREADS) void spx_msc_max_bwd_kernel(const SpxMscArgs a) {
     const long long id = (long long)blockIdx.x * MSC_THREADS + threadIdx.x;
-    const int H = a.H, W = a.W, K = a.d.K, C = a.d.C;
     if (id >= a.gofs[SPX_MSC_MAX_MAPS]) return;
-    // which map: the one whose range of the prefix sums holds id (a map without a gradient has an empty range)
-    int k = 0, h = 1, w = 1;
-    float rh = 1.0f, rw = 1.0f;
-    long long local = 0;
-    void* grad = nullptr;
-#pragma unroll
-    for (int q = 0; q < SPX_MSC_MAX_MAPS; ++q) {
-        if (q < K && id >= a.gofs[q] && id < a.gofs[q + 1]) {
-            k = q;
-            h = a.d.maps[q].h;
-            w = a.d.maps[q].w;
-            rh = a.rh[q];
-            rw = a.rw[q];
-            local = id - a.gofs[q];
-            grad = a.d.grads[q];
-        }
-    }
-    const int j = (int)(local % w);
-    const int i = (int)((local / w) % h);
-    const long long plane = local / ((long long)w * h);                           // b * C + c
-    const bool g16 = a.d.g_dtype == 0, y16 = a.d.out_dtype == 0, sig = a.d.activation == 1;
-    const long long base = plane * H * W;
-
-    float acc = 0.0f;
-    if (k == 0) {
-        const long long o = base + (long long)i * W + j;
-        if (!a.d.index || a.d.index[o] == 0) {
-            float g = msc_load(a.d.g, g16, o);
-            if (sig) {
-                const float y = msc_load(a.d.out, y16, o);
-                g = g * (y * (1.0f - y));
-            }
-            acc = g;
-        }
-    } else {
-        acc = msc_gather(a.d, k, h, w, rh, rw, H, W, i, j, base, base, acc);
-    }
-    if (a.d.in_dtype == 0) ((uint16_t*)grad)[local] = msc_bf16_bits(acc);
-    else ((float*)grad)[local] = acc;
+    const MscSource s = msc_source(a, nullptr, id);
+    const long long base = s.plane * a.H * a.W;
+    msc_store(s.grad, a.d.in_dtype == 0, s.local, msc_max_term(a, s, base, base, 0.0f, false));
 }
 
-static void msc_fill(SpxMscArgs& a, const spx_msc& d) {
+// d, H, W and the ratios of every map
+static void msc_fill(SpxMscCommon& a, const spx_msc& d) {
     a.d = d;
     a.H = d.maps[0].h;
     a.W = d.maps[0].w;
@@ -356,6 +373,26 @@ static void msc_fill(SpxMscArgs& a, const spx_msc& d) {
             a.rw[k] = (float)d.maps[k].w / (float)a.W;
         }
     }
+}
+// gofs of the backward: one thread per element of every map that gets a gradient; returns their number
+static long long msc_grad_offsets(SpxMscCommon& a) {
+    const spx_msc& d = a.d;
+    a.gofs[0] = 0;
+    for (int k = 0; k < SPX_MSC_MAX_MAPS; ++k) {
+        const long long n = (k < d.K && d.grads[k]) ? (long long)d.B * d.C * d.maps[k].h * d.maps[k].w : 0;
+        a.gofs[k + 1] = a.gofs[k] + n;
+    }
+    return a.gofs[SPX_MSC_MAX_MAPS];
+}
+// channels per block of a forward whose one pass over the channels takes `blocks` blocks: enough blocks to fill the chip (about
+// 8 per CU), then as many channels per block as that leaves, a multiple of `round` - what a thread sets up before its channel
+// loop is paid once per block and thread
+static int msc_channel_chunk(long long blocks, int C, int round) {
+    long long chunks = 2048 / blocks;
+    if (chunks < 1) chunks = 1;
+    if (chunks > C) chunks = C;
+    const int cchunk = (int)((C + chunks - 1) / chunks);
+    return (cchunk + round - 1) / round * round;
 }
 
 #define MSC_LAUNCH_FWD(kernel)                                                                                   \
@@ -381,13 +418,7 @@ hipError_t spx_launch_msc_max_fwd(const spx_msc& d, hipStream_t s) {
     a.out_mis = (int)(((uintptr_t)d.out / esz) & (MSC_VEC - 1));
     const long long tasks = (long long)a.H * a.groups;
     const unsigned bx = (unsigned)((tasks + MSC_THREADS - 1) / MSC_THREADS);
-    // enough blocks to fill the chip (about 8 per CU), then as many channels per block as that leaves: the per-row setup is
-    // paid once per block and thread
-    long long chunks = 2048 / ((long long)bx * d.B);
-    if (chunks < 1) chunks = 1;
-    if (chunks > d.C) chunks = d.C;
-    a.cchunk = (int)((d.C + chunks - 1) / chunks);
-    if (d.K == 1) a.cchunk = (a.cchunk + MSC_ACT_UNROLL - 1) / MSC_ACT_UNROLL * MSC_ACT_UNROLL;
+    a.cchunk = msc_channel_chunk((long long)bx * d.B, d.C, d.K == 1 ? MSC_ACT_UNROLL : 1);
     const dim3 grid(bx, (unsigned)((d.C + a.cchunk - 1) / a.cchunk), (unsigned)d.B);
     if (d.K == 1) MSC_LAUNCH_FWD(spx_msc_act_kernel);
     else MSC_LAUNCH_FWD(spx_msc_max_fwd_kernel);
@@ -397,12 +428,7 @@ hipError_t spx_launch_msc_max_fwd(const spx_msc& d, hipStream_t s) {
 hipError_t spx_launch_msc_max_bwd(const spx_msc& d, hipStream_t s) {
     SpxMscArgs a = {};
     msc_fill(a, d);
-    a.gofs[0] = 0;
-    for (int k = 0; k < SPX_MSC_MAX_MAPS; ++k) {
-        const long long n = (k < d.K && d.grads[k]) ? (long long)d.B * d.C * d.maps[k].h * d.maps[k].w : 0;
-        a.gofs[k + 1] = a.gofs[k] + n;
-    }
-    const long long total = a.gofs[SPX_MSC_MAX_MAPS];
+    const long long total = msc_grad_offsets(a);
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(spx_msc_max_bwd_kernel, dim3((unsigned)((total + MSC_THREADS - 1) / MSC_THREADS)), dim3(MSC_THREADS), 0, s, a);
     return hipGetLastError();
@@ -410,7 +436,8 @@ hipError_t spx_launch_msc_max_bwd(const spx_msc& d, hipStream_t s) {
 
 // ---- the packed training maps (spx_msc_pack_fwd / _bwd) ------------------------------------------------------------------------
 // The K maps at their own grids and, with_max, their maximum written side by side on ONE pixel axis: out [C, M], pixel (b, i) of
-// segment q at column off_q + b . h_q . w_q + i (include/spx_hip.h).  Values, index and rounding are those of the kernels above.
+// segment q at column off_q + b . h_q . w_q + i (include/spx_hip.h).  Values, index and rounding are those of the kernels above,
+// by the same device functions.
 //
 //   forward   a thread owns the columns [4 t, 4 t + 4) of a chunk of channels (grid: column groups x channel chunks).  Its four
 //       columns are decoded once, before the channel loop: segment, image, pixel.  A group that lies inside one plane of a plain
@@ -418,13 +445,12 @@ hipError_t spx_launch_msc_max_bwd(const spx_msc& d, hipStream_t s) {
 //       the bandwidth-bound case); every other group - the maximum's, those that straddle a segment or an image, those of a
 //       buffer whose rows a vector cannot address (M no multiple of 4, a misaligned out) - goes column by column.
 //   backward  gather form as above, one thread per source element: first its own segment's term, then the maximum's segment.
-struct SpxMscPackArgs {
-    spx_msc d;
-    float rh[SPX_MSC_MAX_MAPS], rw[SPX_MSC_MAX_MAPS];
-    long long gofs[SPX_MSC_MAX_MAPS + 1];               // backward: prefix sums of the elements of the maps that get a gradient
-    int off[SPX_MSC_MAX_MAPS + 2];                      // first column of every segment; off[nseg] = M
-    int nseg, with_max, off_max, M, H, W, cchunk;
+struct SpxMscPackArgs : SpxMscCommon {
+    int nseg, with_max, off_max, M, cchunk;
     int vec_ok;                                         // forward: M % 4 == 0 and out aligned to a vector
+    // first column of every segment; off[nseg] = M.  (Last on purpose: with the scalars behind it the forward kernel spills
+    // SGPRs and reserves 36 bytes of scratch per lane.)
+    int off[SPX_MSC_MAX_MAPS + 2];
 };
 
 struct MscCol {
@@ -476,28 +502,13 @@ __device__ __forceinline__ float msc_pack_value(const SpxMscPackArgs& a, const M
         msc_src(a.rh[k], m.h, Y, i0, i1, ly);
         msc_src(a.rw[k], m.w, X, j0, j1, lx);
         const long long pl = (long long)col.b * m.batch_stride + (long long)c * m.channel_stride;
-        const long long r0 = pl + (long long)i0 * m.w, r1 = pl + (long long)i1 * m.w;
-        const float v00 = msc_load(m.data, IN_BF16, r0 + j0), v01 = msc_load(m.data, IN_BF16, r0 + j1);
-        const float v10 = msc_load(m.data, IN_BF16, r1 + j0), v11 = msc_load(m.data, IN_BF16, r1 + j1);
-        const float u = (1.0f - ly) * ((1.0f - lx) * v00 + lx * v01) + ly * ((1.0f - lx) * v10 + lx * v11);
-        if (u > v || (u != u && v == v)) {                 // torch.max(dim=0), as in spx_msc_max_fwd_kernel
+        const float u = msc_tap(m.data, IN_BF16, pl + (long long)i0 * m.w, pl + (long long)i1 * m.w, j0, j1, ly, lx);
+        if (msc_takes_over(u, v)) {
             v = u;
             win = k;
         }
     }
     return v;
-}
-
-template <bool OUT_BF16>
-__device__ __forceinline__ void msc_pack_store_vector(void* out, long long o, const float (&v)[MSC_VEC]) {
-    if (OUT_BF16) {
-        uint2 r;
-        r.x = (uint32_t)msc_bf16_bits(v[0]) | ((uint32_t)msc_bf16_bits(v[1]) << 16);
-        r.y = (uint32_t)msc_bf16_bits(v[2]) | ((uint32_t)msc_bf16_bits(v[3]) << 16);
-        *(uint2*)((uint16_t*)out + o) = r;
-    } else {
-        *(float4*)((float*)out + o) = make_float4(v[0], v[1], v[2], v[3]);
-    }
 }
 
 template <bool IN_BF16, bool OUT_BF16>
@@ -538,21 +549,16 @@ __global__ __launch_bounds__(MSC_THREADS) void spx_msc_pack_fwd_kernel(const Spx
             for (int u = 0; u < MSC_ACT_UNROLL; ++u) msc_load_vector<IN_BF16>(col[0].data, col[0].base + (long long)(c + u) * col[0].cs, v[u]);
             if (sig) {
 #pragma unroll
-                for (int u = 0; u < MSC_ACT_UNROLL; ++u)
-#pragma unroll
-                    for (int j = 0; j < MSC_VEC; ++j) v[u][j] = 1.0f / (1.0f + expf(-v[u][j]));
+                for (int u = 0; u < MSC_ACT_UNROLL; ++u) msc_sigmoid(v[u]);
             }
 #pragma unroll
-            for (int u = 0; u < MSC_ACT_UNROLL; ++u) msc_pack_store_vector<OUT_BF16>(a.d.out, (long long)(c + u) * M + xs, v[u]);
+            for (int u = 0; u < MSC_ACT_UNROLL; ++u) msc_store_vector<OUT_BF16>(a.d.out, (long long)(c + u) * M + xs, v[u]);
         }
         for (; c < c1; ++c) {
             float v[MSC_VEC];
             msc_load_vector<IN_BF16>(col[0].data, col[0].base + (long long)c * col[0].cs, v);
-            if (sig) {
-#pragma unroll
-                for (int j = 0; j < MSC_VEC; ++j) v[j] = 1.0f / (1.0f + expf(-v[j]));
-            }
-            msc_pack_store_vector<OUT_BF16>(a.d.out, (long long)c * M + xs, v);
+            if (sig) msc_sigmoid(v);
+            msc_store_vector<OUT_BF16>(a.d.out, (long long)c * M + xs, v);
         }
         return;
     }
@@ -567,99 +573,43 @@ __global__ __launch_bounds__(MSC_THREADS) void spx_msc_pack_fwd_kernel(const Spx
             if (j >= n) continue;
             int win;
             v[j] = msc_pack_value<IN_BF16>(a, col[j], c, win);
-            if (sig) v[j] = 1.0f / (1.0f + expf(-v[j]));
+            if (sig) v[j] = msc_sigmoid(v[j]);
             if (col[j].seg >= a.d.K && a.d.index) a.d.index[((long long)col[j].b * C + c) * HW + col[j].i] = (uint8_t)win;
         }
         if (a.vec_ok && n == MSC_VEC) {
-            msc_pack_store_vector<OUT_BF16>(a.d.out, o, v);
+            msc_store_vector<OUT_BF16>(a.d.out, o, v);
         } else {
 #pragma unroll
-            for (int j = 0; j < MSC_VEC; ++j) {
-                if (j >= n) continue;
-                if (OUT_BF16) ((uint16_t*)a.d.out)[o + j] = msc_bf16_bits(v[j]);
-                else ((float*)a.d.out)[o + j] = v[j];
-            }
+            for (int j = 0; j < MSC_VEC; ++j)
+                if (j < n) msc_store(a.d.out, OUT_BF16, o + j, v[j]);
         }
     }
 }
 
 __global__ __launch_bounds__(MSC_THREADS) void spx_msc_pack_bwd_kernel(const SpxMscPackArgs a) {
     const long long id = (long long)blockIdx.x * MSC_THREADS + threadIdx.x;
-    const int H = a.H, W = a.W, K = a.d.K, C = a.d.C, M = a.M;
     if (id >= a.gofs[SPX_MSC_MAX_MAPS]) return;
-    int k = 0, h = 1, w = 1, off = 0;
-    float rh = 1.0f, rw = 1.0f;
-    long long local = 0;
-    void* grad = nullptr;
-#pragma unroll
-    for (int q = 0; q < SPX_MSC_MAX_MAPS; ++q) {
-        if (q < K && id >= a.gofs[q] && id < a.gofs[q + 1]) {
-            k = q;
-            h = a.d.maps[q].h;
-            w = a.d.maps[q].w;
-            rh = a.rh[q];
-            rw = a.rw[q];
-            off = a.off[q];
-            local = id - a.gofs[q];
-            grad = a.d.grads[q];
-        }
-    }
-    const int j = (int)(local % w);
-    const int i = (int)((local / w) % h);
-    const long long plane = local / ((long long)w * h);                           // b * C + c
-    const int b = (int)(plane / C), c = (int)(plane - (long long)b * C);
-    const bool g16 = a.d.g_dtype == 0, y16 = a.d.out_dtype == 0, sig = a.d.activation == 1;
-    const long long row = (long long)c * M;
+    const MscSource s = msc_source(a, a.off, id);
+    const int C = a.d.C;
+    const int b = (int)(s.plane / C), c = (int)(s.plane - (long long)b * C);
+    const long long row = (long long)c * a.M;
 
     // the map's own segment first
-    float acc;
-    {
-        const long long o = row + off + (long long)b * h * w + (long long)i * w + j;
-        float g = msc_load(a.d.g, g16, o);
-        if (sig) {
-            const float y = msc_load(a.d.out, y16, o);
-            g = g * (y * (1.0f - y));
-        }
-        acc = g;
-    }
-    if (a.with_max) {
-        const long long ibase = plane * H * W;                                    // the index is [B, C, H, W]
-        const long long gbase = row + a.off_max + (long long)b * H * W;
-        if (k == 0) {
-            const long long p = (long long)i * W + j;
-            if (!a.d.index || a.d.index[ibase + p] == 0) {
-                float g = msc_load(a.d.g, g16, gbase + p);
-                if (sig) {
-                    const float y = msc_load(a.d.out, y16, gbase + p);
-                    g = g * (y * (1.0f - y));
-                }
-                acc += g;
-            }
-        } else {
-            acc = msc_gather(a.d, k, h, w, rh, rw, H, W, i, j, gbase, ibase, acc);
-        }
-    }
-    if (a.d.in_dtype == 0) ((uint16_t*)grad)[local] = msc_bf16_bits(acc);
-    else ((float*)grad)[local] = acc;
+    float acc = msc_upstream(a.d, row + s.off + (long long)b * s.h * s.w + (long long)s.i * s.w + s.j);
+    if (a.with_max)                                                               // (the index is [B, C, H, W])
+        acc = msc_max_term(a, s, row + a.off_max + (long long)b * a.H * a.W, s.plane * a.H * a.W, acc, true);
+    msc_store(s.grad, a.d.in_dtype == 0, s.local, acc);
 }
 
 static void msc_pack_fill(SpxMscPackArgs& a, const spx_msc& d, int with_max) {
-    a.d = d;
-    a.H = d.maps[0].h;
-    a.W = d.maps[0].w;
+    msc_fill(a, d);
     a.with_max = with_max ? 1 : 0;
     a.nseg = d.K + a.with_max;
     long long m = 0;
     for (int k = 0; k < SPX_MSC_MAX_MAPS + 2; ++k) {
         a.off[k] = (int)m;
-        if (k < SPX_MSC_MAX_MAPS) a.rh[k] = a.rw[k] = 1.0f;
-        if (k < d.K) {
-            a.rh[k] = (float)d.maps[k].h / (float)a.H;
-            a.rw[k] = (float)d.maps[k].w / (float)a.W;
-            m += (long long)d.B * d.maps[k].h * d.maps[k].w;
-        } else if (k == d.K && with_max) {
-            m += (long long)d.B * a.H * a.W;
-        }
+        if (k < d.K) m += (long long)d.B * d.maps[k].h * d.maps[k].w;
+        else if (k == d.K && with_max) m += (long long)d.B * a.H * a.W;
     }
     a.M = (int)m;                                        // (< 2^31: checked by the entry point)
     a.off_max = a.off[d.K];
@@ -672,13 +622,7 @@ hipError_t spx_launch_msc_pack_fwd(const spx_msc& d, int with_max, hipStream_t s
     a.vec_ok = (a.M % MSC_VEC == 0 && (uintptr_t)d.out % vbytes == 0) ? 1 : 0;
     const long long groups = ((long long)a.M + MSC_VEC - 1) / MSC_VEC;
     const unsigned bx = (unsigned)((groups + MSC_THREADS - 1) / MSC_THREADS);
-    // enough blocks to fill the chip (about 8 per CU), then as many channels per block as that leaves (a multiple of the four
-    // channels of a step): the decode of the columns is paid once per block and thread
-    long long chunks = 2048 / (long long)bx;
-    if (chunks < 1) chunks = 1;
-    if (chunks > d.C) chunks = d.C;
-    a.cchunk = (int)((d.C + chunks - 1) / chunks);
-    a.cchunk = (a.cchunk + MSC_ACT_UNROLL - 1) / MSC_ACT_UNROLL * MSC_ACT_UNROLL;
+    a.cchunk = msc_channel_chunk(bx, d.C, MSC_ACT_UNROLL);                        // (the four channels of a step)
     const dim3 grid(bx, (unsigned)((d.C + a.cchunk - 1) / a.cchunk), 1);
     MSC_LAUNCH_FWD(spx_msc_pack_fwd_kernel);
     return hipGetLastError();
@@ -687,12 +631,7 @@ hipError_t spx_launch_msc_pack_fwd(const spx_msc& d, int with_max, hipStream_t s
 hipError_t spx_launch_msc_pack_bwd(const spx_msc& d, int with_max, hipStream_t s) {
     SpxMscPackArgs a = {};
     msc_pack_fill(a, d, with_max);
-    a.gofs[0] = 0;
-    for (int k = 0; k < SPX_MSC_MAX_MAPS; ++k) {
-        const long long n = (k < d.K && d.grads[k]) ? (long long)d.B * d.C * d.maps[k].h * d.maps[k].w : 0;
-        a.gofs[k + 1] = a.gofs[k] + n;
-    }
-    const long long total = a.gofs[SPX_MSC_MAX_MAPS];
+    const long long total = msc_grad_offsets(a);
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(spx_msc_pack_bwd_kernel, dim3((unsigned)((total + MSC_THREADS - 1) / MSC_THREADS)), dim3(MSC_THREADS), 0, s, a);
     return hipGetLastError();

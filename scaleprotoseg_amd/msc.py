@@ -78,34 +78,45 @@ MSC_ACTIVATIONS = {"none": 0, "sigmoid": 1}
 _DTYPE_CODE = {torch.bfloat16: 0, torch.float32: 1}
 
 
-def _describe(maps: Sequence[torch.Tensor], out_dtype, activation: int) -> "_lib.SpxMsc":
+def _describe(shapes, map_dtype, out_dtype, activation: int, maps: Sequence[torch.Tensor] = ()) -> "_lib.SpxMsc":
+    """The descriptor of a call on maps of ``shapes``; the forward passes the ``maps`` too, the backward reads their sizes only."""
     a = _lib.SpxMsc()
-    a.K, a.B, a.C = len(maps), int(maps[0].shape[0]), int(maps[0].shape[1])
-    a.in_dtype, a.out_dtype, a.activation = _DTYPE_CODE[maps[0].dtype], _DTYPE_CODE[out_dtype], activation
+    a.K, a.B, a.C = len(shapes), int(shapes[0][0]), int(shapes[0][1])
+    a.in_dtype, a.out_dtype, a.activation = _DTYPE_CODE[map_dtype], _DTYPE_CODE[out_dtype], activation
+    for k, s in enumerate(shapes):
+        a.maps[k].h, a.maps[k].w = int(s[2]), int(s[3])
     for k, m in enumerate(maps):
         d = a.maps[k]
         d.data, d.batch_stride, d.channel_stride = m.data_ptr(), int(m.stride(0)), int(m.stride(1))
-        d.h, d.w = int(m.shape[2]), int(m.shape[3])
     return a
 
 
-class _MscMaxFn(torch.autograd.Function):
+class _MscFn(torch.autograd.Function):
+    """Both operators.  ``layout`` None: ``msc_max``, the output is [B, C, H, W].  A ``PackedLayout``: ``msc_pack``, the output is
+    [C, M] and ``want_index`` says whether the layout ends with the maximum's segment (``with_max``)."""
+
     @staticmethod
-    def forward(ctx, activation, out_dtype, out, want_index, *maps):
+    def forward(ctx, activation, out_dtype, out, want_index, layout, *maps):
         lib = _lib.load()
         B, Cc, H, W = maps[0].shape
-        need = any(ctx.needs_input_grad[4:])
+        need = any(ctx.needs_input_grad[5:])
         if out is not None:
             ctx.mark_dirty(out)
-        y = out if out is not None else torch.empty((B, Cc, H, W), dtype=out_dtype, device=maps[0].device)
-        # (K = 1 has one candidate: the backward needs no index, a caller that asks for one gets the zeros it is)
-        index = torch.empty((B, Cc, H, W), dtype=torch.uint8, device=y.device) if want_index or (need and len(maps) > 1) else None
-        a = _describe(maps, out_dtype, activation)
+        y = out if out is not None else torch.empty((B, Cc, H, W) if layout is None else (Cc, layout.M), dtype=out_dtype,
+                                                    device=maps[0].device)
+        # (msc_max with K = 1 has one candidate: the backward needs no index, a caller that asks for one gets the zeros it is)
+        if want_index or (layout is None and need and len(maps) > 1):
+            index = torch.empty((B, Cc, H, W), dtype=torch.uint8, device=y.device)
+        else:
+            index = None
+        ctx.shapes, ctx.map_dtype = [tuple(m.shape) for m in maps], maps[0].dtype
+        ctx.activation, ctx.out_dtype, ctx.layout, ctx.with_max = activation, out_dtype, layout, want_index
+        a = _describe(ctx.shapes, ctx.map_dtype, out_dtype, activation, maps)
         a.out, a.index = y.data_ptr(), None if index is None else index.data_ptr()
-        _lib.check(lib.spx_msc_max_fwd(C.byref(a), _lib.stream_ptr()))
-        ctx.activation, ctx.out_dtype = activation, out_dtype
-        ctx.shapes = [tuple(m.shape) for m in maps]
-        ctx.map_dtype = maps[0].dtype
+        if layout is None:
+            _lib.check(lib.spx_msc_max_fwd(C.byref(a), _lib.stream_ptr()))
+        else:
+            _lib.check(lib.spx_msc_pack_fwd(C.byref(a), int(want_index), _lib.stream_ptr()))
         if need:
             ctx.save_for_backward(y, index)
         if index is None:
@@ -121,43 +132,27 @@ class _MscMaxFn(torch.autograd.Function):
             g = g.float()
         g = g.contiguous()
         grads: List[Optional[torch.Tensor]] = [
-            torch.empty(s, dtype=ctx.map_dtype, device=g.device) if ctx.needs_input_grad[4 + k] else None
+            torch.empty(s, dtype=ctx.map_dtype, device=g.device) if ctx.needs_input_grad[5 + k] else None
             for k, s in enumerate(ctx.shapes)]
-        a = _lib.SpxMsc()
-        a.K, a.B, a.C = len(ctx.shapes), ctx.shapes[0][0], ctx.shapes[0][1]
-        a.in_dtype, a.out_dtype, a.g_dtype = _DTYPE_CODE[ctx.map_dtype], _DTYPE_CODE[ctx.out_dtype], _DTYPE_CODE[g.dtype]
-        a.activation = ctx.activation
-        for k, s in enumerate(ctx.shapes):
-            a.maps[k].h, a.maps[k].w = s[2], s[3]              # (the backward reads the maps' sizes only)
-            a.grads[k] = None if grads[k] is None else grads[k].data_ptr()
+        a = _describe(ctx.shapes, ctx.map_dtype, ctx.out_dtype, ctx.activation)
+        a.g_dtype = _DTYPE_CODE[g.dtype]
+        for k, t in enumerate(grads):
+            a.grads[k] = None if t is None else t.data_ptr()
         a.out, a.g = y.data_ptr(), g.data_ptr()
         a.index = None if index is None else index.data_ptr()
-        _lib.check(lib.spx_msc_max_bwd(C.byref(a), _lib.stream_ptr()))
-        return (None, None, None, None, *grads)
+        if ctx.layout is None:
+            _lib.check(lib.spx_msc_max_bwd(C.byref(a), _lib.stream_ptr()))
+        else:
+            _lib.check(lib.spx_msc_pack_bwd(C.byref(a), int(ctx.with_max), _lib.stream_ptr()))
+        return (None, None, None, None, None, *grads)
 
 
 def msc_max(maps: Sequence[torch.Tensor], activation: str = "none", dtype: Optional[torch.dtype] = None,
             out: Optional[torch.Tensor] = None, return_index: bool = False):
     """Pixel-wise maximum over ``maps[0]`` and the bilinearly resampled ``maps[1:]``, then ``activation``, then the cast to
     ``dtype``: one launch.  The contract is the module docstring's.  Returns ``y`` or ``(y, index)``."""
-    if activation not in MSC_ACTIVATIONS:
-        raise SpxError(f"msc_max: unknown activation {activation!r} (one of {sorted(MSC_ACTIVATIONS)})")
-    maps = _check_maps("msc_max", maps)
-    out_dtype = dtype if dtype is not None else maps[0].dtype
-    if out_dtype not in _DTYPE_CODE:
-        raise SpxError(f"msc_max: dtype {out_dtype}; float32 or bfloat16")
-    if out is not None:
-        if tuple(out.shape) != tuple(maps[0].shape) or out.dtype != out_dtype or not out.is_contiguous():
-            raise SpxError(f"msc_max: out must be a contiguous {out_dtype} {tuple(maps[0].shape)}, got {out.dtype} "
-                           f"{tuple(out.shape)} with strides {tuple(out.stride())}")
-    for k, m in enumerate(maps + ([out] if out is not None else [])):
-        _lib.require_gpu(m, "msc_max: out" if k == len(maps) else f"msc_max: map {k}")
-        if m.device != maps[0].device:
-            raise SpxError(f"msc_max: {m.device} and {maps[0].device} in one call")
-    if out is not None:
-        if torch.is_grad_enabled() and any(m.requires_grad for m in maps):
-            raise SpxError("msc_max: out= is for calls without a gradient")
-    y, index = _MscMaxFn.apply(MSC_ACTIVATIONS[activation], out_dtype, out, bool(return_index), *maps)
+    maps, out_dtype, _ = _check_call("msc_max", maps, activation, dtype, out)
+    y, index = _MscFn.apply(MSC_ACTIVATIONS[activation], out_dtype, out, bool(return_index), None, *maps)
     return (y, index) if return_index else y
 
 
@@ -255,7 +250,11 @@ class PackedMaps:
         return [self.layout.view(self.features, k) for k in range(len(self.layout))]
 
 
-def _check_maps(who: str, maps) -> List[torch.Tensor]:
+def _check_call(who: str, maps, activation: str, dtype, out, with_max: Optional[bool] = None):
+    """The argument checks of ``msc_max`` (``with_max`` None) and ``msc_pack``, before any launch -> (maps as a list, the output's
+    dtype, the ``PackedLayout`` or None)."""
+    if activation not in MSC_ACTIVATIONS:
+        raise SpxError(f"{who}: unknown activation {activation!r} (one of {sorted(MSC_ACTIVATIONS)})")
     if isinstance(maps, torch.Tensor):
         maps = [maps]
     maps = list(maps)
@@ -273,73 +272,19 @@ def _check_maps(who: str, maps) -> List[torch.Tensor]:
         h, w = int(m.shape[2]), int(m.shape[3])
         if (w > 1 and m.stride(3) != 1) or (h > 1 and m.stride(2) != w) or m.stride(0) < 0 or m.stride(1) < 0:
             raise SpxError(f"{who}: the {h} x {w} plane of map {k} is not contiguous (strides {tuple(m.stride())})")
-    return maps
-
-
-class _MscPackFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, activation, out_dtype, out, with_max, layout, *maps):
-        lib = _lib.load()
-        B, Cc, H, W = maps[0].shape
-        need = any(ctx.needs_input_grad[5:])
-        if out is not None:
-            ctx.mark_dirty(out)
-        y = out if out is not None else torch.empty((Cc, layout.M), dtype=out_dtype, device=maps[0].device)
-        index = torch.empty((B, Cc, H, W), dtype=torch.uint8, device=y.device) if with_max else None
-        a = _describe(maps, out_dtype, activation)
-        a.out, a.index = y.data_ptr(), None if index is None else index.data_ptr()
-        _lib.check(lib.spx_msc_pack_fwd(C.byref(a), int(with_max), _lib.stream_ptr()))
-        ctx.activation, ctx.out_dtype, ctx.with_max = activation, out_dtype, with_max
-        ctx.shapes = [tuple(m.shape) for m in maps]
-        ctx.map_dtype = maps[0].dtype
-        if need:
-            ctx.save_for_backward(y, index)
-        if index is None:
-            index = torch.empty(0, dtype=torch.uint8, device=y.device)
-        ctx.mark_non_differentiable(index)
-        return y, index
-
-    @staticmethod
-    def backward(ctx, g, _g_index):
-        lib = _lib.load()
-        y, index = ctx.saved_tensors
-        if g.dtype not in _DTYPE_CODE:
-            g = g.float()
-        g = g.contiguous()
-        grads: List[Optional[torch.Tensor]] = [
-            torch.empty(s, dtype=ctx.map_dtype, device=g.device) if ctx.needs_input_grad[5 + k] else None
-            for k, s in enumerate(ctx.shapes)]
-        a = _lib.SpxMsc()
-        a.K, a.B, a.C = len(ctx.shapes), ctx.shapes[0][0], ctx.shapes[0][1]
-        a.in_dtype, a.out_dtype, a.g_dtype = _DTYPE_CODE[ctx.map_dtype], _DTYPE_CODE[ctx.out_dtype], _DTYPE_CODE[g.dtype]
-        a.activation = ctx.activation
-        for k, s in enumerate(ctx.shapes):
-            a.maps[k].h, a.maps[k].w = s[2], s[3]              # (the backward reads the maps' sizes only)
-            a.grads[k] = None if grads[k] is None else grads[k].data_ptr()
-        a.out, a.g = y.data_ptr(), g.data_ptr()
-        a.index = None if index is None else index.data_ptr()
-        _lib.check(lib.spx_msc_pack_bwd(C.byref(a), int(ctx.with_max), _lib.stream_ptr()))
-        return (None, None, None, None, None, *grads)
-
-
-def msc_pack(maps: Sequence[torch.Tensor], activation: str = "none", dtype: Optional[torch.dtype] = None,
-             with_max: bool = True, out: Optional[torch.Tensor] = None) -> PackedMaps:
-    """``act(maps[k])`` at every map's own grid and (``with_max``) the ``msc_max`` of all of them, side by side on one pixel
-    axis, cast to ``dtype``: one launch.  The contract is the module docstring's.  Returns a ``PackedMaps``."""
-    who = "msc_pack"
-    if activation not in MSC_ACTIVATIONS:
-        raise SpxError(f"{who}: unknown activation {activation!r} (one of {sorted(MSC_ACTIVATIONS)})")
-    maps = _check_maps(who, maps)
     out_dtype = dtype if dtype is not None else maps[0].dtype
     if out_dtype not in _DTYPE_CODE:
         raise SpxError(f"{who}: dtype {out_dtype}; float32 or bfloat16")
-    B, Cc = int(maps[0].shape[0]), int(maps[0].shape[1])
-    layout = PackedLayout.of_maps(B, [tuple(m.shape[2:]) for m in maps], bool(with_max))
-    if Cc * layout.M >= 2 ** 40:
-        raise SpxError(f"{who}: C * M = {Cc} * {layout.M} (below 2^40)")
+    layout, shape = None, tuple(maps[0].shape)
+    if with_max is not None:
+        B, Cc = shape[:2]
+        layout = PackedLayout.of_maps(B, [tuple(m.shape[2:]) for m in maps], with_max)
+        if Cc * layout.M >= 2 ** 40:
+            raise SpxError(f"{who}: C * M = {Cc} * {layout.M} (below 2^40)")
+        shape = (Cc, layout.M)
     if out is not None:
-        if tuple(out.shape) != (Cc, layout.M) or out.dtype != out_dtype or not out.is_contiguous():
-            raise SpxError(f"{who}: out must be a contiguous {out_dtype} {(Cc, layout.M)}, got {out.dtype} "
+        if tuple(out.shape) != shape or out.dtype != out_dtype or not out.is_contiguous():
+            raise SpxError(f"{who}: out must be a contiguous {out_dtype} {shape}, got {out.dtype} "
                            f"{tuple(out.shape)} with strides {tuple(out.stride())}")
     for k, m in enumerate(maps + ([out] if out is not None else [])):
         _lib.require_gpu(m, f"{who}: out" if k == len(maps) else f"{who}: map {k}")
@@ -347,8 +292,16 @@ def msc_pack(maps: Sequence[torch.Tensor], activation: str = "none", dtype: Opti
             raise SpxError(f"{who}: {m.device} and {maps[0].device} in one call")
     if out is not None and torch.is_grad_enabled() and any(m.requires_grad for m in maps):
         raise SpxError(f"{who}: out= is for calls without a gradient")
-    y, index = _MscPackFn.apply(MSC_ACTIVATIONS[activation], out_dtype, out, bool(with_max), layout, *maps)
-    return PackedMaps(features=y.view(1, Cc, 1, layout.M), layout=layout, index=index if with_max else None)
+    return maps, out_dtype, layout
+
+
+def msc_pack(maps: Sequence[torch.Tensor], activation: str = "none", dtype: Optional[torch.dtype] = None,
+             with_max: bool = True, out: Optional[torch.Tensor] = None) -> PackedMaps:
+    """``act(maps[k])`` at every map's own grid and (``with_max``) the ``msc_max`` of all of them, side by side on one pixel
+    axis, cast to ``dtype``: one launch.  The contract is the module docstring's.  Returns a ``PackedMaps``."""
+    maps, out_dtype, layout = _check_call("msc_pack", maps, activation, dtype, out, bool(with_max))
+    y, index = _MscFn.apply(MSC_ACTIVATIONS[activation], out_dtype, out, bool(with_max), layout, *maps)
+    return PackedMaps(features=y.view(1, maps[0].shape[1], 1, layout.M), layout=layout, index=index if with_max else None)
 
 
 class MSC(nn.Module):

@@ -11,6 +11,8 @@ target and the Pascal grids 41 <- {21, 31} and 65 <- {33, 49}.
 * backward: with the kernel's own index every map's gradient within the restatement's gradient bound (fp32 g without and with
   the sigmoid; the bf16-output case against the float64 formula at the bf16 y); a map that needs no gradient gets none and
   leaves the others unchanged; two runs agree bit for bit;
+* eight maps, as many as the kernels' unrolled loops take: forward with the float64 argmax on every pixel, backward with gaps in
+  the set of maps that need a gradient;
 * memory: ``out``, the index and the gradient buffers inside guard bands, poisoned with NaN, at offsets no vector width
   divides, from a channel slice of a wider tensor: every element inside written, nothing outside;
 * the module on the device is ``msc_max`` of its own base outputs; ``fuse_feature_epilogue`` on a small net; one forward +
@@ -135,6 +137,44 @@ def test_backward(name, activation, dtype):
     # a map that needs no gradient gets none; the others are unchanged
     _, _, part = _backward(maps, g, activation, dtype, needs=(True, False, True))
     assert part[1] is None and bits_equal(part[0], grads[0]) and bits_equal(part[2], grads[2])
+
+
+def test_eight_maps_forward():
+    """As many maps as the kernels' unrolled loops take (tests/msc_cases.py): float64 decides every pixel of this case, so the
+    index is the float64 argmax everywhere."""
+    dev = gpu_device()
+    y, index = spx.msc_max(_maps("eight", dev), return_index=True)
+    z, idx64, zb, u, b = MC.restated("eight")
+    assert MR.decided(u, b).all()
+    err = np.abs(y.cpu().numpy().astype(np.float64) - z)
+    print(f"msc_max forward eight: worst error / bound {np.max(err[zb > 0] / zb[zb > 0]):.3f}")
+    assert (err <= zb).all()
+    assert np.array_equal(index.cpu().numpy(), idx64)
+
+
+@pytest.mark.parametrize("activation,dtype", [("none", torch.float32), ("sigmoid", torch.bfloat16)])
+def test_eight_maps_backward(activation, dtype):
+    """``test_backward``'s measure on eight maps, then with ``MC.EIGHT_NEEDS``: empty ranges of the prefix sums at the front, in
+    the middle and next to the end."""
+    dev = gpu_device()
+    maps = _maps("eight", dev)
+    g = torch.from_numpy(MC.case("eight")["g"]).to(dev)
+    if dtype == torch.bfloat16:
+        g = g.to(torch.bfloat16).float()
+    y, index, grads = _backward(maps, g, activation, dtype)
+    y64, g64 = y.float().cpu().numpy().astype(np.float64), g.cpu().numpy().astype(np.float64)
+    gprime = g64 * y64 * (1.0 - y64) if activation == "sigmoid" else g64
+    ref, bounds = MR.gradients([m.shape[2:] for m in maps], index.cpu().numpy(), gprime, derivative=activation == "sigmoid")
+    for k, (got, want, bound) in enumerate(zip(grads, ref, bounds)):
+        err = np.abs(got.cpu().numpy().astype(np.float64) - want)
+        worst = np.max(err[bound > 0] / bound[bound > 0]) if (bound > 0).any() else 0.0
+        print(f"msc_max backward eight {activation} {dtype} map {k}: worst error / bound {worst:.3f}")
+        assert tuple(got.shape) == want.shape and (err <= bound).all(), k
+        assert float(got.abs().max()) > 0
+    _, index2, part = _backward(maps, g, activation, dtype, needs=MC.EIGHT_NEEDS)
+    assert torch.equal(index, index2)
+    for k, need in enumerate(MC.EIGHT_NEEDS):
+        assert (bits_equal(part[k], grads[k]) if need else part[k] is None), k
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

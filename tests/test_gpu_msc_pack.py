@@ -5,7 +5,7 @@ path), on the recorded MSC cases at B = 2, C = 5 (tests/msc_cases.py) and on the
 1. values: every segment view bit-equal to what ``msc_max`` returns for that segment (``[m]`` for the plain ones, all maps for
    the maximum), the index too; every segment within the float64 bounds of tests/test_gpu_msc.py; ``with_max=False``; K = 1;
 2. backward: every gradient within the bound of tests/msc_pack_cases.py; bf16 maps get bf16 gradients; two runs bit-identical;
-   a map that needs no gradient gets no buffer;
+   a map that needs no gradient gets no buffer; 1. and 2. on eight maps too (nine segments, gaps in the set of gradients);
 3. the distance path on the packed axis against the fixture / the oracle (``parity_cases.close_fwd``, ``grad_close``) in the
    three tuple modes, with a loss that weights the segments differently; bit-equality with the list path is measured and
    printed (distances and activations: asserted, as the MI355X run showed it; logits: reported only - they were bit-equal on
@@ -155,6 +155,49 @@ def test_backward(name, activation, dtype):
     assert none is None
     for got, want, bound in zip(own, ref0, bounds0):
         assert (np.abs(got.cpu().numpy().astype(np.float64) - want) <= bound).all()
+
+
+@pytest.mark.parametrize("activation,dtype", [("none", torch.float32), ("sigmoid", torch.bfloat16)])
+@pytest.mark.parametrize("with_max", [True, False])
+def test_eight_maps_pack_is_msc_max_per_segment(with_max, activation, dtype):
+    """As many maps as the kernels' unrolled decode loops take (tests/msc_cases.py): M = 880 with the maximum's segment (vector
+    stores), 754 without (element stores)."""
+    dev = gpu_device()
+    maps = _maps("eight", dev)
+    lay = PC.layout("eight", with_max)
+    pk = spx.msc_pack(maps, activation=activation, dtype=dtype, with_max=with_max)
+    assert lay.M == (880 if with_max else 754) and pk.segments == lay.segments and len(pk.views()) == 8 + with_max
+    views = pk.views()
+    for k, m in enumerate(maps):
+        assert _same_bits(views[k], spx.msc_max([m], activation=activation, dtype=dtype)), k
+    if with_max:
+        want, index = spx.msc_max(maps, activation=activation, dtype=dtype, return_index=True)
+        assert _same_bits(views[8], want) and torch.equal(pk.index, index)
+    else:
+        assert pk.index is None
+
+
+@pytest.mark.parametrize("activation,dtype", [("none", torch.float32), ("sigmoid", torch.bfloat16)])
+def test_eight_maps_backward(activation, dtype):
+    """``test_backward``'s measure on eight maps, then with ``MC.EIGHT_NEEDS``: empty ranges of the prefix sums at the front, in
+    the middle and next to the end."""
+    dev = gpu_device()
+    maps = _maps("eight", dev)
+    lay = PC.layout("eight")
+    B, Cc = maps[0].shape[:2]
+    g = _upstream(lay, Cc, dev, dtype)
+    y, index, grads = _backward(maps, g, activation, dtype)
+    y64 = y.float().reshape(Cc, lay.M).cpu().numpy() if activation == "sigmoid" else None
+    ref, bounds = PC.gradients([tuple(m.shape[2:]) for m in maps], B, index.cpu().numpy(), g.cpu().numpy(), y64)
+    for k, (got, want, bound) in enumerate(zip(grads, ref, bounds)):
+        err = np.abs(got.cpu().numpy().astype(np.float64) - want)
+        worst = np.max(err[bound > 0] / bound[bound > 0]) if (bound > 0).any() else 0.0
+        print(f"msc_pack backward eight {activation} {dtype} map {k}: worst error / bound {worst:.3f}")
+        assert tuple(got.shape) == want.shape and (err <= bound).all(), k
+    _, index2, part = _backward(maps, g, activation, dtype, needs=MC.EIGHT_NEEDS)
+    assert torch.equal(index, index2)
+    for k, need in enumerate(MC.EIGHT_NEEDS):
+        assert (bits_equal(part[k], grads[k]) if need else part[k] is None), k
 
 
 def test_bf16_maps_get_bf16_gradients():

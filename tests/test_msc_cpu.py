@@ -3,6 +3,7 @@
 * tests/msc_restatement.py reproduces what the reference's REAL ``MSC`` recorded (tests/golden/msc_features*.npz,
   tools/gen_msc_golden.py): ``logits_max`` within the per-element bound, the index wherever the float64 gap between the best and
   the second candidate exceeds the sum of their bounds, the gradients (with the reference's index) within the gradient bound;
+  on the generated case of eight maps (tests/msc_cases.py) it reproduces the stock torch formula, the index on every pixel;
 * ``spx.MSC`` on CPU tensors (the reference's stock formula) matches the fixture in eval and training mode; ``scales=[]``, a
   list-returning base, ``state_dict`` keys and ``str()``; ``PPNetMultiScale(spx.MSC(base), ...)`` constructs;
 * ``msc_max`` refuses CPU tensors and every malformed input before any launch; ``fuse_feature_epilogue`` refuses a backbone that
@@ -13,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 import msc_cases as MC
 import msc_restatement as MR
@@ -53,6 +55,21 @@ def test_restatement_reproduces_the_reference_gradients(name):
         err = np.abs(g - c[f"d{k}"])
         assert g.shape == c[f"d{k}"].shape and (err <= b).all(), (k, (err - b).max())
         assert k == 0 or np.abs(g).max() > 0 or name == "tie"
+
+
+def test_restatement_reproduces_the_stock_formula_on_eight_maps():
+    """The generated case with as many maps as the kernels take: float64 decides every pixel, every map wins its share, and the
+    stock ``F.interpolate`` + ``torch.max`` formula is within the bound with an equal index."""
+    maps = [torch.from_numpy(m) for m in MC.case("eight")["maps"]]
+    z, idx, zb, u, b = MC.restated("eight")
+    assert len(maps) == 8 and idx.size == 630 and MR.decided(u, b).all()
+    assert np.bincount(idx.ravel(), minlength=8).min() >= 45
+    H, W = maps[0].shape[2:]
+    up = [maps[0]] + [F.interpolate(m, size=(H, W), mode="bilinear", align_corners=False) for m in maps[1:]]
+    ref, ref_index = torch.max(torch.stack(up), dim=0)
+    assert (np.abs(z - ref.numpy().astype(np.float64)) <= zb).all() and np.array_equal(idx, ref_index.numpy())
+    grids = [m.shape[2:] for m in maps]
+    assert spx.PackedLayout.of_maps(2, grids).M == 880 and spx.PackedLayout.of_maps(2, grids, with_max=False).M == 754
 
 
 class _TableBase(nn.Module):
