@@ -10,13 +10,13 @@ on an AMD GPU when the distance methods are called.
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional, Tuple, Union
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
 
 from ._cache import cached
-from .functional import (MAX_FUSED_HEAD_ROWS, BankLayout, ClassGather, SpxError, class_gather_table,
+from .functional import (MAX_FUSED_HEAD_ROWS, BankLayout, ClassGather, FusedCrossEntropy, SpxError, class_gather_table,
                          cross_entropy_from_logits, identity_is_one_hot, invalidate_pack_cache, proto_head_forward,
                          push_min_from_features, shifted_labels_i32, wide_linear)
 from .loss import ClassDistances
@@ -61,6 +61,20 @@ def _build_add_on(kind: str, in_ch: int, proto_ch: int, bottleneck_stride: Optio
     return nn.Sequential(
         nn.Conv2d(in_ch, proto_ch, kernel_size=1), nn.ReLU(), nn.Conv2d(proto_ch, proto_ch, kernel_size=1), nn.Sigmoid()
     )
+
+
+class _HeadOut(NamedTuple):
+    """What a class's ``_head`` computed, flat over the pixels of its input ([B, C, H, W] or a packed [1, C, 1, M]), whatever
+    branch produced it."""
+
+    logits: torch.Tensor                         # [M, K]
+    dist: Optional[torch.Tensor]                 # [B, P, H, W], or [B, J, H*W] with ``gather``
+    act: Optional[torch.Tensor]                  # [M, P]
+    ce: Optional[FusedCrossEntropy] = None       # of ``ce_target``, from whichever kernel carried it
+    gather: Optional[ClassGather] = None         # prototype phase: ``dist`` holds each pixel's own class alone
+    units: Optional[torch.Tensor] = None         # group phase: act . wd^T [M, U] or ``g`` = exp(units), one of the two per branch
+    g: Optional[torch.Tensor] = None
+    wd: Optional[torch.Tensor] = None            # ... and the dense group matrix the forward multiplied with
 
 
 class _PrototypeBankMixin:
@@ -185,11 +199,95 @@ class _PrototypeBankMixin:
         dist = self._scale_head_chain(conv_features)
         act = self.distance_2_similarity(dist).permute(0, 2, 3, 1).reshape(B * H * W, -1)
         logits = self.run_last_layer(act).reshape(B, H, W, -1)
+        return self._result(logits, dist, act, return_activations, return_distances)
+
+    # -- the rules both classes' forward_from_conv_features follow, each stated here alone ---------
+    def _check_patch_classification(self):
+        if not getattr(self, "patch_classification", False):
+            raise Exception("Original Prototype Network Implementation")
+
+    @staticmethod
+    def _wants_distances(return_activations: bool, return_distances: bool) -> bool:
+        return return_distances or not return_activations
+
+    @staticmethod
+    def _result(logits, dist, act, return_activations: bool, return_distances: bool):
+        """The reference's return tuple (model_multiscale.py:377-388)."""
         if return_activations and not return_distances:
             return logits, act
         if return_activations and return_distances:
             return logits, dist, act
         return logits, dist
+
+    @staticmethod
+    def _ce_labels(ce_target, x: torch.Tensor):
+        """``ce_target`` ([B, H, W] on the grid of ``x``, 0 = void, 1..K) as the kernels' int32 [B, H*W] class index, or None."""
+        if ce_target is None:
+            return None
+        B, _, H, W = x.shape
+        if tuple(ce_target.shape) != (B, H, W):
+            raise SpxError(f"ce_target must be [{B}, {H}, {W}] (latent grid), got {tuple(ce_target.shape)}")
+        return shifted_labels_i32(ce_target.reshape(B, -1), x.device)
+
+    @staticmethod
+    def _attach_ce(logits: torch.Tensor, fused_ce, ce_target):
+        if fused_ce is not None:
+            fused_ce.target = ce_target
+            fused_ce.target_version = ce_target._version      # an in-place edit of the labels afterwards voids the attachment
+            logits.spx_ce = fused_ce
+
+    def _refuse_packed(self, ce_target) -> str:
+        """What a ``PackedMaps`` cannot carry, in the order the refusals fire; returns the name the messages go by."""
+        who = "forward_from_conv_features(PackedMaps)"
+        self._check_patch_classification()
+        if ce_target is not None:
+            raise SpxError(f"{who}: ce_target is refused - the fused cross entropy has one mean and one backward coefficient per "
+                           f"launch, the objective one per segment {self._packed_ce_hint}")
+        if self.scale_head is not None:
+            raise SpxError(f"{who}: a scale_head chains launches per scale and has no packed form")
+        if callable(self.prototype_activation_function):
+            raise SpxError(f"{who}: a callable similarity has no packed form ('log' or 'linear')")
+        self._check_1x1()                   # what _check_fusable asks beyond the scale_head refused above
+        return who
+
+    @staticmethod
+    def _split_packed(lay, r: "_HeadOut", want_dist: bool, want_act: bool):
+        """The flat results of ONE launch over ``lay``'s pixel axis -> per segment (logits [B, h_k, w_k, K], distances
+        [B, P, h_k, w_k] or [B, J, h_k w_k], activations [B h_k w_k, P]); what is not wanted is None.  Logits and activations
+        are row slices, distances strided views of the one map; ``torch.split_with_sizes`` gives each output one backward that
+        assembles the packed gradient in a single pass."""
+        none = [None] * len(lay)
+        logits_k = [t.reshape(lay.B, h, w, -1) for t, (h, w) in zip(lay.split_rows(r.logits), lay.grids)]
+        for k, l in enumerate(logits_k):            # segment k of ONE packed forward: SegmentedCrossEntropy runs on ``logits`` as it is
+            l.spx_packed = (r.logits, lay, k, r.logits._version)
+        acts_k = lay.split_rows(r.act) if want_act else none
+        dists_k = list(lay.split_columns(r.dist)) if want_dist else none
+        return logits_k, dists_k, acts_k
+
+    def _callable_similarity(self, conv_features: torch.Tensor):
+        """(distances [B, P, H, W], activations [B*H*W, P]) under a user-supplied ``prototype_activation_function``
+        (model_multiscale.py:329-330: any callable on the distance map): the distance kernel writes the map, the user's function
+        runs on it as ordinary torch code (autograd included); the heads on its NHWC view are the fp32 MFMA product kernels."""
+        B, _, H, W = conv_features.shape
+        _, dist, _ = proto_head_forward(conv_features, self.prototype_vectors, None, self._layout(1), want_distances=True,
+                                        epsilon=self.epsilon, activation="log")
+        return dist, self.prototype_activation_function(dist).permute(0, 2, 3, 1).reshape(B * H * W, -1)
+
+    def _initialize_add_on(self):
+        for m in self.add_on_layers.modules():  # model_multiscale.py:466-476
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def __repr__(self):
+        return (
+            "PPNet(\n\tfeatures: {},\n\timg_size: {},\n\tprototype_shape: {},\n\tproto_layer_rf_info: {},\n"
+            "\tnum_classes: {},\n\tepsilon: {}\n)"
+        ).format(self.features, self.img_size, self.prototype_shape, self.proto_layer_rf_info, self.num_classes, self.epsilon)
 
     def _prune_bank(self, prototypes_to_prune) -> List[int]:
         """The bank half of ``prune_prototypes`` (model_multiscale.py:400-423, :428-432): shrinks ``prototype_vectors``,
@@ -374,129 +472,84 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
             return self._forward_packed(conv_features, return_activations, return_distances, target_labels, ce_target)
         if isinstance(conv_features, list):
             return [self.forward_from_conv_features(c) for c in conv_features]  # flags dropped, as in :359
-        if not (hasattr(self, "patch_classification") and self.patch_classification):
-            raise Exception("Original Prototype Network Implementation")
+        self._check_patch_classification()
         if self.scale_head is not None:
             if target_labels is not None or ce_target is not None:
                 raise SpxError("target_labels / ce_target live in the fused distance kernel's epilogues, which do not carry a scale_head")
             return self._scale_head_forward(conv_features, return_activations, return_distances)
-        self._check_fusable()
+        self._check_1x1()                   # what _check_fusable asks beyond the scale_head that left above
         B, _, H, W = conv_features.shape
         if callable(self.prototype_activation_function):
             return self._forward_callable_similarity(conv_features, return_activations, return_distances, target_labels, ce_target)
-        want_dist = return_distances or not return_activations
-        wide = self.num_classes > MAX_FUSED_HEAD_ROWS          # e.g. scaleproto_coco.gin: 182 classes
-        layout = self._layout(1 if wide else self.num_classes)
-        gather = None
-        if target_labels is not None and want_dist:
-            if tuple(target_labels.shape) != (B, H, W):
-                raise SpxError(f"target_labels must be [{B}, {H}, {W}] (latent grid), got {tuple(target_labels.shape)}")
-            gather = self._class_gather(target_labels, layout, conv_features.device)
-        ce_labels = fused_ce = None
-        if ce_target is not None:
-            if tuple(ce_target.shape) != (B, H, W):
-                raise SpxError(f"ce_target must be [{B}, {H}, {W}] (latent grid), got {tuple(ce_target.shape)}")
-            ce_labels = shifted_labels_i32(ce_target.reshape(B, -1), conv_features.device)
+        want_dist = self._wants_distances(return_activations, return_distances)
+        if target_labels is not None and want_dist and tuple(target_labels.shape) != (B, H, W):
+            raise SpxError(f"target_labels must be [{B}, {H}, {W}] (latent grid), got {tuple(target_labels.shape)}")
+        r = self._head(conv_features, want_dist=want_dist, want_act=return_activations, target_labels=target_labels,
+                       ce_target=ce_target)
+        dist = r.dist
+        if r.gather is not None:
+            dist = ClassDistances(values=dist, labels=r.gather.labels, table=r.gather.table, grid=(H, W), target=target_labels,
+                                  target_version=target_labels._version)
+        logits = r.logits.reshape(B, H, W, -1)
+        self._attach_ce(logits, r.ce, ce_target)
+        return self._result(logits, dist, r.act, return_activations, return_distances)
+
+    def _head(self, x: torch.Tensor, *, want_dist: bool, want_act: bool, target_labels=None, ce_target=None) -> _HeadOut:
+        """Distances, similarity and ``last_layer`` over the pixels of ``x`` ([B, C, H, W], or a packed [1, C, 1, M] with
+        ``target_labels`` [1, M]), on the one branch this bank takes: the whole chain in the distance kernel, or - more classes
+        than its head carries - the kernel hands out the activations once and the head is the fp32 MFMA product kernel
+        (csrc/spx_gemm.hip) on them.  ``target_labels`` count only where distances are wanted (they replace the P-wide map)."""
+        K = self.num_classes
+        wide = K > MAX_FUSED_HEAD_ROWS          # e.g. scaleproto_coco.gin: 182 classes
+        layout = self._layout(1 if wide else K)
+        gather = self._class_gather(target_labels, layout, x.device) if target_labels is not None and want_dist else None
+        ce_labels = self._ce_labels(ce_target, x)
         out = proto_head_forward(
-            conv_features, self.prototype_vectors, None if wide else self.last_layer.weight, layout,
-            want_distances=want_dist and gather is None, want_activations=return_activations or wide,
+            x, self.prototype_vectors, None if wide else self.last_layer.weight, layout,
+            want_distances=want_dist and gather is None, want_activations=want_act or wide,
             epsilon=self.epsilon, activation=self.prototype_activation_function, class_gather=gather,
             ce_labels=None if wide else ce_labels,
         )
         logits, dist, act = out[:3]
-        if wide:      # the kernel hands out the activations once; the 182-row head is the fp32 MFMA product kernel (csrc/spx_gemm.hip) on them
+        ce = None
+        if wide:
             logits = wide_linear(act, self.last_layer.weight)
             if ce_labels is not None:
-                fused_ce = cross_entropy_from_logits(logits, ce_labels)
+                ce = cross_entropy_from_logits(logits, ce_labels)
         elif ce_labels is not None:
-            fused_ce = out[3]
-        if gather is not None:
-            dist = ClassDistances(values=dist, labels=gather.labels, table=gather.table, grid=(H, W), target=target_labels,
-                                  target_version=target_labels._version)
-        logits = logits.reshape(B, H, W, -1)
-        if fused_ce is not None:
-            fused_ce.target = ce_target
-            fused_ce.target_version = ce_target._version      # an in-place edit of the labels afterwards voids the attachment
-            logits.spx_ce = fused_ce
-        if return_activations and not return_distances:
-            return logits, act
-        if return_activations and return_distances:
-            return logits, dist, act
-        return logits, dist
+            ce = out[3]
+        return _HeadOut(logits, dist, act, ce, gather)
+
+    _packed_ce_hint = "(module_multiscale.py:273); call PixelWiseCrossEntropyLoss on each segment's logits"
 
     def _forward_packed(self, pk: PackedMaps, return_activations, return_distances, target_labels, ce_target):
         """The four training maps on one pixel axis (``pk.features`` [1, C, 1, M]): one forward launch - and, through autograd,
-        one pixel-side and one parameter-side backward launch - for all segments.  Distances, activations and logits are
-        per-pixel quantities, so the outputs are split by columns / rows: logits [B, h_k, w_k, K] and activations [B h_k w_k, P]
-        are row slices, distances [B, P, h_k, w_k] strided views of the one map.  ``torch.split_with_sizes`` gives each output
-        one backward that assembles the packed gradient in a single pass."""
-        who = "forward_from_conv_features(PackedMaps)"
-        if not (hasattr(self, "patch_classification") and self.patch_classification):
-            raise Exception("Original Prototype Network Implementation")
-        if ce_target is not None:
-            raise SpxError(f"{who}: ce_target is refused - the fused cross entropy has one mean and one backward coefficient per "
-                           "launch, the objective one per segment (module_multiscale.py:273); call PixelWiseCrossEntropyLoss on "
-                           "each segment's logits")
-        if self.scale_head is not None:
-            raise SpxError(f"{who}: a scale_head chains launches per scale and has no packed form")
-        if callable(self.prototype_activation_function):
-            raise SpxError(f"{who}: a callable similarity has no packed form ('log' or 'linear')")
-        self._check_fusable()
+        one pixel-side and one parameter-side backward launch - for all segments, on the head branch a single map takes.
+        Distances, activations and logits are per-pixel quantities, so the outputs are split by columns / rows
+        (``_split_packed``)."""
+        who = self._refuse_packed(ce_target)
         lay = pk.layout
-        want_dist = return_distances or not return_activations
-        wide = self.num_classes > MAX_FUSED_HEAD_ROWS
-        layout = self._layout(1 if wide else self.num_classes)
-        gather = None
+        want_dist = self._wants_distances(return_activations, return_distances)
         if target_labels is not None:
             lay.check_labels(target_labels, f"{who}: target_labels")                       # before any launch
-            if want_dist:
-                gather = self._class_gather(lay.pack_labels(target_labels), layout, pk.features.device)
-        logits, dist, act = proto_head_forward(
-            pk.features, self.prototype_vectors, None if wide else self.last_layer.weight, layout,
-            want_distances=want_dist and gather is None, want_activations=return_activations or wide,
-            epsilon=self.epsilon, activation=self.prototype_activation_function, class_gather=gather,
-        )[:3]
-        if wide:
-            logits = wide_linear(act, self.last_layer.weight)
-        n = len(lay)
-        logits_k = [t.reshape(lay.B, h, w, -1) for t, (h, w) in zip(lay.split_rows(logits), lay.grids)]
-        for k, l in enumerate(logits_k):            # segment k of ONE packed forward: SegmentedCrossEntropy runs on ``logits`` as it is
-            l.spx_packed = (logits, lay, k, logits._version)
-        acts_k = lay.split_rows(act) if return_activations else [None] * n
-        dists_k = [None] * n
-        if want_dist:
-            dists_k = list(lay.split_columns(dist))
-            if gather is not None:
-                dists_k = [ClassDistances(values=v, labels=gather.labels[0, o:o + m].view(lay.B, -1), table=gather.table, grid=g,
-                                          target=t, target_version=t._version)
-                           for v, o, m, g, t in zip(dists_k, lay.offsets, lay.sizes, lay.grids, target_labels)]
-        out = []
-        for l, d, a in zip(logits_k, dists_k, acts_k):
-            if return_activations and not return_distances:
-                out.append((l, a))
-            elif return_activations and return_distances:
-                out.append((l, d, a))
-            else:
-                out.append((l, d))
-        return out
+        r = self._head(pk.features, want_dist=want_dist, want_act=return_activations,
+                       target_labels=lay.pack_labels(target_labels) if target_labels is not None and want_dist else None)
+        logits_k, dists_k, acts_k = self._split_packed(lay, r, want_dist, return_activations)
+        if r.gather is not None:
+            dists_k = [ClassDistances(values=v, labels=r.gather.labels[0, o:o + m].view(lay.B, -1), table=r.gather.table, grid=g,
+                                      target=t, target_version=t._version)
+                       for v, o, m, g, t in zip(dists_k, lay.offsets, lay.sizes, lay.grids, target_labels)]
+        return [self._result(l, d, a, return_activations, return_distances) for l, d, a in zip(logits_k, dists_k, acts_k)]
 
     def _forward_callable_similarity(self, conv_features, return_activations, return_distances, target_labels, ce_target):
-        """A user-supplied ``prototype_activation_function`` (model_multiscale.py:329-330: any callable on the [B, P, H, W]
-        distance map): the distance kernel writes the map, the user's function runs on it as ordinary torch code (autograd
-        included), and the head is the fp32 MFMA product kernel on its NHWC view - the reference's op order with its two
-        GEMM-shaped pieces on this package's kernels."""
+        """A user-supplied ``prototype_activation_function`` (``_callable_similarity``) and the head on the fp32 MFMA product
+        kernel: the reference's op order with its two GEMM-shaped pieces on this package's kernels."""
         if target_labels is not None or ce_target is not None:
             raise SpxError("target_labels / ce_target need a built-in similarity ('log' or 'linear')")
         B, _, H, W = conv_features.shape
-        _, dist, _ = proto_head_forward(conv_features, self.prototype_vectors, None, self._layout(1), want_distances=True,
-                                        epsilon=self.epsilon, activation="log")
-        act = self.prototype_activation_function(dist).permute(0, 2, 3, 1).reshape(B * H * W, -1)
+        dist, act = self._callable_similarity(conv_features)
         logits = wide_linear(act, self.last_layer.weight).reshape(B, H, W, -1)
-        if return_activations and not return_distances:
-            return logits, act
-        if return_activations and return_distances:
-            return logits, dist, act
-        return logits, dist
+        return self._result(logits, dist, act, return_activations, return_distances)
 
     def prune_prototypes(self, prototypes_to_prune: List[int]):
         """Drop prototype rows and re-pack the scale table (model_multiscale.py:400-432)."""
@@ -512,21 +565,8 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         invalidate_pack_cache()
 
     def _initialize_weights(self):
-        for m in self.add_on_layers.modules():  # :466-476
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-            elif isinstance(m, nn.BatchNorm2d):
-                nn.init.constant_(m.weight, 1)
-                nn.init.constant_(m.bias, 0)
+        self._initialize_add_on()
         self.set_last_layer_incorrect_connection(incorrect_strength=-0.5)
-
-    def __repr__(self):
-        return (
-            "PPNet(\n\tfeatures: {},\n\timg_size: {},\n\tprototype_shape: {},\n\tproto_layer_rf_info: {},\n"
-            "\tnum_classes: {},\n\tepsilon: {}\n)"
-        ).format(self.features, self.img_size, self.prototype_shape, self.proto_layer_rf_info, self.num_classes, self.epsilon)
 
 
 def construct_PPNet(

@@ -20,9 +20,8 @@ import torch.nn as nn
 
 from ._cache import cached
 from .functional import (MAX_FUSED_HEAD_ROWS, MAX_FUSED_TAIL_CLASSES, GroupTables, SpxError, cross_entropy_from_logits,
-                         group_dense, group_exp, invalidate_pack_cache, proto_head_forward, shifted_labels_i32, wide_group_tail,
-                         wide_linear)
-from .model_multiscale import _PrototypeBankMixin, _build_add_on, _first_add_on_channels
+                         group_dense, group_exp, invalidate_pack_cache, proto_head_forward, wide_group_tail, wide_linear)
+from .model_multiscale import _HeadOut, _PrototypeBankMixin, _build_add_on, _first_add_on_channels
 from .msc import PackedMaps
 from .utils import projection_simplex_sort, projection_simplex_sort_
 
@@ -219,148 +218,94 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
             return self._forward_packed(conv_features, return_activations, return_distances, ce_target)
         if isinstance(conv_features, list):
             return [self.forward_from_conv_features(c) for c in conv_features]
-        if not (hasattr(self, "patch_classification") and self.patch_classification):
-            raise Exception("Original Prototype Network Implementation")
+        self._check_patch_classification()
         if self.scale_head is not None:
             if ce_target is not None:
                 raise SpxError("ce_target lives in the fused distance kernel's epilogue, which does not carry a scale_head")
             return self._scale_head_forward(conv_features, return_activations, return_distances)
-        self._check_fusable()
+        self._check_1x1()                   # what _check_fusable asks beyond the scale_head that left above
         B, _, H, W = conv_features.shape
-        wd = self._dense_group_matrix()
         if callable(self.prototype_activation_function):
             # model_multiscale_group.py:393-394: the user's function on the distance map as ordinary torch code; both head
             # products on the fp32 MFMA product kernels
+            wd = self._dense_group_matrix()
             if ce_target is not None:
                 raise SpxError("ce_target needs a built-in similarity ('log' or 'linear')")
-            _, dist, _ = proto_head_forward(conv_features, self.prototype_vectors, None, self._layout(1), want_distances=True,
-                                            epsilon=self.epsilon, activation="log")
-            act = self.prototype_activation_function(dist).permute(0, 2, 3, 1).reshape(B * H * W, -1)
+            dist, act = self._callable_similarity(conv_features)
             units = wide_linear(act, wd)
             act.spx_group = (act._version, units, None)
             logits = wide_group_tail(units, self.last_layer_group.weight).reshape(B, H, W, -1)
-            if return_activations and not return_distances:
-                return logits, act
-            if return_activations and return_distances:
-                return logits, dist, act
-            return logits, dist
-        want_dist = return_distances or not return_activations
-        wg = self.last_layer_group.weight
+            return self._result(logits, dist, act, return_activations, return_distances)
+        r = self._head(conv_features, want_dist=self._wants_distances(return_activations, return_distances),
+                       want_act=return_activations, ce_target=ce_target)
+        if r.act is not None:
+            r.act.spx_group = (r.act._version, r.units, r.g)
+        logits = r.logits.reshape(B, H, W, -1)
+        logits.spx_group_wd = self._group_wd_tag(r.wd)
+        self._attach_ce(logits, r.ce, ce_target)
+        return self._result(logits, r.dist, r.act, return_activations, return_distances)
+
+    def _head(self, x: torch.Tensor, *, want_dist: bool, want_act: bool, ce_target=None) -> _HeadOut:
+        """Distances, similarity and the grouping head over the pixels of ``x`` ([B, C, H, W] or a packed [1, C, 1, M]), on the
+        one branch this bank takes.  The record holds the units or - where the kernel applied the exp itself - exp(units)."""
+        wd, wg = self._dense_group_matrix(), self.last_layer_group.weight
         rows, k2 = int(wd.shape[0]), int(wg.shape[0])
+        ce_labels = self._ce_labels(ce_target, x)
         kw = dict(want_distances=want_dist, epsilon=self.epsilon, activation=self.prototype_activation_function)
-        ce_labels = fused_ce = None
-        if ce_target is not None:
-            if tuple(ce_target.shape) != (B, H, W):
-                raise SpxError(f"ce_target must be [{B}, {H}, {W}] (latent grid), got {tuple(ce_target.shape)}")
-            ce_labels = shifted_labels_i32(ce_target.reshape(B, -1), conv_features.device)
-        if rows <= MAX_FUSED_HEAD_ROWS and k2 <= MAX_FUSED_TAIL_CLASSES:
+        units = g = ce = None
+        units_in_kernel = rows <= MAX_FUSED_HEAD_ROWS
+        if units_in_kernel and k2 <= MAX_FUSED_TAIL_CLASSES:
             # whole grouping head in the kernels: units = act . Wd^T, exp, last_layer_group (:303-308)
-            out = proto_head_forward(
-                conv_features, self.prototype_vectors, wd, self._layout(rows), want_activations=return_activations,
-                group_tail=wg, ce_labels=ce_labels, **kw,
-            )
+            out = proto_head_forward(x, self.prototype_vectors, wd, self._layout(rows), want_activations=want_act, group_tail=wg,
+                                     ce_labels=ce_labels, **kw)
             logits, dist, act = out[:3]
             if ce_labels is not None:
-                fused_ce = out[3]
-            if act is not None:
-                act.spx_group = (act._version, None, out[-1])        # exp(units) [M, U], written by the kernel
-        elif rows <= MAX_FUSED_HEAD_ROWS:
+                ce = out[3]
+            g = out[-1]                                             # exp(units) [M, U], written by the kernel
+        elif units_in_kernel:
             # up to 160 units but more than 32 classes: the unit product stays in the kernel, the tail is the fp32 MFMA product kernel (exp fused into its operand staging)
-            units, dist, act = proto_head_forward(
-                conv_features, self.prototype_vectors, wd, self._layout(rows), want_activations=return_activations, **kw,
-            )
+            units, dist, act = proto_head_forward(x, self.prototype_vectors, wd, self._layout(rows), want_activations=want_act, **kw)
             logits = wide_group_tail(units, wg)
-            if act is not None:
-                act.spx_group = (act._version, units, None)
         else:
             # group_scaleproto_ade.gin (150 classes x 3 groups = 450 units) / _coco.gin (546): the kernel hands out the
             # [pixel][P] activations once, both products are the fp32 MFMA product kernels (csrc/spx_gemm.hip) on them
-            _, dist, act = proto_head_forward(
-                conv_features, self.prototype_vectors, None, self._layout(1), want_activations=True, **kw,
-            )
+            _, dist, act = proto_head_forward(x, self.prototype_vectors, None, self._layout(1), want_activations=True, **kw)
             units = wide_linear(act, wd)
-            act.spx_group = (act._version, units, None)
             logits = wide_group_tail(units, wg)
-        if ce_labels is not None and fused_ce is None:
-            fused_ce = cross_entropy_from_logits(logits, ce_labels)       # heads the fused kernels do not carry
-        logits = logits.reshape(B, H, W, -1)
-        # the dense group matrix this forward multiplied with (GroupRegularizers(logits=...) differentiates through it, so the
-        # group weights receive one scatter for both gradients); the weights' versions void it after an optimiser step
-        logits.spx_group_wd = (wd, self, tuple(gp.weight._version for gp in self.group_projection))
-        if fused_ce is not None:
-            fused_ce.target = ce_target
-            fused_ce.target_version = ce_target._version      # an in-place edit of the labels afterwards voids the attachment
-            logits.spx_ce = fused_ce
-        if return_activations and not return_distances:
-            return logits, act
-        if return_activations and return_distances:
-            return logits, dist, act
-        return logits, dist
+        if ce_labels is not None and ce is None:
+            ce = cross_entropy_from_logits(logits, ce_labels)       # heads the fused kernels do not carry
+        return _HeadOut(logits, dist, act, ce, None, units, g, wd)
+
+    def _group_wd_tag(self, wd: torch.Tensor):
+        """``spx_group_wd``: the dense group matrix a forward multiplied with (GroupRegularizers(logits=...) differentiates
+        through it, so the group weights receive one scatter for both gradients); the weights' versions void it after an
+        optimiser step."""
+        return wd, self, tuple(gp.weight._version for gp in self.group_projection)
+
+    _packed_ce_hint = "(module_multiscale_group_train.py:232-310); call SegmentedCrossEntropy on the segments' logits"
 
     def _forward_packed(self, pk: PackedMaps, return_activations, return_distances, ce_target):
         """The four training maps on one pixel axis (``pk.features`` [1, C, 1, M]; module_multiscale_group_train.py:232,
         forward :396-402): ONE launch of the distance kernel for all segments, then the head branch this bank takes on a single
-        map.  Units, group activations and logits are per-pixel quantities like the distances: logits [B, h_k, w_k, K],
-        activations, units and group activations are row slices (``split_with_sizes``: one backward assembles each packed
-        gradient), distances [B, P, h_k, w_k] strided views.  Every segment's activations carry ``spx_group`` with ITS rows of
-        the one [M, U] tensor - ``compute_group`` returns views of it and a KLD gradient on them enters the one backward as part
-        of dUnits - and every segment's logits carry ``spx_group_wd`` and ``spx_packed`` (``SegmentedCrossEntropy`` then runs
-        on the packed logits as they are)."""
-        who = "forward_from_conv_features(PackedMaps)"
-        if not (hasattr(self, "patch_classification") and self.patch_classification):
-            raise Exception("Original Prototype Network Implementation")
-        if ce_target is not None:
-            raise SpxError(f"{who}: ce_target is refused - the fused cross entropy has one mean and one backward coefficient per "
-                           "launch, the objective one per segment (module_multiscale_group_train.py:232-310); call "
-                           "SegmentedCrossEntropy on the segments' logits")
-        if self.scale_head is not None:
-            raise SpxError(f"{who}: a scale_head chains launches per scale and has no packed form")
-        if callable(self.prototype_activation_function):
-            raise SpxError(f"{who}: a callable similarity has no packed form ('log' or 'linear')")
-        self._check_fusable()
+        map.  Units, group activations and logits are per-pixel quantities like the distances, so they split like them
+        (``_split_packed``; units and group activations are row slices).  Every segment's activations carry ``spx_group`` with
+        ITS rows of the one [M, U] tensor - ``compute_group`` returns views of it and a KLD gradient on them enters the one
+        backward as part of dUnits - and every segment's logits carry ``spx_group_wd`` and ``spx_packed``
+        (``SegmentedCrossEntropy`` then runs on the packed logits as they are)."""
+        self._refuse_packed(ce_target)
         lay = pk.layout
-        wd = self._dense_group_matrix()
-        wg = self.last_layer_group.weight
-        rows, k2 = int(wd.shape[0]), int(wg.shape[0])
-        want_dist = return_distances or not return_activations
-        kw = dict(want_distances=want_dist, epsilon=self.epsilon, activation=self.prototype_activation_function)
-        units = g = None
-        if rows <= MAX_FUSED_HEAD_ROWS and k2 <= MAX_FUSED_TAIL_CLASSES:
-            out = proto_head_forward(pk.features, self.prototype_vectors, wd, self._layout(rows), want_activations=return_activations,
-                                     group_tail=wg, **kw)
-            logits, dist, act = out[:3]
-            g = out[-1] if act is not None else None          # exp(units) [M, U], written by the kernel
-        elif rows <= MAX_FUSED_HEAD_ROWS:
-            units, dist, act = proto_head_forward(pk.features, self.prototype_vectors, wd, self._layout(rows),
-                                                  want_activations=return_activations, **kw)
-            logits = wide_group_tail(units, wg)
-        else:
-            _, dist, act = proto_head_forward(pk.features, self.prototype_vectors, None, self._layout(1), want_activations=True, **kw)
-            units = wide_linear(act, wd)
-            logits = wide_group_tail(units, wg)
-        n = len(lay)
-        versions = tuple(gp.weight._version for gp in self.group_projection)
-        logits_k = [t.reshape(lay.B, h, w, -1) for t, (h, w) in zip(lay.split_rows(logits), lay.grids)]
-        for k, l in enumerate(logits_k):
-            l.spx_group_wd = (wd, self, versions)
-            l.spx_packed = (logits, lay, k, logits._version)
-        acts_k = [None] * n
+        want_dist = self._wants_distances(return_activations, return_distances)
+        r = self._head(pk.features, want_dist=want_dist, want_act=return_activations)
+        logits_k, dists_k, acts_k = self._split_packed(lay, r, want_dist, return_activations)
+        tag = self._group_wd_tag(r.wd)
+        for l in logits_k:
+            l.spx_group_wd = tag
         if return_activations:
-            acts_k = lay.split_rows(act)
-            units_k = lay.split_rows(units) if units is not None else [None] * n
-            g_k = lay.split_rows(g) if g is not None else [None] * n
+            units_k = lay.split_rows(r.units) if r.units is not None else [None] * len(lay)
+            g_k = lay.split_rows(r.g) if r.g is not None else [None] * len(lay)
             for a, u, gg in zip(acts_k, units_k, g_k):
                 a.spx_group = (a._version, u, gg)
-        dists_k = list(lay.split_columns(dist)) if want_dist else [None] * n
-        out = []
-        for l, d, a in zip(logits_k, dists_k, acts_k):
-            if return_activations and not return_distances:
-                out.append((l, a))
-            elif return_activations and return_distances:
-                out.append((l, d, a))
-            else:
-                out.append((l, d))
-        return out
+        return [self._result(l, d, a, return_activations, return_distances) for l, d, a in zip(logits_k, dists_k, acts_k)]
 
     def forward_packed(self, x, **kwargs):
         """``forward`` with MSC's training maps packed (after ``fuse_feature_epilogue(dtype)``): in training
@@ -395,25 +340,12 @@ class PPNetMultiScale(_PrototypeBankMixin, nn.Module):
         invalidate_pack_cache()
 
     def _initialize_weights(self, equiv_path=None, equiv_scale_weight: float = 0.25):
-        for m in self.add_on_layers.modules():  # :493-519
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-            elif isinstance(m, nn.BatchNorm2d):
-                nn.init.constant_(m.weight, 1)
-                nn.init.constant_(m.bias, 0)
+        self._initialize_add_on()  # :493-519
         if equiv_path is not None:
             raise SpxError("equiv_path initialisation is deprecated in the reference (NOT USED) and not built")
         for gp in self.group_projection:
             gp.weight.data = projection_simplex_sort(gp.weight.data)
         self.set_last_layer_incorrect_connection()
-
-    def __repr__(self):
-        return (
-            "PPNet(\n\tfeatures: {},\n\timg_size: {},\n\tprototype_shape: {},\n\tproto_layer_rf_info: {},\n"
-            "\tnum_classes: {},\n\tepsilon: {}\n)"
-        ).format(self.features, self.img_size, self.prototype_shape, self.proto_layer_rf_info, self.num_classes, self.epsilon)
 
 
 PPNetMultiScaleGroup = PPNetMultiScale
