@@ -149,8 +149,9 @@ __global__ __launch_bounds__(SPX_BK_THREADS, 2) void spx_bank_bwd_kernel(const S
     f32x16 accw[NCB];
     float csum[PH];
     // the d_bank accumulators (and colsum) live in the units of the chunk added last (2^e_acc); a chunk of a tile with another
-    // fp16 exponent first multiplies them by the power-of-two ratio (see chunk_scale)
-    int e_acc = 0;
+    // fp16 exponent first multiplies them by the power-of-two ratio (see chunk_scale); e_min: the smallest exponent added so
+    // far, i.e. the largest tile
+    int e_acc = 0, e_min = 0;
     bool have_e = false;
 #pragma unroll
     for (int i = 0; i < PH; ++i) {
@@ -356,11 +357,15 @@ __global__ __launch_bounds__(SPX_BK_THREADS, 2) void spx_bank_bwd_kernel(const S
 
     // d_bank part of one pixel k-step: this wave's prototype blocks x channel blocks 2 cp, 2 cp + 1
     // bring the accumulators to the units of the chunk about to be added (a power-of-two multiply, exact); returns false for
-    // a chunk whose gradients are more than 2^80 below what the accumulators are scaled for: it could not change them
+    // a chunk whose gradients are more than 2^80 below the LARGEST tile added so far: it could not change the sums that tile
+    // entered.  (Against the chunk added last instead, a descending staircase of tiles - each within 2^80 of the one before -
+    // multiplies the first tile's sums by the whole span and takes them past 2^127; so the units never leave
+    // [2^e_min, 2^(e_min + 80)] and the sums, at most 2^22 per chunk in their own units, stay finite.)
     auto chunk_scale = [&]() -> bool {
         const int e_c = __builtin_amdgcn_readfirstlane(ebuf[cur_buf]);
         if (have_e && e_c == e_acc) return true;
-        if (have_e && e_c - e_acc > 80) return false;
+        if (have_e && e_c - e_min > 80) return false;
+        e_min = (have_e && e_min < e_c) ? e_min : e_c;
         const float ratio = have_e ? __builtin_amdgcn_ldexpf(1.0f, e_c - e_acc) : 1.0f;
 #pragma unroll
         for (int i = 0; i < PH; ++i) {
@@ -640,7 +645,7 @@ __global__ __launch_bounds__(SPX_BK_THREADS, 2) void spx_bank_dma_kernel(const S
     auto cs_owner = [&](int i) { return i == 0 ? cs_first : i + 1; };
     f32x16 accp[PH][2];
     float csum[PH];
-    int e_acc = 0;
+    int e_acc = 0, e_min = 0;
     bool have_e = false;
 #pragma unroll
     for (int i = 0; i < PH; ++i) {
@@ -727,7 +732,8 @@ __global__ __launch_bounds__(SPX_BK_THREADS, 2) void spx_bank_dma_kernel(const S
         const char* const Xs = xring + xs * SPX_BD_XUNIT;
         // bring the accumulators to the units of the chunk about to be added (see chunk_scale above)
         const int e_c = __builtin_amdgcn_readfirstlane(*(const int32_t*)(epad + gs * 1024));
-        if (have_e && e_c - e_acc > 80) return;
+        if (have_e && e_c - e_min > 80) return;
+        e_min = (have_e && e_min < e_c) ? e_min : e_c;
         if (!have_e || e_c != e_acc) {
             const float ratio = have_e ? __builtin_amdgcn_ldexpf(1.0f, e_c - e_acc) : 1.0f;
 #pragma unroll
